@@ -1,6 +1,6 @@
 """Benchmark of the embedding-extraction hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one process per GPU.  Under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (the driver's command; RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* from the environment) every rank runs main() directly.  Started plainly (``python bench.py --gpus N``, no WORLD_SIZE in the
@@ -528,6 +528,30 @@ def two_stream_run(name, dev, wav, steps, ref):
             'note': 'front-end + backbone of two 128-utterance halves on two HIP streams, no cosine block; an option of the caller, not the headline'}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: each tensor (all with this rank's B rows) as out_dir/<name>.npy in fp32.  The default run writes a few hundred KB;
+    should they exceed DUMP_LIMIT_BYTES in all (large --batch x many GPUs), every array keeps the same seeded, sorted sample of rows --
+    the same rows for the same arguments -- and rows.npy says which (fp64 row indices)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {name: t.detach().float().cpu() for name, t in arrays.items()}
+    n = {t.shape[0] for t in arrays.values()}
+    assert len(n) == 1, {name: tuple(t.shape) for name, t in arrays.items()}
+    n = n.pop()
+    row_bytes = sum(t[0].numel() * 4 for t in arrays.values())
+    budget = DUMP_LIMIT_BYTES - 4096   # the .npy headers
+    if n * row_bytes > budget:
+        keep = max(1, budget // (row_bytes + 8))   # + 8: the row's fp64 index in rows.npy
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        arrays = {name: t[rows] for name, t in arrays.items()}
+        np.save(os.path.join(out_dir, 'rows.npy'), rows.double().numpy())
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), t.numpy())
+
+
 def self_launch(args):
     """python bench.py --gpus N without a launcher: re-exec under torch.distributed.run with N ranks on this node and hand its exit code back"""
     import socket
@@ -597,7 +621,11 @@ def main():
     ap.add_argument('--cpu-threads', type=int, default=32, help='cap on the torch CPU threads of the oracle baseline')
     ap.add_argument('--no-box', action='store_true', help='skip the box yard-stick (PMC passes: its launches would enter the per-kernel averages)')
     ap.add_argument('--dry-launch', action='store_true', help='N ranks rendezvous (gloo), rank 0 prints what it saw, nothing runs on a device')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="rank 0 writes the last timed step's outputs as DIR/<name>.npy (fp32): embeddings [B, D] "
+                    'and the cosine score block [B, N*B] -- inputs and weights are seeded, so two builds compare output for output')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if 'WORLD_SIZE' not in os.environ and (args.gpus > 1 or args.dry_launch):   # --dry-launch always rendezvouses: also one rank goes through the launcher
         sys.exit(self_launch(args))
@@ -685,6 +713,8 @@ def main():
         elapsed = time.perf_counter() - t0
 
     cdll.mv_profile_enable(0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, embeddings=emb, scores=scores)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if group is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)

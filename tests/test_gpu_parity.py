@@ -1119,3 +1119,27 @@ def test_gpu_bench_under_a_launcher_runs_its_collectives_on_the_rccl_group():
     assert 1500 < box['copy_gbs'] < 8000 and 800 < box['mfma_f16_tflops'] < 2600, box
     assert 0.8 < box['ring_k3072_clock_ghz'] <= box['short_launch_clock_ghz'] + 0.05 and 0.8 < box['mfma_clock_ghz'] < 2.6, box
     assert 0.2 < box['ring_k3072_frac_of_2p5pf'] < box['ring_k3072_frac_at_sustained_clock'] < 1.0, box
+
+
+def test_gpu_bench_dump_outputs_are_the_timed_steps_embeddings_and_scores(tmp_path):
+    """bench.py --dump-outputs: the last timed step's embeddings [B, 192] and cosine block [B, B] as fp32 .npy -- the embeddings are the oracle's
+    for the seeded waveforms and weights (so two builds compare output for output), the scores their cosine matrix."""
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / 'dump'
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT', 'MASTER_ADDR')}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1', '--no-cpu-baseline',
+                        '--no-other-configs', '--no-box', '--dump-outputs', str(out)], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    assert d['steps'] == 2 and d['warmup'] == 1
+    assert sorted(os.listdir(out)) == ['embeddings.npy', 'scores.npy']
+    emb, scores = np.load(out / 'embeddings.npy'), np.load(out / 'scores.npy')
+    assert emb.dtype == np.float32 and emb.shape == (256, 192) and np.isfinite(emb).all()
+    assert scores.dtype == np.float32 and scores.shape == (256, 256)
+    assert np.abs(scores - scoring.cosine_similarity(emb, emb)).max() < 1e-3
+    _, _, state_cpu = bench.build('ecapa1024', torch.device('cpu'))
+    wav = (0.1 * torch.randn([256, bench.SAMPLES], generator=torch.Generator().manual_seed(1234))).clamp(-1, 1)
+    with torch.no_grad():
+        ref, _ = bench.oracle_embeddings('ecapa1024', state_cpu, wav[:4])
+    assert cos_dist(torch.from_numpy(emb[:4]), ref).max() < 1e-4

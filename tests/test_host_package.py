@@ -458,6 +458,31 @@ def test_bench_launches_its_own_ranks_and_fails_clearly_without_devices():
     assert r.returncode != 0 and 'WORLD_SIZE=2' in r.stderr
 
 
+
+def test_bench_dump_outputs_keeps_a_seeded_row_sample_under_64_mb(tmp_path):
+    """bench.py --dump-outputs: small outputs are written whole in fp32; outputs over 64 MB in all keep the same seeded, sorted rows in every
+    array (rows.npy names them), identical from call to call"""
+    import bench
+    emb, scores = torch.randn(256, 192, dtype=torch.float64), torch.randn(256, 256)
+    bench.dump_outputs(str(tmp_path / 'small'), embeddings=emb, scores=scores)
+    assert sorted(os.listdir(tmp_path / 'small')) == ['embeddings.npy', 'scores.npy']
+    e = np.load(tmp_path / 'small' / 'embeddings.npy')
+    assert e.dtype == np.float32 and np.array_equal(e, emb.float().numpy())
+    emb, scores = torch.randn(4096, 192), torch.randn(4096, 4 * 4096)   # 272 MB
+    for d in ('big_a', 'big_b'):
+        bench.dump_outputs(str(tmp_path / d), embeddings=emb, scores=scores)
+    files = sorted(os.listdir(tmp_path / 'big_a'))
+    assert files == ['embeddings.npy', 'rows.npy', 'scores.npy']
+    assert sum(os.path.getsize(tmp_path / 'big_a' / f) for f in files) <= 64 << 20
+    rows = np.load(tmp_path / 'big_a' / 'rows.npy')
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 0 < len(rows) < 4096
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / 'big_a' / 'embeddings.npy'), emb[r].numpy())
+    assert np.array_equal(np.load(tmp_path / 'big_a' / 'scores.npy'), scores[r].numpy())
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / 'big_a' / f), np.load(tmp_path / 'big_b' / f))
+
+
 SYNC_WORKER = r'''
 import os, sys, json, torch, torch.distributed as dist
 sys.path[:0] = [sys.argv[1], os.path.join(sys.argv[1], "tests"), os.path.join(sys.argv[1], "voiceprintrecognition-pytorch_amd")]

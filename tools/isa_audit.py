@@ -5,14 +5,14 @@ the number of s_waitcnt vmcnt(0) and how many of them stand directly in front of
 time -- a load under one `if` and its use under another, or two load forms under complementary lane masks into the same registers).
 Round 5 finds (profiles/r14k-o): cam_dense_block_kernel (36 lone MFMAs, 54 FLAT loads, two drains per layer), conv2ds_kernel (28-41 wait-then-load),
 linear_f32_splitk_kernel (12), fcm_block_kernel<5, 2, true> (15: measured, no effect).
-usage: python tools/isa_audit.py [file.hip ...]      (writes /tmp/isa_audit/<file>.s)"""
+usage: python tools/isa_audit.py [file.hip ...]      (writes voiceprintrecognition-pytorch_amd/build/isa_audit/<file>.s, git-ignored)"""
 import glob, os, re, subprocess, sys
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, 'voiceprintrecognition-pytorch_amd')
 sys.path.insert(0, PKG)
 import build_native
 
-OUT = '/tmp/isa_audit'
+OUT = os.path.join(build_native.OBJ_DIR, 'isa_audit')   # inside this checkout: no directory shared with other users or checkouts
 
 
 def audit(files=None):

@@ -1,10 +1,11 @@
 """Register loads inside blocks a forward branch may skip (s_cbranch_* .LBBx ... .LBBx:), per kernel, from the assembly tools/isa_audit.py leaves under
-/tmp/isa_audit (run that first): at the join the compiler's wait-count insertion assumes such a load was NOT issued, so every later s_waitcnt vmcnt(N) counts it
+voiceprintrecognition-pytorch_amd/build/isa_audit (run that first): at the join the compiler's wait-count insertion assumes such a load was NOT issued, so every later s_waitcnt vmcnt(N) counts it
 out and comes out too strict (\"skippable blocks\"; the Res2Net chain's fragment requests, round 6).
 usage: python tools/isa_audit.py >/dev/null; python tools/isa_cond_loads.py | sort -t= -k2 -n -r | head -40"""
-import re, glob, subprocess
+import re, glob, os, subprocess
+ASM_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'voiceprintrecognition-pytorch_amd', 'build', 'isa_audit')
 # register loads that sit in a block a forward branch may skip (s_cbranch_* .LBBx ... .LBBx:), i.e. loads the wait-count insertion must assume "not issued" at the join
-for asm in sorted(glob.glob('/tmp/isa_audit/*.s')):
+for asm in sorted(glob.glob(os.path.join(ASM_DIR, '*.s'))):
     kernel = None; lines = []
     ks = {}
     for line in open(asm):
