@@ -180,6 +180,71 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
                        mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Front-end 3: Spectrogram (power STFT, the linear-frequency bins are the features) + time-mean
+ * subtraction + mask.  Replaces torchaudio.transforms.Spectrogram(**method_args) (featurizer.py:43-44)
+ * and featurizer.py:77-90.  Output [B, T, n_fft / 2 + 1].  The STFT fields mean what they mean in
+ * MvMelSpecCfg.  n_fft = 400: one launch (melspec_tile_kernel's FFT); any other n_fft: dense DFT +
+ * spec_cmn_mask_kernel.  Additive since ABI 5.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct MvSpectrogramCfg {
+    int32_t n_fft;       /* 400 */
+    int32_t win_length;  /* 400 (<= n_fft) */
+    int32_t hop_length;  /* 200 */
+    int32_t pad;         /* 0 */
+    float power;         /* 2.0; any positive exponent of |X| (power=None, the complex spectrogram, is refused) */
+    int32_t normalized;  /* MV_STFT_NORM_* */
+    int32_t center;      /* 1 */
+    int32_t pad_mode;    /* MV_STFT_PAD_* */
+    int32_t subtract_time_mean; /* 1 */
+    const float* window; /* NULL = periodic Hann | HOST array [win_length] (copied at create) */
+} MvSpectrogramCfg;
+
+typedef struct MvSpectrogram MvSpectrogram;
+
+void mv_spectrogram_default_cfg(MvSpectrogramCfg* cfg);
+int mv_spectrogram_create(const MvSpectrogramCfg* cfg, MvSpectrogram** out);
+/* *kernel = 1 for the fused n_fft = 400 launch, 0 for the dense DFT */
+int mv_spectrogram_info(const MvSpectrogram* h, int32_t* kernel);
+int mv_spectrogram_destroy(MvSpectrogram* h);
+int mv_spectrogram_num_frames(const MvSpectrogram* h, int64_t num_samples, int64_t* num_frames);
+size_t mv_spectrogram_workspace_bytes(const MvSpectrogram* h, int32_t B, int64_t L);
+int mv_spectrogram_forward(const MvSpectrogram* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                           const float* lens_ratio, float* out, void* workspace, size_t workspace_bytes,
+                           mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Front-end 4: MFCC (mel power -> dB with a top_db floor, or log(mel + 1e-6) -> DCT-II) + time-mean
+ * subtraction + mask.  Replaces torchaudio.transforms.MFCC(**method_args) and featurizer.py:77-90.
+ * Output [B, T, n_mfcc].  With log_mels = 0 the floor is (max dB over the WHOLE batch of the call)
+ * - top_db, as torchaudio's amplitude_to_DB on a [B, n_mels, T] tensor: a row's features depend on
+ * the other rows of the call.  The batch max stays on the device (no host synchronisation).
+ * Additive since ABI 5.
+ * ------------------------------------------------------------------------------------------------ */
+enum { MV_DCT_NORM_NONE = 0, MV_DCT_NORM_ORTHO = 1 };
+
+typedef struct MvMfccCfg {
+    MvMelSpecCfg mel;    /* the mel stage (subtract_time_mean is ignored: the mean is taken of the coefficients) */
+    int32_t n_mfcc;      /* 40, <= mel.n_mels */
+    int32_t dct_norm;    /* MV_DCT_NORM_ORTHO (1) | MV_DCT_NORM_NONE */
+    int32_t log_mels;    /* 0 */
+    float top_db;        /* 80 (>= 0) */
+    int32_t subtract_time_mean; /* 1 */
+} MvMfccCfg;
+
+typedef struct MvMfcc MvMfcc;
+
+void mv_mfcc_default_cfg(MvMfccCfg* cfg);
+int mv_mfcc_create(const MvMfccCfg* cfg, MvMfcc** out);
+/* *mel_kernel = what mv_melspec_info reports for the mel stage; *dct_lds = 1 when the DCT table is held in LDS */
+int mv_mfcc_info(const MvMfcc* h, int32_t* mel_kernel, int32_t* dct_lds);
+int mv_mfcc_destroy(MvMfcc* h);
+int mv_mfcc_num_frames(const MvMfcc* h, int64_t num_samples, int64_t* num_frames);
+size_t mv_mfcc_workspace_bytes(const MvMfcc* h, int32_t B, int64_t L);
+int mv_mfcc_forward(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                    const float* lens_ratio, float* out, void* workspace, size_t workspace_bytes,
+                    mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Backbones.  A model handle is built from the reference-layout fp32 ``state_dict`` (same key names
  * and shapes as the reference modules, so ``model.pth`` loads unchanged: mvector/utils/checkpoint.py:
  * 11-51).  create() folds eval-mode BatchNorm into per-channel scale/shift, packs conv weights to the

@@ -21,6 +21,7 @@
 #include "frontend_common.h"
 #include "kernels.h"
 #include "melfft.h"
+#include "spectral.h"
 
 namespace mv {
 
@@ -209,8 +210,9 @@ struct MelTileArgs {
     const float* window;      // [400]
     const float* tw400;       // [13 k1][16 n2][2] cos, sin of 2 pi n2 k1 / 400
     const float* melb;        // MFMA B-operand order (frontend_common.h)
-    int B, T, hop, pad, n_mels, cmn, tile_rows;
+    int B, T, hop, pad, n_mels, cmn, tile_rows;   // SPEC: n_mels = 201 bins
     MelPlan plan;
+    float power;              // SPEC: exponent of |X| (the mel instantiation takes 2)
 };
 
 // real 5-point DFT: X[d] = sum_a v[a] W5^(a d); returns X[0] (real) and X[1], X[2] (X[5-d] = conj X[d])
@@ -255,7 +257,9 @@ __device__ __forceinline__ cplx mul_w25(cplx z) {
     return cmul_conjtw(z, C[M], S[M]);
 }
 
-template <int G0, int G1>
+// SPEC = true (G0 = G1 = 0): the Spectrogram front-end -- the 201 power bins of every frame are the features themselves; lane l owns
+// bins l + 64 j (j = 0..3) of the wave's four frames for the time mean, and the rows are 201 floats (no 16-byte row alignment).
+template <int G0, int G1, bool SPEC = false>
 __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArgs a) {
     constexpr int THREADS = MST_WAVES * 64;
     MV_DYN_SMEM(smem);
@@ -277,7 +281,7 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
     float2v ctw[13];
 #pragma unroll
     for (int k1 = 1; k1 < 13; ++k1) ctw[k1] = *reinterpret_cast<const float2v*>(a.tw400 + 2 * (k1 * 16 + l16));
-    float4v mb0[G0], mb1[G1 > 0 ? G1 : 1];
+    float4v mb0[G0 > 0 ? G0 : 1], mb1[G1 > 0 ? G1 : 1];
 #pragma unroll
     for (int g = 0; g < G0; ++g) mb0[g] = *reinterpret_cast<const float4v*>(a.melb + (size_t)g * 256 + lane * 4);
 #pragma unroll
@@ -297,12 +301,13 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
     const float* ap0 = arow + a.plan.pass_start[0][lane >> 2];
     const float* ap1 = arow + a.plan.pass_start[1][lane >> 2];
     const int blk = lane >> 2;
-    const int split0 = a.plan.pass_split[0], split1 = a.plan.pass_split[1];
+    const int split0 = SPEC ? 1 : a.plan.pass_split[0], split1 = SPEC ? 1 : a.plan.pass_split[1];
     const int m0 = 4 * (a.plan.pass_gbase[0] + blk / split0) + (lane & 3);
     const int m1 = 4 * (a.plan.pass_gbase[1] + blk / split1) + (lane & 3);
     const bool own0 = m0 < nm && (blk & (split0 - 1)) == 0;
     const bool own1 = G1 > 0 && m1 < nm && (blk & (split1 - 1)) == 0;
     float csum0 = 0.0f, csum1 = 0.0f;
+    float csum_s[4] = {0.0f, 0.0f, 0.0f, 0.0f};   // SPEC: bins lane + 64 j
     const int tile_rows = a.tile_rows;  // multiple of 4
 
     const int nquads = (T + 3) >> 2;
@@ -389,6 +394,29 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
             }
         }
         MV_WAVE_FENCE();
+        if constexpr (SPEC) {
+            const int frames_here = (q * 4 + 4 <= T) ? 4 : T - q * 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (r >= frames_here) break;
+                const float* pr = wslot + r * MST_PSTR;
+                auto dl = MV_AS_LDS(float, tile + (q * 4 + r) * nm);
+                auto dg = MV_AS_GLOBAL(float, orow + (int64_t)(q * 4 + r) * nm);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int bin = lane + 64 * j;
+                    if (bin < nm) {
+                        const float p = pr[bin];
+                        const float v = a.power == 2.0f ? p : (a.power == 1.0f ? sqrtf(p) : powf(p, 0.5f * a.power));   // as stft_power_kernel
+                        csum_s[j] += v;
+                        if (q * 4 < tile_rows) dl[bin] = v;   // uniform: rows held in LDS / rows that go through global memory
+                        else dg[bin] = v;
+                    }
+                }
+            }
+            MV_WAVE_FENCE();  // the power rows are consumed
+            return;
+        }
         // ---- banded mel on the matrix pipe ----
         const float4v zero4 = float4v{0.0f, 0.0f, 0.0f, 0.0f};
         float4v acc0[4], acc1[4];
@@ -469,8 +497,14 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
 
     // ---- per-utterance time mean over ALL frames (featurizer.py:79), mask, single write of the rows held in LDS ----
     __syncthreads();
-    if (own0) colsum[wave * 256 + m0] = csum0;
-    if (own1) colsum[wave * 256 + m1] = csum1;
+    if constexpr (SPEC) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (lane + 64 * j < 256) colsum[wave * 256 + lane + 64 * j] = csum_s[j];
+    } else {
+        if (own0) colsum[wave * 256 + m0] = csum0;
+        if (own1) colsum[wave * 256 + m1] = csum1;
+    }
     __syncthreads();
     float* mean = colsum + MST_WAVES * 256;
     if (tid < 256) {
@@ -482,6 +516,18 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
     __syncthreads();
     int mask_len = T;
     if (a.lens_ratio != nullptr) mask_len = (int)rintf(a.lens_ratio[b] * (float)T);
+    if constexpr (SPEC) {   // rows of 201 floats: element-wise, consecutive threads on consecutive addresses
+        const int held = T < tile_rows ? T : tile_rows;
+        for (int i = tid; i < held * nm; i += THREADS) {
+            const int t = i / nm, c = i - t * nm;
+            orow[i] = t < mask_len ? tile[i] - mean[c] : 0.0f;
+        }
+        for (int i = held * nm + tid; i < T * nm; i += THREADS) {
+            const int t = i / nm, c = i - t * nm;
+            orow[i] = t < mask_len ? orow[i] - mean[c] : 0.0f;
+        }
+        return;
+    }
     const int qn = nm >> 2;  // n_mels % 4 == 0 for this kernel
     const int rows_per_pass = THREADS / qn;
     const int r0 = tid / qn, cg = tid - r0 * qn;
@@ -532,10 +578,40 @@ __global__ __launch_bounds__(256) void cmn_mask_kernel(float* out, int T, int C,
     }
 }
 
+// Spectrogram rows: P [b * T + t][ldp] (stft_power_kernel's padded bin rows) -> out [b][t][C] minus the time mean over ALL frames, frames
+// t >= round_half_even(ratio * T) zeroed.  One workgroup per utterance; sums in the fixed order of cmn_mask_kernel.
+__global__ __launch_bounds__(256) void spec_cmn_mask_kernel(const float* P, int ldp, float* out, int T, int C, const float* lens_ratio, int cmn) {
+    __shared__ float part[4][64];
+    __shared__ float mean[64];
+    const int b = blockIdx.x;
+    const float* p = P + (int64_t)b * T * ldp;
+    float* o = out + (int64_t)b * T * C;
+    const int tid = threadIdx.x;
+    int mask_len = T;
+    if (lens_ratio != nullptr) mask_len = (int)rintf(lens_ratio[b] * (float)T);
+    for (int c0 = 0; c0 < C; c0 += 64) {
+        const int c = c0 + (tid & 63);
+        const int ph = tid >> 6;
+        float s = 0.0f;
+        if (c < C)
+            for (int t = ph; t < T; t += 4) s += p[(int64_t)t * ldp + c];
+        part[ph][tid & 63] = s;
+        __syncthreads();
+        if (tid < 64) mean[tid] = cmn ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)T : 0.0f;
+        __syncthreads();
+        if (c < C) {
+            const float m = mean[tid & 63];
+            for (int t = ph; t < T; t += 4) o[(int64_t)t * C + c] = t < mask_len ? p[(int64_t)t * ldp + c] - m : 0.0f;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace mv
 
 struct MvMelSpec {
     MvMelSpecCfg cfg;
+    bool spectrogram = false;   // the Spectrogram front-end (mv_spectrogram_*, spectral.hip): the power bins are the features, no mel stage
     int nbin, nbin_pad, kpad, pad;
     bool pre_pad = false;   // cfg.pad > 0 or a centre padding other than reflect: melspec_extend_kernel writes the extended signal to the workspace first
     float* d_window = nullptr;
@@ -589,7 +665,11 @@ void mv_melspec_default_cfg(MvMelSpecCfg* cfg) {
     cfg->pad_mode = MV_STFT_PAD_REFLECT;
 }
 
-int mv_melspec_create(const MvMelSpecCfg* cfg, MvMelSpec** out) {
+int mv_melspec_create(const MvMelSpecCfg* cfg, MvMelSpec** out) { return mv::melspec_create_mode(cfg, false, out); }
+
+}  // extern "C"
+
+int mv::melspec_create_mode(const MvMelSpecCfg* cfg, bool spectrogram, MvMelSpec** out) {
     MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_melspec_create: null argument");
     MV_REQUIRE(cfg->n_fft >= 4 && cfg->n_fft <= 8192, "mv_melspec_create: n_fft out of range");
     MV_REQUIRE(cfg->win_length >= 1 && cfg->win_length <= cfg->n_fft, "mv_melspec_create: win_length must be in [1, n_fft]");
@@ -604,6 +684,7 @@ int mv_melspec_create(const MvMelSpecCfg* cfg, MvMelSpec** out) {
     MV_REQUIRE(cfg->pad_mode >= MV_STFT_PAD_REFLECT && cfg->pad_mode <= MV_STFT_PAD_CIRCULAR, "mv_melspec_create: unknown pad_mode");
     MvMelSpec* h = new MvMelSpec();
     h->cfg = *cfg;
+    h->spectrogram = spectrogram;
     h->cfg.window = nullptr;   // (the caller's host array is read below and not kept)
     const int n_fft = cfg->n_fft;
     h->nbin = n_fft / 2 + 1;
@@ -669,6 +750,28 @@ int mv_melspec_create(const MvMelSpecCfg* cfg, MvMelSpec** out) {
         mv_melspec_destroy(h);
         return rc;
     }
+    // ---- Spectrogram: melspec_tile_kernel's FFT with the power bins as the features (n_fft = 400), the dense DFT otherwise ----
+    if (spectrogram) {
+        if (n_fft == 400) {
+            std::vector<float> tw(13 * 16 * 2);
+            for (int k1 = 0; k1 < 13; ++k1)
+                for (int n2 = 0; n2 < 16; ++n2) {
+                    tw[2 * (k1 * 16 + n2)] = (float)cos(2.0 * pi * (n2 * k1) / 400.0);
+                    tw[2 * (k1 * 16 + n2) + 1] = (float)sin(2.0 * pi * (n2 * k1) / 400.0);
+                }
+            if ((rc = upload_vec(tw, &h->d_tw400))) {
+                mv_melspec_destroy(h);
+                return rc;
+            }
+            h->tile_kernel = true;
+            if (MV_SET_MAX_SMEM((mv::melspec_tile_kernel<0, 0, true>), 160 * 1024) != hipSuccess) {
+                mv_melspec_destroy(h);
+                return mv::fail(MV_ERR_HIP, "mv_spectrogram_create: cannot reserve dynamic LDS for melspec_tile_kernel");
+            }
+        }
+        *out = h;
+        return MV_OK;
+    }
     // ---- FFT path (melspec_tile_kernel) when the geometry matches ----
     if (n_fft == 400 && cfg->power == 2.0f && (cfg->n_mels & 3) == 0 && cfg->n_mels <= 128) {
         std::vector<std::vector<float>> banks(cfg->n_mels, std::vector<float>(h->nbin, 0.0f));
@@ -722,6 +825,8 @@ int mv_melspec_create(const MvMelSpecCfg* cfg, MvMelSpec** out) {
     *out = h;
     return MV_OK;
 }
+
+extern "C" {
 
 int mv_melspec_info(const MvMelSpec* h, int32_t* tile_kernel) {
     MV_REQUIRE(h != nullptr && tile_kernel != nullptr, "mv_melspec_info: null argument");
@@ -799,12 +904,28 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
     } else if (h->cfg.center) {
         MV_REQUIRE(L > h->pad, "mv_melspec_forward: reflect padding needs more than n_fft/2 samples (torch.stft raises too)");
     }
-    if (h->tile_kernel && (int64_t)T * h->cfg.n_mels < ((int64_t)1 << 31)) {
+    if (h->spectrogram && h->tile_kernel && (int64_t)T * h->nbin < ((int64_t)1 << 31)) {
+        mv::MelTileArgs t = {};
+        t.wav = wav; t.wav_stride = wav_stride; t.L = L; t.lens_ratio = lens_ratio; t.out = out;
+        t.window = h->d_window; t.tw400 = h->d_tw400; t.melb = nullptr;
+        t.B = B; t.T = (int)T; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->nbin; t.cmn = h->cfg.subtract_time_mean;
+        t.power = h->cfg.power;
+        // as many 201-float rows as fit next to the wave slots stay in LDS (136); the rest go through global memory
+        const size_t slots = (size_t)mv::MST_WAVES * mv::MST_SLOT_FLOATS * sizeof(float);
+        int64_t rows = (int64_t)((160 * 1024 - slots) / ((size_t)h->nbin * sizeof(float))) & ~(int64_t)3;
+        const int64_t need = (T + 3) & ~(int64_t)3;
+        t.tile_rows = (int)(rows < need ? rows : need);
+        const size_t smem = slots + (size_t)t.tile_rows * h->nbin * sizeof(float);
+        MV_LAUNCH((mv::melspec_tile_kernel<0, 0, true>), ((unsigned)B, 1, 1), (mv::MST_WAVES * 64, 1, 1), smem, static_cast<hipStream_t>(stream), t);
+        return mv::check_launch("melspec_tile_kernel<spectrogram>");
+    }
+    if (!h->spectrogram && h->tile_kernel && (int64_t)T * h->cfg.n_mels < ((int64_t)1 << 31)) {
         mv::MelTileArgs t;
         t.wav = wav; t.wav_stride = wav_stride; t.L = L; t.lens_ratio = lens_ratio; t.out = out;
         t.window = h->d_window; t.tw400 = h->d_tw400; t.melb = h->d_melb;
         t.B = B; t.T = (int)T; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->cfg.n_mels; t.cmn = h->cfg.subtract_time_mean;
         t.plan = h->plan;
+        t.power = 2.0f;
         // feature rows that fit next to the wave slots stay in LDS until the time mean is known; the rest go through global memory
         const size_t slots = (size_t)mv::MST_WAVES * mv::MST_SLOT_FLOATS * sizeof(float);
         int64_t rows = (int64_t)((160 * 1024 - slots) / ((size_t)h->cfg.n_mels * sizeof(float))) & ~(int64_t)3;
@@ -816,7 +937,7 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
         mv::prof_end(prof, static_cast<hipStream_t>(stream));
         return mv::check_launch("melspec_tile_kernel");
     }
-    if (h->pow2_kernel && (int64_t)T * h->cfg.n_mels < ((int64_t)1 << 31)) {
+    if (!h->spectrogram && h->pow2_kernel && (int64_t)T * h->cfg.n_mels < ((int64_t)1 << 31)) {
         mv::MelFftArgs t;
         t.wav = wav; t.wav_stride = wav_stride; t.L = L; t.lens_ratio = lens_ratio; t.out = out;
         t.window = h->d_window; t.tw512 = h->d_tw512; t.w1024 = h->d_w1024; t.melb = h->d_melb;
@@ -860,6 +981,11 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
     MV_LAUNCH(mv::stft_power_kernel<7>, (gx, gy, 1), (256, 1, 1), 0, st, a);
     int rc = mv::check_launch("stft_power_kernel");
     if (rc != MV_OK) return rc;
+    if (h->spectrogram) {
+        MV_LAUNCH(mv::spec_cmn_mask_kernel, ((unsigned)B, 1, 1), (256, 1, 1), 0, st, a.P, h->nbin_pad, out, (int)T, h->nbin, lens_ratio,
+                  h->cfg.subtract_time_mean);
+        return mv::check_launch("spec_cmn_mask_kernel");
+    }
     rc = mv::linear_f32_launch(a.P, h->nbin_pad, h->d_fbT, h->nbin_pad, nullptr, MV_ACT_NONE, out, h->cfg.n_mels, (int)nframes,
                                h->nbin, h->cfg.n_mels, 0, st);
     if (rc != MV_OK) return rc;

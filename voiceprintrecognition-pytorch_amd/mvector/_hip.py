@@ -36,6 +36,16 @@ class MvMelSpecCfg(ctypes.Structure):
                 ('pad', c_i32), ('pad_mode', c_i32)]
 
 
+class MvSpectrogramCfg(ctypes.Structure):
+    _fields_ = [('n_fft', c_i32), ('win_length', c_i32), ('hop_length', c_i32), ('pad', c_i32), ('power', c_f32), ('normalized', c_i32),
+                ('center', c_i32), ('pad_mode', c_i32), ('subtract_time_mean', c_i32), ('window', c_vp)]
+
+
+class MvMfccCfg(ctypes.Structure):
+    _fields_ = [('mel', MvMelSpecCfg), ('n_mfcc', c_i32), ('dct_norm', c_i32), ('log_mels', c_i32), ('top_db', c_f32),
+                ('subtract_time_mean', c_i32)]
+
+
 class MvTensorRef(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char_p), ('data', c_vp), ('numel', c_i64)]
 
@@ -137,6 +147,20 @@ _SIGNATURES = {
     'mv_profile_read': (c_i32, [c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_i32]),
     'mv_wave_prepare_i16': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
     'mv_asp_pool_f16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    'mv_spectrogram_default_cfg': (None, [ctypes.POINTER(MvSpectrogramCfg)]),
+    'mv_spectrogram_create': (c_i32, [ctypes.POINTER(MvSpectrogramCfg), ctypes.POINTER(c_vp)]),
+    'mv_spectrogram_info': (c_i32, [c_vp, ctypes.POINTER(c_i32)]),
+    'mv_spectrogram_destroy': (c_i32, [c_vp]),
+    'mv_spectrogram_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
+    'mv_spectrogram_workspace_bytes': (c_sz, [c_vp, c_i32, c_i64]),
+    'mv_spectrogram_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_mfcc_default_cfg': (None, [ctypes.POINTER(MvMfccCfg)]),
+    'mv_mfcc_create': (c_i32, [ctypes.POINTER(MvMfccCfg), ctypes.POINTER(c_vp)]),
+    'mv_mfcc_info': (c_i32, [c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
+    'mv_mfcc_destroy': (c_i32, [c_vp]),
+    'mv_mfcc_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
+    'mv_mfcc_workspace_bytes': (c_sz, [c_vp, c_i32, c_i64]),
+    'mv_mfcc_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_fcm_conv3x3_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'mv_fcm_block_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
     'mv_fcm_block_c1_f16': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
@@ -318,6 +342,15 @@ class MelSpec:
         self._cdll = cdll or lib()
         cfg = MvMelSpecCfg()
         self._cdll.mv_melspec_default_cfg(ctypes.byref(cfg))
+        win_host = self.fill_cfg(cfg, method_args, subtract_time_mean)  # noqa: F841  (alive until create has copied it)
+        self.n_mels = cfg.n_mels
+        self._h = c_vp()
+        check(self._cdll.mv_melspec_create(ctypes.byref(cfg), ctypes.byref(self._h)), self._cdll)
+
+    @classmethod
+    def fill_cfg(cls, cfg, method_args, subtract_time_mean=True):
+        """MelSpectrogram(**method_args) checked as torchaudio checks it, into an MvMelSpecCfg (also the mel stage of Mfcc); returns the
+        host window tensor that cfg.window points to (None for the default), which must stay alive until create"""
         a = dict(method_args or {})
         allowed = {'sample_rate', 'n_fft', 'win_length', 'hop_length', 'f_min', 'f_max', 'pad', 'n_mels', 'power',
                    'normalized', 'center', 'pad_mode', 'onesided', 'norm', 'mel_scale', 'window_fn', 'wkwargs'}
@@ -327,7 +360,7 @@ class MelSpec:
         # not implemented: two-sided spectra (torchaudio's own MelScale refuses their bin count), power=None (a complex spectrogram has no mel scale)
         if a.get('onesided') not in (None, True) or a.get('power', 2.0) is None:
             raise NotImplementedError('MelSpectrogram option not implemented by the HIP kernel')
-        if a.get('pad_mode', 'reflect') not in self.PAD_MODES:
+        if a.get('pad_mode', 'reflect') not in cls.PAD_MODES:
             raise NotImplementedError(f"Unrecognised padding mode {a.get('pad_mode')}")   # (torch.nn.functional.pad's own error class)
         if a.get('norm') not in (None, 'slaney'):
             raise ValueError('norm must be one of None or "slaney"')          # torchaudio.functional.melscale_fbanks' own messages
@@ -352,16 +385,14 @@ class MelSpec:
         cfg.norm = 1 if a.get('norm') == 'slaney' else 0
         cfg.normalized = {False: 0, True: 1, 'window': 1, 'frame_length': 2}[a.get('normalized', False)]
         cfg.pad = int(a.get('pad', 0))
-        cfg.pad_mode = self.PAD_MODES[a.get('pad_mode', 'reflect')]
+        cfg.pad_mode = cls.PAD_MODES[a.get('pad_mode', 'reflect')]
         win_host = None
         if a.get('window_fn') is not None:   # torchaudio evaluates window_fn(win_length, **wkwargs) once, at construction: so does this
             win_host = a['window_fn'](cfg.win_length, **(a.get('wkwargs') or {})).detach().to(device='cpu', dtype=torch.float32).contiguous()
             if win_host.shape != (cfg.win_length,):
                 raise ValueError(f'window_fn returned {tuple(win_host.shape)}, expected ({cfg.win_length},)')
             cfg.window = win_host.data_ptr()
-        self.n_mels = cfg.n_mels
-        self._h = c_vp()
-        check(self._cdll.mv_melspec_create(ctypes.byref(cfg), ctypes.byref(self._h)), self._cdll)
+        return win_host
 
     def info(self):
         """{'tile_kernel': bool, 'kernel': name}: True when an FFT kernel runs -- melspec_tile_kernel (n_fft = 400) or melspec_pow2_kernel
@@ -398,6 +429,143 @@ class MelSpec:
                 self._cdll.mv_melspec_destroy(self._h)
         except Exception:
             pass
+
+
+_SPEC_KEYS = ('n_fft', 'win_length', 'hop_length', 'pad', 'window_fn', 'power', 'normalized', 'wkwargs', 'center', 'pad_mode', 'onesided',
+              'return_complex')
+_MFCC_KEYS = ('sample_rate', 'n_mfcc', 'dct_type', 'norm', 'log_mels', 'melkwargs')
+
+
+def _stft_fields(cfg, a, what):
+    """the STFT keyword arguments torchaudio's Spectrogram / MelSpectrogram share, checked as torchaudio checks them, into `cfg`;
+    returns the host window tensor (kept alive by the caller until create has copied it) or None"""
+    if a.get('onesided') not in (None, True) or ('power' in a and a['power'] is None):
+        raise NotImplementedError(f'{what} option not implemented by the HIP kernel')   # complex / two-sided output
+    if a.get('pad_mode', 'reflect') not in MelSpec.PAD_MODES:
+        raise NotImplementedError(f"Unrecognised padding mode {a.get('pad_mode')}")
+    if a.get('normalized', False) not in (False, True, 'window', 'frame_length'):
+        raise ValueError(f"Invalid normalized parameter: {a.get('normalized')}")
+    cfg.n_fft = int(a.get('n_fft', 400))
+    win = a.get('win_length')
+    cfg.win_length = int(win if win is not None else cfg.n_fft)
+    hop = a.get('hop_length')
+    cfg.hop_length = int(hop if hop is not None else cfg.win_length // 2)
+    cfg.power = float(a.get('power', 2.0))
+    cfg.center = 1 if a.get('center', True) else 0
+    cfg.normalized = {False: 0, True: 1, 'window': 1, 'frame_length': 2}[a.get('normalized', False)]
+    cfg.pad = int(a.get('pad', 0))
+    cfg.pad_mode = MelSpec.PAD_MODES[a.get('pad_mode', 'reflect')]
+    win_host = None
+    if a.get('window_fn') is not None:
+        win_host = a['window_fn'](cfg.win_length, **(a.get('wkwargs') or {})).detach().to(device='cpu', dtype=torch.float32).contiguous()
+        if win_host.shape != (cfg.win_length,):
+            raise ValueError(f'window_fn returned {tuple(win_host.shape)}, expected ({cfg.win_length},)')
+        cfg.window = win_host.data_ptr()
+    return win_host
+
+
+class _FrontEnd:
+    """shared forward of the Spectrogram / MFCC handles: [B, L] fp32 -> [B, T, dim] with the caller's stream and a workspace per call"""
+    _prefix = None
+
+    def num_frames(self, num_samples):
+        t = c_i64()
+        check(getattr(self._cdll, self._prefix + 'num_frames')(self._h, num_samples, ctypes.byref(t)), self._cdll)
+        return t.value
+
+    def __call__(self, wav, lens_ratio=None):
+        assert wav.dim() == 2 and wav.dtype == torch.float32
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+        B, L = wav.shape
+        T = self.num_frames(L)
+        out = torch.empty((B, T, self.dim), dtype=torch.float32, device=wav.device)
+        if B == 0 or T == 0:
+            return out
+        if lens_ratio is not None:
+            lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
+        nbytes = getattr(self._cdll, self._prefix + 'workspace_bytes')(self._h, B, L)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=wav.device)
+        check(getattr(self._cdll, self._prefix + 'forward')(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(),
+                                                            ws.data_ptr(), nbytes, current_stream(wav)), self._cdll)
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, '_h', None):
+                getattr(self._cdll, self._prefix + 'destroy')(self._h)
+        except Exception:
+            pass
+
+
+class Spectrogram(_FrontEnd):
+    """Handle of the Spectrogram + CMN + mask path (mv_spectrogram_*): torchaudio.transforms.Spectrogram(**method_args), then
+    AudioFeaturizer's time mean and mask.  Output [B, T, n_fft // 2 + 1]."""
+    _prefix = 'mv_spectrogram_'
+
+    def __init__(self, method_args=None, subtract_time_mean=True, cdll=None):
+        self._cdll = cdll or lib()
+        a = dict(method_args or {})
+        for k in a:
+            if k not in _SPEC_KEYS:
+                raise TypeError(f"Spectrogram got an unexpected keyword argument '{k}'")
+        cfg = MvSpectrogramCfg()
+        self._cdll.mv_spectrogram_default_cfg(ctypes.byref(cfg))
+        win_host = _stft_fields(cfg, a, 'Spectrogram')  # noqa: F841  (alive until create has copied it)
+        cfg.subtract_time_mean = 1 if subtract_time_mean else 0
+        self.dim = cfg.n_fft // 2 + 1
+        self._h = c_vp()
+        check(self._cdll.mv_spectrogram_create(ctypes.byref(cfg), ctypes.byref(self._h)), self._cdll)
+
+    def info(self):
+        """{'kernel': name}: the fused n_fft = 400 launch or the dense DFT"""
+        k = c_i32()
+        check(self._cdll.mv_spectrogram_info(self._h, ctypes.byref(k)), self._cdll)
+        return {'kernel': {0: 'stft_power_kernel (dense DFT)', 1: 'melspec_tile_kernel (spectrogram)'}[k.value]}
+
+
+class Mfcc(_FrontEnd):
+    """Handle of the MFCC + CMN + mask path (mv_mfcc_*): torchaudio.transforms.MFCC(**method_args), then AudioFeaturizer's time mean
+    and mask.  Output [B, T, n_mfcc].  With log_mels=False the top_db floor is taken over the whole batch of the call, as torchaudio does."""
+    _prefix = 'mv_mfcc_'
+
+    def __init__(self, method_args=None, subtract_time_mean=True, cdll=None):
+        self._cdll = cdll or lib()
+        a = dict(method_args or {})
+        for k in a:
+            if k not in _MFCC_KEYS:
+                raise TypeError(f"MFCC got an unexpected keyword argument '{k}'")
+        # torchaudio.transforms.MFCC.__init__: the DCT type, then the mel stage, then the coefficient count, then create_dct's norm
+        if a.get('dct_type', 2) != 2:
+            raise ValueError(f"DCT type not supported: {a.get('dct_type')}")
+        melkwargs = dict(a.get('melkwargs') or {})
+        if 'sample_rate' in melkwargs:
+            raise TypeError("MelSpectrogram got multiple values for keyword argument 'sample_rate'")
+        melkwargs['sample_rate'] = a.get('sample_rate', 16000)
+        cfg = MvMfccCfg()
+        self._cdll.mv_mfcc_default_cfg(ctypes.byref(cfg))
+        self._mel_window = MelSpec.fill_cfg(cfg.mel, melkwargs, subtract_time_mean=False)
+        n_mfcc = int(a.get('n_mfcc', 40))
+        if n_mfcc > cfg.mel.n_mels:
+            raise ValueError('Cannot select more MFCC coefficients than # mel bins')
+        if a.get('norm', 'ortho') not in (None, 'ortho'):
+            raise AssertionError(f"norm must be None or 'ortho', got {a.get('norm')!r}")   # (create_dct asserts)
+        cfg.n_mfcc = n_mfcc
+        cfg.dct_norm = 1 if a.get('norm', 'ortho') == 'ortho' else 0
+        cfg.log_mels = 1 if a.get('log_mels', False) else 0
+        cfg.top_db = 80.0
+        cfg.subtract_time_mean = 1 if subtract_time_mean else 0
+        self.dim = n_mfcc
+        self._h = c_vp()
+        check(self._cdll.mv_mfcc_create(ctypes.byref(cfg), ctypes.byref(self._h)), self._cdll)
+        self._mel_window = None
+
+    def info(self):
+        """{'mel_kernel': name of the mel stage's kernel, 'dct_lds': bool}"""
+        k, d = c_i32(), c_i32()
+        check(self._cdll.mv_mfcc_info(self._h, ctypes.byref(k), ctypes.byref(d)), self._cdll)
+        return {'mel_kernel': {0: 'stft_power_kernel (dense DFT)', 1: 'melspec_tile_kernel', 2: 'melspec_pow2_kernel'}[k.value],
+                'dct_lds': bool(d.value)}
 
 
 class Model:

@@ -1,4 +1,4 @@
-"""Host-tensor front-end: batched torch implementation of Kaldi Fbank / MelSpectrogram + CMN + mask.
+"""Host-tensor front-end: batched torch implementation of Kaldi Fbank / MelSpectrogram / Spectrogram / MFCC + CMN + mask.
 
 Used only for CPU tensors (``use_gpu=False`` predictors and DataLoader worker processes, exactly where the
 reference runs its featurizer, mvector/data_utils/featurizer.py:53-91).  CUDA tensors never come here: they go
@@ -22,6 +22,9 @@ _FBANK_IGNORED = ()
 _WINDOWS = ('povey', 'hamming', 'hanning', 'rectangular', 'blackman')
 _MEL_KEYS = {'sample_rate', 'n_fft', 'win_length', 'hop_length', 'f_min', 'f_max', 'pad', 'n_mels', 'power',
              'normalized', 'center', 'pad_mode', 'onesided', 'norm', 'mel_scale', 'window_fn', 'wkwargs'}
+_SPEC_KEYS = {'n_fft', 'win_length', 'hop_length', 'pad', 'window_fn', 'power', 'normalized', 'wkwargs', 'center', 'pad_mode', 'onesided',
+              'return_complex'}
+_MFCC_KEYS = {'sample_rate', 'n_mfcc', 'dct_type', 'norm', 'log_mels', 'melkwargs'}
 
 
 def validate_args(method, args):
@@ -36,6 +39,31 @@ def validate_args(method, args):
                     raise NotImplementedError(f'Fbank argument {k}={v!r} is not implemented')
             else:
                 raise TypeError(f"fbank() got an unexpected keyword argument '{k}'")
+    elif method == 'Spectrogram':
+        for k in args:
+            if k not in _SPEC_KEYS:
+                raise TypeError(f"Spectrogram got an unexpected keyword argument '{k}'")
+        if args.get('onesided') not in (None, True) or ('power' in args and args['power'] is None):
+            raise NotImplementedError('Spectrogram option not implemented')   # complex / two-sided output
+        if args.get('pad_mode', 'reflect') not in ('reflect', 'constant', 'replicate', 'circular'):
+            raise NotImplementedError(f"Unrecognised padding mode {args.get('pad_mode')}")
+        if args.get('normalized', False) not in (False, True, 'window', 'frame_length'):
+            raise ValueError(f"Invalid normalized parameter: {args.get('normalized')}")
+    elif method == 'MFCC':
+        # torchaudio.transforms.MFCC.__init__, in its order: dct_type, the mel stage, n_mfcc against n_mels, create_dct's norm
+        for k in args:
+            if k not in _MFCC_KEYS:
+                raise TypeError(f"MFCC got an unexpected keyword argument '{k}'")
+        if args.get('dct_type', 2) != 2:
+            raise ValueError(f"DCT type not supported: {args.get('dct_type')}")
+        melkwargs = dict(args.get('melkwargs') or {})
+        if 'sample_rate' in melkwargs:
+            raise TypeError("MelSpectrogram got multiple values for keyword argument 'sample_rate'")
+        validate_args('MelSpectrogram', melkwargs)
+        if int(args.get('n_mfcc', 40)) > int(melkwargs.get('n_mels', 128)):
+            raise ValueError('Cannot select more MFCC coefficients than # mel bins')
+        if args.get('norm', 'ortho') not in (None, 'ortho'):
+            raise AssertionError(f"norm must be None or 'ortho', got {args.get('norm')!r}")
     elif method == 'MelSpectrogram':
         for k in args:
             if k not in _MEL_KEYS:
@@ -198,6 +226,57 @@ def _mel_fbank(sr, n_fft, f_min, f_max, n_mels, mel_scale, norm):
     return fb
 
 
+def spectrogram_batch(wav, args):
+    """[B, L] -> [B, frames, n_fft // 2 + 1] power spectrogram (no CMN): torchaudio.transforms.Spectrogram(**args) (torchaudio.functional.spectrogram)"""
+    n_fft = int(args.get('n_fft', 400))
+    win = args.get('win_length')
+    win = int(win if win is not None else n_fft)
+    hop = args.get('hop_length')
+    hop = int(hop if hop is not None else win // 2)
+    power = float(args.get('power', 2.0))
+    window = args['window_fn'](win, **(args.get('wkwargs') or {})).float() if args.get('window_fn') is not None else torch.hann_window(win)
+    normalized = args.get('normalized', False)
+    if int(args.get('pad', 0)) > 0:
+        wav = torch.nn.functional.pad(wav, (int(args['pad']), int(args['pad'])), 'constant')
+    spec = torch.stft(wav, n_fft, hop, win, window, center=bool(args.get('center', True)), pad_mode=args.get('pad_mode', 'reflect'),
+                      normalized=normalized == 'frame_length', onesided=True, return_complex=True)
+    if normalized in (True, 'window'):
+        spec = spec / window.pow(2.0).sum().sqrt()
+    spec = spec.abs()
+    if power != 1.0:
+        spec = spec.pow(power)
+    return spec.transpose(1, 2)
+
+
+@functools.lru_cache(maxsize=8)
+def _dct_matrix(n_mfcc, n_mels, norm):
+    """torchaudio.functional.create_dct: [n_mels, n_mfcc] fp32"""
+    n = torch.arange(float(n_mels))
+    k = torch.arange(float(n_mfcc)).unsqueeze(1)
+    dct = torch.cos(math.pi / float(n_mels) * (n + 0.5) * k)
+    if norm is None:
+        dct *= 2.0
+    else:
+        dct[0] *= 1.0 / math.sqrt(2.0)
+        dct *= math.sqrt(2.0 / float(n_mels))
+    return dct.t().contiguous()
+
+
+def mfcc_batch(wav, args):
+    """[B, L] -> [B, frames, n_mfcc] (no CMN): torchaudio.transforms.MFCC(**args).  With log_mels=False the top_db = 80 floor is ONE
+    maximum over the whole [B, n_mels, T] batch (torchaudio.functional.amplitude_to_DB packs B as channels of one item)."""
+    melkwargs = dict(args.get('melkwargs') or {})
+    melkwargs['sample_rate'] = args.get('sample_rate', 16000)
+    mel = melspec_batch(wav, melkwargs)   # [B, T, n_mels]
+    if args.get('log_mels', False):
+        mel = torch.log(mel + 1e-6)
+    else:
+        mel = 10.0 * torch.log10(torch.clamp(mel, min=1e-10))
+        if mel.numel() > 0:
+            mel = torch.max(mel, mel.amax() - 80.0)
+    return mel @ _dct_matrix(int(args.get('n_mfcc', 40)), mel.shape[2], args.get('norm', 'ortho'))
+
+
 def melspec_batch(wav, args):
     """[B, L] -> [B, frames, n_mels] mel spectrogram (no log, no CMN): torchaudio.transforms.MelSpectrogram(**args)"""
     sr = int(args.get('sample_rate', 16000))
@@ -227,7 +306,7 @@ def melspec_batch(wav, args):
 
 
 def featurize(wav, lens_ratio, method, args):
-    feats = fbank_batch(wav, args) if method == 'Fbank' else melspec_batch(wav, args)
+    feats = {'Fbank': fbank_batch, 'MelSpectrogram': melspec_batch, 'Spectrogram': spectrogram_batch, 'MFCC': mfcc_batch}[method](wav, args)
     feats = feats - feats.mean(1, keepdim=True)  # time mean over ALL frames (featurizer.py:79)
     if lens_ratio is not None:
         T = feats.shape[1]

@@ -3,8 +3,10 @@
 
 Device rule
 -----------
-* CUDA (ROCm) tensors: ``mv_fbank_forward`` / ``mv_melspec_forward`` -- waveform batch in HBM ->
-  STFT + mel + (log) + time-mean subtraction + length mask in one pass, output on the same device.
+* CUDA (ROCm) tensors: ``mv_fbank_forward`` / ``mv_melspec_forward`` / ``mv_spectrogram_forward`` / ``mv_mfcc_forward`` --
+  waveform batch in HBM -> STFT (+ mel + log / dB + DCT) + time-mean subtraction + length mask, output on the same device.
+  MFCC with ``log_mels=False`` floors the dB at (loudest value of the whole call) - 80, as torchaudio does on a batch: a row's
+  MFCC features depend on the other rows of the same call (``forward_varlen`` featurises each row alone).
   There is no fallback on this path: a missing libmvector_hip.so raises.
 * CPU tensors (``use_gpu=False`` predictors, DataLoader worker processes after fork -- they must not touch
   HIP): a batched torch implementation of the same arithmetic (``_cpu_frontend``), as the reference itself
@@ -23,7 +25,7 @@ from mvector.utils.logger import logger
 class AudioFeaturizer(nn.Module):
     """音频特征器
 
-    :param feature_method: 所使用的预处理方法 (``Fbank`` / ``MelSpectrogram`` on the accelerated path)
+    :param feature_method: 所使用的预处理方法 (``Fbank`` / ``MelSpectrogram`` / ``Spectrogram`` / ``MFCC``)
     :param use_hf_model: HuggingFace feature models are outside the accelerated path
     :param method_args: 预处理方法的参数
     """
@@ -38,9 +40,6 @@ class AudioFeaturizer(nn.Module):
                                       'MI355X embedding path; use Fbank or MelSpectrogram')
         if feature_method not in ('Fbank', 'MelSpectrogram', 'Spectrogram', 'MFCC'):
             raise Exception(f'预处理方法 {self._feature_method} 不存在!')
-        if feature_method in ('Spectrogram', 'MFCC'):
-            raise NotImplementedError(f'{feature_method} is not part of the accelerated path (no BASELINE config uses '
-                                      f'it); use Fbank or MelSpectrogram')
         _cpu_frontend.validate_args(feature_method, self._method_args)
         self._native = {}  # device index -> native handle (built lazily; never pickled)
         logger.info(f'使用【{feature_method}】提取特征')
@@ -58,6 +57,10 @@ class AudioFeaturizer(nn.Module):
             with torch.cuda.device(key):
                 if self._feature_method == 'Fbank':
                     h = _hip.Fbank(self._method_args)
+                elif self._feature_method == 'Spectrogram':
+                    h = _hip.Spectrogram(self._method_args)
+                elif self._feature_method == 'MFCC':
+                    h = _hip.Mfcc(self._method_args)
                 else:
                     h = _hip.MelSpec(self._method_args)
             self._native[key] = h
