@@ -260,7 +260,8 @@ typedef struct MvModel MvModel;
 
 /* EcapaTdnn.forward (mvector/models/ecapa_tdnn.py:253-283), pooling_type "ASP". */
 typedef struct MvEcapaCfg {
-    int32_t input_size;          /* F */
+    int32_t input_size;          /* F, any positive width: not a multiple of 8 -> zero-padded to round_up(F, 8) on the device (bits of that width
+                                  * with zero-padded features and first-layer weights) */
     int32_t embd_dim;            /* 192 */
     int32_t channels[5];         /* {512,512,512,512,1536} */
     int32_t kernel_sizes[5];     /* {5,3,3,3,1} */
@@ -293,7 +294,7 @@ int mv_campp_create(const MvCamppCfg* cfg, const MvTensorRef* tensors, int32_t n
 
 /* TDNN.forward (mvector/models/tdnn.py:46-68), pooling_type "ASP". */
 typedef struct MvTdnnCfg {
-    int32_t input_size;
+    int32_t input_size; /* F, any positive width: not a multiple of 8 -> a zero-padded fp32 copy at round_up(F, 8) in the workspace */
     int32_t channels; /* 512 */
     int32_t embd_dim; /* 192 */
 } MvTdnnCfg;

@@ -85,6 +85,10 @@ int seg_mean_launch(const half_t* x, int64_t ld, int B, int T, int C, int seg_le
 int se_gate_residual_launch(const half_t* y, int64_t ldy, const float* gate, const half_t* res, int64_t ldr, half_t* out,
                             int64_t ldo, int B, int T, int C, hipStream_t stream);
 int cast_reflect_pad_launch(const float* src, half_t* dst, int B, int T, int C, int pad, hipStream_t stream);
+// ragged feature width F: destination pitch ldd = round_up(F, 8), columns F..ldd-1 zero (any F; the model takes it for F % 8 != 0)
+int cast_reflect_pad_ragged_launch(const float* src, half_t* dst, int B, int T, int F, int ldd, int pad, hipStream_t stream);
+// fp32 rows of width F copied to pitch ldd (a multiple of 4), columns F..ldd-1 zero
+int pad_rows_f32_launch(const float* src, int F, float* dst, int64_t ldd, int64_t n_rows, hipStream_t stream);
 int cast_rows_f32_f16_launch(const float* src, int64_t lds_, half_t* dst, int64_t ldd, int64_t n_rows, int C, hipStream_t stream);
 int copy_slice_launch(const half_t* src, int64_t lds_, half_t* dst, int64_t ldd, int C, int64_t n_rows, hipStream_t stream);
 bool res2_chain_supported(int T, int width, int steps, int k, int dil);

@@ -339,7 +339,7 @@ struct EcapaModel : MvModelBase {
         ConvLayer shortcut;
     };
     TdnnBlk block0, mfa;
-    ConvLayer block0w;         // block 0 as a 1x1 conv over the contiguous k*F window of the reflect-padded features
+    ConvLayer block0w;         // block 0 as a 1x1 conv over the contiguous k*Fp window of the reflect-padded features
     bool block0_window = false;
     std::vector<SeRes2> blocks;
     AspLayer asp;
@@ -359,21 +359,36 @@ struct EcapaModel : MvModelBase {
         embd_dim = c.embd_dim;
         int rc;
         MV_REQUIRE(c.res2net_scale >= 2 && c.res2net_scale <= 16, "ecapa: res2net_scale out of range");
-        if ((rc = make_tdnn(w, "blocks.0", c.channels[0], c.input_size, c.kernel_sizes[0], &block0))) return rc;
-        // Channel-last features with F % 8 == 0 and a dilation-1 first conv: the k taps of output step t are the k*F
-        // CONTIGUOUS values starting at row t of the reflect-padded features, so block 0 is a 1x1 conv with cin = k*F and
-        // row stride F (rows overlap).  K = 5*80 = 400 -> 7 stages of 64 instead of 5 taps x 128 (80 padded) = 10.
-        block0_window = c.dilations[0] == 1 && c.input_size % 8 == 0 && c.kernel_sizes[0] > 1 && (c.kernel_sizes[0] % 2) == 1;
+        MV_REQUIRE(c.input_size > 0, "ecapa: input_size must be positive");
+        // The features enter block 0 at the pitch Fp = round_up(F, 8) (the fp16 copy of forward(); for a ragged F its channels F..Fp-1 are
+        // zeros), and block 0's weights get zero input columns F..Fp-1: a zero weight times a finite feature adds an exact zero, so F = 201
+        // computes the bits of F = 208 with zero-padded features and weights.  For F % 8 == 0 nothing is padded.
+        const int F = c.input_size, Fp = (int)round_up(F, 8), k0 = c.kernel_sizes[0], C0 = c.channels[0];
+        if (Fp == F) {
+            if ((rc = make_tdnn(w, "blocks.0", C0, F, k0, &block0))) return rc;
+        } else {
+            std::vector<float> w0, wp((size_t)C0 * Fp * k0, 0.0f);
+            if ((rc = w.host("blocks.0.conv.conv.weight", (int64_t)C0 * F * k0, w0))) return rc;
+            for (int co = 0; co < C0; ++co)
+                memcpy(&wp[(size_t)co * Fp * k0], &w0[(size_t)co * F * k0], (size_t)F * k0 * sizeof(float));
+            float* tmp = upload(wp);
+            if (tmp == nullptr) return fail(MV_ERR_HIP, "ecapa create: upload failed");
+            if ((rc = make_conv_from(tmp, &w, "blocks.0.conv.conv.bias", C0, Fp, k0, &block0.conv))) return rc;
+            if ((rc = make_bn(w, "blocks.0.norm.norm", C0, &block0.scale, &block0.shift))) return rc;
+        }
+        // Channel-last features and a dilation-1 first conv: the k taps of output step t are the k*Fp CONTIGUOUS values starting at row t
+        // of the reflect-padded features, so block 0 is a 1x1 conv with cin = k*Fp and row stride Fp (rows overlap).
+        // K = 5*80 = 400 -> 7 stages of 64 instead of 5 taps x 128 (80 padded) = 10.
+        block0_window = c.dilations[0] == 1 && k0 > 1 && (k0 % 2) == 1;
         if (block0_window) {
-            const int F = c.input_size, k0 = c.kernel_sizes[0], C0 = c.channels[0];
-            std::vector<float> w0, wr((size_t)C0 * k0 * F);
+            std::vector<float> w0, wr((size_t)C0 * k0 * Fp, 0.0f);
             if ((rc = w.host("blocks.0.conv.conv.weight", (int64_t)C0 * F * k0, w0))) return rc;
             for (int co = 0; co < C0; ++co)
                 for (int ci = 0; ci < F; ++ci)
-                    for (int j = 0; j < k0; ++j) wr[((size_t)co * k0 + j) * F + ci] = w0[((size_t)co * F + ci) * k0 + j];
+                    for (int j = 0; j < k0; ++j) wr[((size_t)co * k0 + j) * Fp + ci] = w0[((size_t)co * F + ci) * k0 + j];
             float* tmp = upload(wr);
             if (tmp == nullptr) return fail(MV_ERR_HIP, "ecapa create: upload failed");
-            if ((rc = make_conv_from(tmp, &w, "blocks.0.conv.conv.bias", C0, k0 * F, 1, &block0w))) return rc;
+            if ((rc = make_conv_from(tmp, &w, "blocks.0.conv.conv.bias", C0, k0 * Fp, 1, &block0w))) return rc;
         }
         nblocks = 3;
         blocks.resize(nblocks);
@@ -471,16 +486,21 @@ struct EcapaModel : MvModelBase {
         if (s.bytes > ws_bytes) return fail(MV_ERR_WORKSPACE, "ecapa forward: workspace too small");
         int rc;
         const int R = MV_PAD_REFLECT;
-        // features to fp16 once (12 MB), then blocks.0 on the direct-to-LDS path
-        const int64_t ldf = round_up(cfg.input_size, 8);
+        // features to fp16 once (12 MB) at the pitch ldf = round_up(F, 8) (zeros in channels F..ldf-1), then blocks.0 on the direct-to-LDS path
+        const int F = cfg.input_size;
+        const int64_t ldf = round_up(F, 8);
         const int pad0 = cfg.dilations[0] * (cfg.kernel_sizes[0] - 1) / 2;
         if (block0_window) {
-            if ((rc = cast_reflect_pad_launch(feats, s.x16, B, T, cfg.input_size, pad0, st))) return rc;
-            if ((rc = run_conv(block0w, s.x16, MV_DT_F16, cfg.input_size, nullptr, 0, s.a0, MV_DT_F16, cfg.channels[0], B, T + 2 * pad0, T,
+            if (ldf == F) {
+                if ((rc = cast_reflect_pad_launch(feats, s.x16, B, T, F, pad0, st))) return rc;
+            } else {
+                if ((rc = cast_reflect_pad_ragged_launch(feats, s.x16, B, T, F, (int)ldf, pad0, st))) return rc;
+            }
+            if ((rc = run_conv(block0w, s.x16, MV_DT_F16, ldf, nullptr, 0, s.a0, MV_DT_F16, cfg.channels[0], B, T + 2 * pad0, T,
                                1, 0, MV_PAD_ZERO, MV_ACT_RELU, block0.scale, block0.shift, MV_ACT_NONE, nullptr, true, st)))
                 return rc;
         } else {
-            if ((rc = cast_rows_f32_f16_launch(feats, cfg.input_size, s.x16, ldf, (int64_t)B * T, cfg.input_size, st))) return rc;
+            if ((rc = cast_rows_f32_f16_launch(feats, F, s.x16, ldf, (int64_t)B * T, F, st))) return rc;
             if ((rc = run_conv(block0.conv, s.x16, MV_DT_F16, ldf, nullptr, 0, s.a0, MV_DT_F16, cfg.channels[0], B, T, T,
                                cfg.dilations[0], pad0, R, MV_ACT_RELU, block0.scale, block0.shift, MV_ACT_NONE, nullptr, true, st)))
                 return rc;
@@ -582,11 +602,24 @@ struct TdnnModel : MvModelBase {
         input_size = c.input_size;
         embd_dim = c.embd_dim;
         MV_REQUIRE(c.channels % 8 == 0, "tdnn: channels must be a multiple of 8");
+        MV_REQUIRE(c.input_size > 0, "tdnn: input_size must be positive");
         int rc;
+        // td_layer1 reads the features at the pitch Fp = round_up(F, 8): for a ragged F a zero-padded fp32 copy (forward()), and its weights
+        // get zero input columns F..Fp-1 -- the bits of F = Fp with zero-padded features and weights
+        const int F = c.input_size, Fp = (int)round_up(F, 8);
         for (int i = 0; i < 5; ++i) {
             const std::string p = "td_layer" + std::to_string(i + 1);
-            if ((rc = make_conv(w, p + ".weight", p + ".bias", c.channels, i == 0 ? c.input_size : c.channels, K[i], &conv[i])))
+            if (i == 0 && Fp != F) {
+                std::vector<float> w0, wp((size_t)c.channels * Fp * K[0], 0.0f);
+                if ((rc = w.host(p + ".weight", (int64_t)c.channels * F * K[0], w0))) return rc;
+                for (int co = 0; co < c.channels; ++co)
+                    memcpy(&wp[(size_t)co * Fp * K[0]], &w0[(size_t)co * F * K[0]], (size_t)F * K[0] * sizeof(float));
+                float* tmp = upload(wp);
+                if (tmp == nullptr) return fail(MV_ERR_HIP, "tdnn create: upload failed");
+                if ((rc = make_conv_from(tmp, &w, p + ".bias", c.channels, Fp, K[0], &conv[0]))) return rc;
+            } else if ((rc = make_conv(w, p + ".weight", p + ".bias", c.channels, i == 0 ? F : c.channels, K[i], &conv[i]))) {
                 return rc;
+            }
             if (i < 4)
                 if ((rc = make_bn(w, "bn" + std::to_string(i + 1), c.channels, &scale[i], &shift[i]))) return rc;
         }
@@ -600,11 +633,12 @@ struct TdnnModel : MvModelBase {
 
     struct Ws {
         half_t *a, *b, *h;
-        float *asp_f, *pooled;
+        float *asp_f, *pooled, *xp;
         size_t bytes;
     };
     Ws carve(void* base, int B, int T) const {
         const size_t N = (size_t)B * T;
+        const int64_t Fp = round_up(cfg.input_size, 8);
         Carver c(base);
         Ws s;
         s.a = c.take<half_t>(N * cfg.channels);
@@ -612,6 +646,7 @@ struct TdnnModel : MvModelBase {
         s.h = c.take<half_t>(N * 128);
         s.asp_f = c.take<float>(asp.workspace_floats(B, T));
         s.pooled = c.take<float>((size_t)B * 2 * cfg.channels);
+        s.xp = Fp != cfg.input_size ? c.take<float>(N * Fp) : nullptr;   // zero-padded features of a ragged F
         s.bytes = c.total();
         return s;
     }
@@ -629,6 +664,11 @@ struct TdnnModel : MvModelBase {
         const void* x = feats;
         int xdt = MV_DT_F32;
         int64_t ldx = cfg.input_size;
+        if (s.xp != nullptr) {
+            ldx = round_up(cfg.input_size, 8);
+            if ((rc = pad_rows_f32_launch(feats, cfg.input_size, s.xp, ldx, (int64_t)B * T, st))) return rc;
+            x = s.xp;
+        }
         int Tin = T;
         half_t* bufs[2] = {s.a, s.b};
         for (int i = 0; i < 5; ++i) {

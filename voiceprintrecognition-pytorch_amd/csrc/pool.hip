@@ -318,6 +318,65 @@ int cast_reflect_pad_launch(const float* src, half_t* dst, int B, int T, int C, 
     return check_launch("cast_reflect_pad_kernel");
 }
 
+// The same for a feature width F that is not a multiple of 8: source rows of F floats (a row starts 4-byte aligned only), destination rows of
+// pitch ldd = round_up(F, 8) halves whose columns F..ldd-1 are written as exact zeros.  One lane = 8 destination channels (one 16-byte store);
+// its loads are guarded scalar loads, which the lanes of a wave still issue as consecutive 32-byte runs of the row.
+__global__ __launch_bounds__(256) void cast_reflect_pad_ragged_kernel(const float* src, half_t* dst, int B, int T, int F, int ldd, int pad) {
+    const int Tp = T + 2 * pad, G = ldd >> 3;
+    const int total = B * Tp * G;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+        const int g = i % G, r = i / G;
+        const int b = r / Tp;
+        int t = r - b * Tp - pad;
+        t = t < 0 ? -t : (t >= T ? 2 * (T - 1) - t : t);
+        const float* s = src + ((int64_t)b * T + t) * F;
+        const int c0 = g * 8;
+        half8v o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float v = c0 + j < F ? s[c0 + j] : 0.0f;
+            o[j] = (half_t)fminf(fmaxf(v, -65504.0f), 65504.0f);
+        }
+        *reinterpret_cast<half8v*>(dst + (int64_t)i * 8) = o;
+    }
+}
+
+int cast_reflect_pad_ragged_launch(const float* src, half_t* dst, int B, int T, int F, int ldd, int pad, hipStream_t stream) {
+    MV_REQUIRE(src != nullptr && dst != nullptr, "cast_reflect_pad_ragged: null tensor");
+    MV_REQUIRE(B > 0 && T > 0 && F > 0 && ldd >= F && ldd % 8 == 0, "cast_reflect_pad_ragged: bad shape (ldd must be a multiple of 8, at least F)");
+    MV_REQUIRE(pad >= 0 && pad < T, "cast_reflect_pad_ragged: reflect padding needs 0 <= pad < T");
+    const int64_t total = (int64_t)B * (T + 2 * pad) * (ldd / 8);
+    MV_REQUIRE(total < (int64_t)1 << 31, "cast_reflect_pad_ragged: batch too large");
+    const int grid = ew_grid(total);
+    MV_LAUNCH(cast_reflect_pad_ragged_kernel, (grid, 1, 1), (256, 1, 1), 0, stream, src, dst, B, T, F, ldd, pad);
+    return check_launch("cast_reflect_pad_ragged_kernel");
+}
+
+// dst[n, 0:F] = src[n, 0:F], dst[n, F:ldd] = 0 in fp32: features of a ragged width F at a pitch the conv loader accepts (TDNN td_layer1, which
+// reads fp32 itself).  One lane = 4 destination floats (one 16-byte store), guarded scalar loads.
+__global__ __launch_bounds__(256) void pad_rows_f32_kernel(const float* src, int F, float* dst, int64_t ldd, int64_t n_rows) {
+    const int64_t G = ldd >> 2;
+    const int64_t total = n_rows * G;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t n = i / G;
+        const int c0 = (int)(i - n * G) * 4;
+        const float* s = src + n * F;
+        float4v o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = c0 + j < F ? s[c0 + j] : 0.0f;
+        *reinterpret_cast<float4v*>(dst + i * 4) = o;
+    }
+}
+
+int pad_rows_f32_launch(const float* src, int F, float* dst, int64_t ldd, int64_t n_rows, hipStream_t stream) {
+    MV_REQUIRE(src != nullptr && dst != nullptr, "pad_rows_f32: null tensor");
+    MV_REQUIRE(F > 0 && ldd >= F && ldd % 4 == 0 && n_rows > 0, "pad_rows_f32: bad shape (ldd must be a multiple of 4, at least F)");
+    const int64_t total = n_rows * (ldd / 4);
+    const int grid = ew_grid(total);
+    MV_LAUNCH(pad_rows_f32_kernel, (grid, 1, 1), (256, 1, 1), 0, stream, src, F, dst, ldd, n_rows);
+    return check_launch("pad_rows_f32_kernel");
+}
+
 int copy_slice_launch(const half_t* src, int64_t lds_, half_t* dst, int64_t ldd, int C, int64_t n_rows, hipStream_t stream) {
     MV_REQUIRE(C % 8 == 0 && lds_ % 8 == 0 && ldd % 8 == 0, "copy_slice: channels must be a multiple of 8");
     const int64_t total = n_rows * (C / 8);
