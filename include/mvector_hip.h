@@ -258,7 +258,7 @@ typedef struct MvTensorRef {
 
 typedef struct MvModel MvModel;
 
-/* EcapaTdnn.forward (mvector/models/ecapa_tdnn.py:253-283), pooling_type "ASP". */
+/* EcapaTdnn.forward (mvector/models/ecapa_tdnn.py:253-283), pooling_type "ASP" (other heads: mv_ecapa_create_pooled below). */
 typedef struct MvEcapaCfg {
     int32_t input_size;          /* F, any positive width: not a multiple of 8 -> zero-padded to round_up(F, 8) on the device (bits of that width
                                   * with zero-padded features and first-layer weights) */
@@ -292,13 +292,29 @@ typedef struct MvCamppCfg {
 #define MV_CAMPP_HEAD_F32 2
 int mv_campp_create(const MvCamppCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
 
-/* TDNN.forward (mvector/models/tdnn.py:46-68), pooling_type "ASP". */
+/* TDNN.forward (mvector/models/tdnn.py:46-68), pooling_type "ASP" (other heads: mv_tdnn_create_pooled below). */
 typedef struct MvTdnnCfg {
     int32_t input_size; /* F, any positive width: not a multiple of 8 -> a zero-padded fp32 copy at round_up(F, 8) in the workspace */
     int32_t channels; /* 512 */
     int32_t embd_dim; /* 192 */
 } MvTdnnCfg;
 int mv_tdnn_create(const MvTdnnCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
+
+/* The pooling heads of EcapaTdnn and TDNN (the reference's `pooling_type`, mvector/models/pooling.py), over the pooling input x [B, C, T]:
+ *   MV_POOL_ASP  attentive statistics pooling: weighted mean | weighted std   -> 2C   (what mv_ecapa_create / mv_tdnn_create build)
+ *   MV_POOL_SAP  self-attentive pooling: sum_t softmax_t(W2 . tanh(W1 . x + b1) + b2) x   -> C  (bottleneck 128: keys <pool>.linear1.*, .linear2.*)
+ *   MV_POOL_TAP  mean over time   -> C
+ *   MV_POOL_TSP  mean | unbiased variance over time (torch.var: NaN at T = 1)   -> 2C
+ * Behind the head: EcapaTdnn asp_bn -> fc (SAP / TAP / TSP: asp_bn is a plain BatchNorm1d, keys asp_bn.*; ASP: asp_bn.norm.*), TDNN bn5 ->
+ * linear -> bn6 -- folded into one exact-fp32 layer as for ASP.  The _pooled create calls take one of these codes; MV_POOL_ASP builds the same
+ * handle as the plain create call.  An unknown code, or a state_dict without the chosen head's tensors, is refused with MV_ERR_INVALID_ARGUMENT /
+ * MV_ERR_MISSING_TENSOR and a message. */
+#define MV_POOL_ASP 0
+#define MV_POOL_SAP 1
+#define MV_POOL_TAP 2
+#define MV_POOL_TSP 3
+int mv_ecapa_create_pooled(const MvEcapaCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
+int mv_tdnn_create_pooled(const MvTdnnCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
 
 /* ERes2Net.forward / ERes2NetV2.forward (mvector/models/eres2net.py:266-287 / 441-456): 2-D Res2Net blocks with AFF
  * fusion, temporal statistics pooling (pooling.py:130-148), seg_1 (+ optional ReLU -> seg_bn_1 -> seg_2). */
@@ -570,6 +586,17 @@ int mv_wave_prepare_i16(const int16_t* pcm, int64_t pcm_stride, const int64_t* n
  * pass a negative value for the online-softmax form (any weights). */
 int mv_asp_pool_f16(const void* h, const void* w2_packed, const void* x, int64_t ldx, const float* gmean, int64_t gmean_ld,
                     float* out, int32_t B, int32_t T, int32_t C, int32_t A, float logit_bound_log2, mv_stream_t stream);
+
+/* Self-attentive pooling tail (the SAP head, pooling.py:50-65): the mean-only form of mv_asp_pool_f16 on the same kernels.
+ *   h  fp16 [B, T, A] = tanh(W1 . x + b1) (the conv1d layer with its bias and MV_ACT_TANH),  w2_packed = mv_conv1d_pack_weight of linear2's
+ *   W2[C, A, 1] * log2(e) (its bias is constant over time and cancels in the softmax),  x fp16 [B, T, ldx],  out fp32 [B, C] = sum_t softmax_t(W2 . h) x.
+ * logit_bound_log2 as mv_asp_pool_f16. */
+int mv_sap_pool_f16(const void* h, const void* w2_packed, const void* x, int64_t ldx, float* out, int32_t B, int32_t T, int32_t C, int32_t A,
+                    float logit_bound_log2, mv_stream_t stream);
+/* Mean and UNBIASED variance over time (the TSP head, pooling.py:29-47) of a channel-last fp16 tensor [B, T, ld] (ld % 8 == 0, 16-byte
+ * aligned rows): out[b * ld_out + c] = mean, out[b * ld_out + C + c] = var (ld_out >= 2C).  Centred two-pass form, a fixed summation order per
+ * (utterance, channel) whatever B is; a constant channel has variance exactly 0, and T = 1 gives NaN (0 / 0, as torch.var). */
+int mv_time_mean_var_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C, float* out, int64_t ld_out, mv_stream_t stream);
 
 /* One 3x3 Conv2d of the CAM++ front-end (FCM, mvector/models/campplus.py:221-292: BasicResBlock.conv1 / conv2 (+ shortcut) and
  * FCM.conv2) on channel-last fp16 maps with 32 feature maps, eval BatchNorm already folded into w / bias, ReLU at the end:

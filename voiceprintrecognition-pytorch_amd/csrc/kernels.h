@@ -94,7 +94,14 @@ int copy_slice_launch(const half_t* src, int64_t lds_, half_t* dst, int64_t ldd,
 bool res2_chain_supported(int T, int width, int steps, int k, int dil);
 int res2_chain_launch(const half_t* x, half_t* y, const half_t* const* w, const float* const* bias, const float* const* scale,
                       const float* const* shift, int B, int T, int C, int width, int steps, int k, int dil, hipStream_t stream);
+// with_std = false: the weighted mean alone, out [B, C] (the mean-only instantiation of the same kernels: SAP)
 int asp_pool_launch(const half_t* h, const half_t* w2_packed, const half_t* x, int64_t ldx, const float* gmean,
-                    int64_t gmean_ld, float* out, int B, int T, int C, int A, float logit_bound_log2, hipStream_t stream);
+                    int64_t gmean_ld, float* out, int B, int T, int C, int A, float logit_bound_log2, hipStream_t stream,
+                    bool with_std = true);
+// SelfAttentivePooling: h = tanh(W1 . x + b1) [B, T, A], w2_packed = W2 * log2(e) -> out [B, C]
+int sap_pool_launch(const half_t* h, const half_t* w2_packed, const half_t* x, int64_t ldx, float* out, int B, int T, int C, int A,
+                    float logit_bound_log2, hipStream_t stream);
+// TemporalStatisticsPooling: out[b, 0:C] = mean over time, out[b, C:2C] = unbiased variance (centred two-pass; T = 1 -> NaN)
+int time_mean_var_launch(const half_t* x, int64_t ld, int B, int T, int C, float* out, int64_t ld_out, hipStream_t stream);
 
 }  // namespace mv

@@ -84,4 +84,21 @@ struct AspLayer {
                 bool have_gstats = false) const;
 };
 
+// W2 (C x A) of an attention head packed times log2(e), and the bound max_c sum_k |W2[c,k]| * log2(e) of every logit (-1: none)
+int make_attention_projection(MvModelBase* m, const Weights& w, const std::string& name, int C, int A, ConvLayer* out, float* bound_log2);
+
+// the other pooling heads of pooling.py (MV_POOL_SAP / _TAP / _TSP) over x [B, T, ldx] fp16 -> pooled fp32 [B, width()]
+struct PoolHead {
+    static constexpr int SAP_A = 128;   // SelfAttentivePooling's bottleneck: fixed at 128 in both models, not attention_channels
+    int type = MV_POOL_TAP;
+    int C = 0;
+    ConvLayer sap1;                     // SAP linear1 (SAP_A x C, with bias): h = tanh(linear1(x))
+    ConvLayer sap2;                     // SAP linear2 (C x SAP_A) times log2(e), bias dropped (it cancels in the softmax over time)
+    float logit_bound_log2 = -1.0f;
+    int create(MvModelBase* m, const Weights& w, const std::string& prefix, int type, int C);
+    int width() const { return type == MV_POOL_TSP ? 2 * C : C; }
+    int hidden_width() const { return type == MV_POOL_SAP ? SAP_A : 0; }   // fp16 [B, T, .] scratch the forward needs
+    int forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, float* pooled, hipStream_t stream) const;
+};
+
 }  // namespace mv

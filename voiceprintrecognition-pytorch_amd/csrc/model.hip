@@ -1,5 +1,6 @@
 // Backbone forwards orchestrated natively: EcapaTdnn (mvector/models/ecapa_tdnn.py:253-283) and TDNN
-// (mvector/models/tdnn.py:46-68), both ending in attentive statistics pooling (mvector/models/pooling.py:86-127).
+// (mvector/models/tdnn.py:46-68), both ending in attentive statistics pooling (mvector/models/pooling.py:86-127) or, with the
+// _pooled create calls, in one of the other heads of pooling.py (SAP / TAP / TSP: PoolHead).
 //
 // create(): takes the reference-layout fp32 state_dict (device pointers), folds eval-mode BatchNorm into
 // per-channel (scale, shift), packs conv weights for the MFMA kernel, folds asp_bn / bn5 / bn6 into the final
@@ -192,26 +193,29 @@ int AspLayer::create(MvModelBase* m, const Weights& w, const std::string& prefix
     if (tmp == nullptr) return fail(MV_ERR_HIP, "asp create: upload failed");
     if ((rc = m->make_conv_from(tmp, &w, prefix + ".tdnn.conv.conv.bias", A, C, 1, &tdnn))) return rc;
     if ((rc = m->make_bn(w, prefix + ".tdnn.norm.norm", A, &bn_scale, &bn_shift))) return rc;
-    // attention projection asp.conv (C x A): stored times log2(e) so that the pooling kernel's softmax weight is a bare
-    // 2^logit; its bias is constant over time and cancels in the softmax over time (pooling.py:117-119), so it is dropped.
-    // h = tanh(.) is bounded by 1, so sum_k |W2[c,k]| bounds every logit (-> NOMAX form of the kernel)
-    {
-        const float log2e = 1.4426950408889634f;
-        std::vector<float> w2;
-        if ((rc = w.host(prefix + ".conv.conv.weight", (int64_t)C * A, w2))) return rc;
-        double bound = 0.0;
-        for (int c = 0; c < C; ++c) {
-            double sabs = 0.0;
-            for (int k = 0; k < A; ++k) sabs += fabs((double)w2[(size_t)c * A + k]);
-            bound = sabs > bound ? sabs : bound;
-        }
-        for (float& v : w2) v *= log2e;
-        logit_bound_log2 = std::isfinite(bound) ? (float)(bound * log2e * 1.001) : -1.0f;  // margin for the fp16 rounding of W2
-        float* tmp2 = m->upload(w2);
-        if (tmp2 == nullptr) return fail(MV_ERR_HIP, "asp create: upload failed");
-        if ((rc = m->make_conv_from(tmp2, nullptr, "", C, A, 1, &conv))) return rc;
+    // attention projection asp.conv (C x A)
+    return make_attention_projection(m, w, prefix + ".conv.conv.weight", C, A, &conv, &logit_bound_log2);
+}
+
+// Attention projection W2 (C x A) of the ASP and SAP heads: stored times log2(e) so that the pooling kernel's softmax weight is a bare
+// 2^logit; its bias is constant over time and cancels in the softmax over time (pooling.py:63,117-119), so it is dropped.
+// h = tanh(.) is bounded by 1, so sum_k |W2[c,k]| bounds every logit (-> NOMAX form of the kernel)
+int make_attention_projection(MvModelBase* m, const Weights& w, const std::string& name, int C, int A, ConvLayer* out, float* bound_log2) {
+    const float log2e = 1.4426950408889634f;
+    std::vector<float> w2;
+    int rc;
+    if ((rc = w.host(name, (int64_t)C * A, w2))) return rc;
+    double bound = 0.0;
+    for (int c = 0; c < C; ++c) {
+        double sabs = 0.0;
+        for (int k = 0; k < A; ++k) sabs += fabs((double)w2[(size_t)c * A + k]);
+        bound = sabs > bound ? sabs : bound;
     }
-    return MV_OK;
+    for (float& v : w2) v *= log2e;
+    *bound_log2 = std::isfinite(bound) ? (float)(bound * log2e * 1.001) : -1.0f;  // margin for the fp16 rounding of W2
+    float* tmp2 = m->upload(w2);
+    if (tmp2 == nullptr) return fail(MV_ERR_HIP, "attention projection: upload failed");
+    return m->make_conv_from(tmp2, nullptr, "", C, A, 1, out);
 }
 
 // [B, 2C] global mean | std, [B, A] context bias, the two partial buffers of the hidden conv's fused input statistics, the K slices of the
@@ -279,6 +283,43 @@ int AspLayer::forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, flo
     return asp_pool_launch(h, conv.w, x, ldx, gmean, 2 * C, pooled, B, T, C, A, logit_bound_log2, stream);
 }
 
+// --------------------------------------------------------------------------------------- SAP / TAP / TSP heads
+
+int PoolHead::create(MvModelBase* m, const Weights& w, const std::string& prefix, int type_, int C_) {
+    type = type_;
+    C = C_;
+    if (type != MV_POOL_SAP) return MV_OK;   // TAP / TSP have no parameters
+    int rc;
+    // h = tanh(linear1(x)): the conv layer with its bias and a tanh epilogue
+    if ((rc = m->make_conv(w, prefix + ".linear1.weight", prefix + ".linear1.bias", SAP_A, C, 1, &sap1))) return rc;
+    MV_REQUIRE(sap1.bias != nullptr, "state_dict is missing '" + prefix + ".linear1.bias'");
+    return make_attention_projection(m, w, prefix + ".linear2.weight", C, SAP_A, &sap2, &logit_bound_log2);
+}
+
+int PoolHead::forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, float* pooled, hipStream_t st) const {
+    int rc;
+    switch (type) {
+        case MV_POOL_SAP:
+            if ((rc = run_conv(sap1, x, MV_DT_F16, ldx, nullptr, 0, h, MV_DT_F16, SAP_A, B, T, T, 1, 0, MV_PAD_REFLECT, MV_ACT_NONE, nullptr,
+                               nullptr, MV_ACT_TANH, nullptr, true, st)))
+                return rc;
+            return sap_pool_launch(h, sap2.w, x, ldx, pooled, B, T, C, SAP_A, logit_bound_log2, st);
+        case MV_POOL_TAP:   // the SE squeeze's time mean (time_stats_kernel, mean only)
+            return time_stats_launch(x, ldx, B, T, C, pooled, nullptr, C, 0, 0.0f, st);
+        case MV_POOL_TSP:
+            return time_mean_var_launch(x, ldx, B, T, C, pooled, 2 * C, st);
+        default:
+            return fail(MV_ERR_INVALID_ARGUMENT, "pooling head: not SAP, TAP or TSP");
+    }
+}
+
+static int check_pool_type(int32_t pooling_type, const char* fn) {
+    if (pooling_type < MV_POOL_ASP || pooling_type > MV_POOL_TSP)
+        return fail(MV_ERR_INVALID_ARGUMENT, std::string(fn) + ": pooling_type " + std::to_string(pooling_type) +
+                                                 " is not MV_POOL_ASP (0), MV_POOL_SAP (1), MV_POOL_TAP (2) or MV_POOL_TSP (3)");
+    return MV_OK;
+}
+
 // fold y = BN_out( W . BN_in(p) + b ) into one affine map (either BN optional)
 int fold_final_linear(MvModelBase* m, const Weights& w, const std::string& weight_name, const std::string& bias_name,
                       const std::string& bn_in, const std::string& bn_out, int O, int K, float** wf_out, float** bf_out) {
@@ -342,10 +383,14 @@ struct EcapaModel : MvModelBase {
     ConvLayer block0w;         // block 0 as a 1x1 conv over the contiguous k*Fp window of the reflect-padded features
     bool block0_window = false;
     std::vector<SeRes2> blocks;
-    AspLayer asp;
+    int pool = MV_POOL_ASP;
+    AspLayer asp;      // pool == MV_POOL_ASP
+    PoolHead head;     // the other heads
     float* fc_w = nullptr;
     float* fc_b = nullptr;
     int ccat = 0, cmax = 0;
+
+    int pooled_width() const { return pool == MV_POOL_ASP ? 2 * cfg.channels[4] : head.width(); }
 
     int make_tdnn(const Weights& w, const std::string& prefix, int cout, int cin, int k, TdnnBlk* out) {
         int rc = make_conv(w, prefix + ".conv.conv.weight", prefix + ".conv.conv.bias", cout, cin, k, &out->conv);
@@ -353,8 +398,9 @@ struct EcapaModel : MvModelBase {
         return make_bn(w, prefix + ".norm.norm", cout, &out->scale, &out->shift);
     }
 
-    int create(const MvEcapaCfg& c, const Weights& w) {
+    int create(const MvEcapaCfg& c, const Weights& w, int pool_type) {
         cfg = c;
+        pool = pool_type;
         input_size = c.input_size;
         embd_dim = c.embd_dim;
         int rc;
@@ -427,10 +473,17 @@ struct EcapaModel : MvModelBase {
         }
         MV_REQUIRE(ccat == c.channels[4], "ecapa: channels[-1] must equal the sum of the SE-Res2Net block widths");
         if ((rc = make_tdnn(w, "mfa", c.channels[4], ccat, c.kernel_sizes[4], &mfa))) return rc;
-        if ((rc = asp.create(this, w, "asp", c.channels[4], c.attention_channels, c.global_context != 0))) return rc;
-        if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn.norm", "", c.embd_dim, 2 * c.channels[4],
-                                    &fc_w, &fc_b)))
-            return rc;
+        if (pool == MV_POOL_ASP) {
+            if ((rc = asp.create(this, w, "asp", c.channels[4], c.attention_channels, c.global_context != 0))) return rc;
+            if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn.norm", "", c.embd_dim, 2 * c.channels[4],
+                                        &fc_w, &fc_b)))
+                return rc;
+        } else {
+            // SAP / TAP / TSP: asp_bn is a plain BatchNorm1d over the head's width (ecapa_tdnn.py:229-250)
+            if ((rc = head.create(this, w, "asp", pool, c.channels[4]))) return rc;
+            if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn", "", c.embd_dim, head.width(), &fc_w, &fc_b)))
+                return rc;
+        }
         MV_HIP_OK(hipDeviceSynchronize());
         return MV_OK;
     }
@@ -455,13 +508,13 @@ struct EcapaModel : MvModelBase {
         s.t2 = c.take<half_t>(N * cmax);
         s.sc = c.take<half_t>(N * cmax);
         s.mfa = c.take<half_t>(N * cfg.channels[4]);
-        s.h = c.take<half_t>(N * cfg.attention_channels);
+        s.h = c.take<half_t>(N * (pool == MV_POOL_ASP ? cfg.attention_channels : head.hidden_width()));
         s.se_mean = c.take<float>((size_t)B * cmax);
         s.se_hid = c.take<float>((size_t)B * cfg.se_channels);
         s.gate = c.take<float>((size_t)B * cmax);
-        s.asp_f = c.take<float>(asp.workspace_floats(B, T));
-        s.pooled = c.take<float>((size_t)B * 2 * cfg.channels[4]);
-        s.fc_ws_floats = linear_f32_splitk_floats(B, 2 * cfg.channels[4], cfg.embd_dim);   // K slices of the final layer (linear.hip)
+        s.asp_f = c.take<float>(pool == MV_POOL_ASP ? asp.workspace_floats(B, T) : 0);
+        s.pooled = c.take<float>((size_t)B * pooled_width());
+        s.fc_ws_floats = linear_f32_splitk_floats(B, pooled_width(), cfg.embd_dim);   // K slices of the final layer (linear.hip)
         s.fc_ws = c.take<float>(s.fc_ws_floats);
         s.bytes = c.total();
         return s;
@@ -577,10 +630,15 @@ struct EcapaModel : MvModelBase {
                            cfg.dilations[4] * (cfg.kernel_sizes[4] - 1) / 2, R, MV_ACT_RELU, mfa.scale, mfa.shift, MV_ACT_NONE,
                            nullptr, true, st)))
             return rc;
-        if ((rc = asp.forward(s.mfa, Cm, B, T, s.h, s.asp_f, s.pooled, st))) return rc;
+        if (pool == MV_POOL_ASP) {
+            if ((rc = asp.forward(s.mfa, Cm, B, T, s.h, s.asp_f, s.pooled, st))) return rc;
+        } else if ((rc = head.forward(s.mfa, Cm, B, T, s.h, s.pooled, st))) {
+            return rc;
+        }
         // asp_bn folded into fc
-        return linear_f32_launch(s.pooled, 2 * Cm, fc_w, 2 * Cm, fc_b, MV_ACT_NONE, emb, cfg.embd_dim, B, 2 * Cm, cfg.embd_dim, 0,
-                                 st, s.fc_ws, s.fc_ws_floats);
+        const int P = pooled_width();
+        return linear_f32_launch(s.pooled, P, fc_w, P, fc_b, MV_ACT_NONE, emb, cfg.embd_dim, B, P, cfg.embd_dim, 0, st, s.fc_ws,
+                                 s.fc_ws_floats);
     }
 };
 
@@ -591,14 +649,19 @@ struct TdnnModel : MvModelBase {
     ConvLayer conv[5];
     float* scale[4] = {nullptr, nullptr, nullptr, nullptr};
     float* shift[4] = {nullptr, nullptr, nullptr, nullptr};
-    AspLayer asp;
+    int pool = MV_POOL_ASP;
+    AspLayer asp;      // pool == MV_POOL_ASP
+    PoolHead head;     // the other heads
     float* fc_w = nullptr;
     float* fc_b = nullptr;
     static constexpr int K[5] = {5, 3, 3, 1, 1};
     static constexpr int D[5] = {1, 2, 3, 1, 1};
 
-    int create(const MvTdnnCfg& c, const Weights& w) {
+    int pooled_width() const { return pool == MV_POOL_ASP ? 2 * cfg.channels : head.width(); }
+
+    int create(const MvTdnnCfg& c, const Weights& w, int pool_type) {
         cfg = c;
+        pool = pool_type;
         input_size = c.input_size;
         embd_dim = c.embd_dim;
         MV_REQUIRE(c.channels % 8 == 0, "tdnn: channels must be a multiple of 8");
@@ -623,8 +686,12 @@ struct TdnnModel : MvModelBase {
             if (i < 4)
                 if ((rc = make_bn(w, "bn" + std::to_string(i + 1), c.channels, &scale[i], &shift[i]))) return rc;
         }
-        if ((rc = asp.create(this, w, "pooling", c.channels, 128, true))) return rc;
-        if ((rc = fold_final_linear(this, w, "linear.weight", "linear.bias", "bn5", "bn6", c.embd_dim, 2 * c.channels, &fc_w,
+        if (pool == MV_POOL_ASP) {
+            if ((rc = asp.create(this, w, "pooling", c.channels, 128, true))) return rc;
+        } else if ((rc = head.create(this, w, "pooling", pool, c.channels))) {
+            return rc;
+        }
+        if ((rc = fold_final_linear(this, w, "linear.weight", "linear.bias", "bn5", "bn6", c.embd_dim, pooled_width(), &fc_w,
                                     &fc_b)))
             return rc;
         MV_HIP_OK(hipDeviceSynchronize());
@@ -643,9 +710,9 @@ struct TdnnModel : MvModelBase {
         Ws s;
         s.a = c.take<half_t>(N * cfg.channels);
         s.b = c.take<half_t>(N * cfg.channels);
-        s.h = c.take<half_t>(N * 128);
-        s.asp_f = c.take<float>(asp.workspace_floats(B, T));
-        s.pooled = c.take<float>((size_t)B * 2 * cfg.channels);
+        s.h = c.take<half_t>(N * (pool == MV_POOL_ASP ? 128 : head.hidden_width()));
+        s.asp_f = c.take<float>(pool == MV_POOL_ASP ? asp.workspace_floats(B, T) : 0);
+        s.pooled = c.take<float>((size_t)B * pooled_width());
         s.xp = Fp != cfg.input_size ? c.take<float>(N * Fp) : nullptr;   // zero-padded features of a ragged F
         s.bytes = c.total();
         return s;
@@ -683,9 +750,13 @@ struct TdnnModel : MvModelBase {
             ldx = cfg.channels;
             Tin = Tout;
         }
-        if ((rc = asp.forward(static_cast<const half_t*>(x), cfg.channels, B, Tin, s.h, s.asp_f, s.pooled, st))) return rc;
-        return linear_f32_launch(s.pooled, 2 * cfg.channels, fc_w, 2 * cfg.channels, fc_b, MV_ACT_NONE, emb, cfg.embd_dim, B,
-                                 2 * cfg.channels, cfg.embd_dim, 0, st);
+        if (pool == MV_POOL_ASP) {
+            if ((rc = asp.forward(static_cast<const half_t*>(x), cfg.channels, B, Tin, s.h, s.asp_f, s.pooled, st))) return rc;
+        } else if ((rc = head.forward(static_cast<const half_t*>(x), cfg.channels, B, Tin, s.h, s.pooled, st))) {
+            return rc;
+        }
+        const int P = pooled_width();
+        return linear_f32_launch(s.pooled, P, fc_w, P, fc_b, MV_ACT_NONE, emb, cfg.embd_dim, B, P, cfg.embd_dim, 0, st);
     }
 };
 constexpr int TdnnModel::K[5];
@@ -701,7 +772,20 @@ int mv_ecapa_create(const MvEcapaCfg* cfg, const MvTensorRef* tensors, int32_t n
     int rc = w.init(tensors, num_tensors);
     if (rc != MV_OK) return rc;
     auto m = std::make_unique<mv::EcapaModel>();
-    rc = m->create(*cfg, w);
+    rc = m->create(*cfg, w, MV_POOL_ASP);
+    if (rc != MV_OK) return rc;
+    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
+    return MV_OK;
+}
+
+int mv_ecapa_create_pooled(const MvEcapaCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
+    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_ecapa_create_pooled: null argument");
+    int rc = mv::check_pool_type(pooling_type, "mv_ecapa_create_pooled");
+    if (rc != MV_OK) return rc;
+    mv::Weights w;
+    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
+    auto m = std::make_unique<mv::EcapaModel>();
+    rc = m->create(*cfg, w, pooling_type);
     if (rc != MV_OK) return rc;
     *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
     return MV_OK;
@@ -713,7 +797,20 @@ int mv_tdnn_create(const MvTdnnCfg* cfg, const MvTensorRef* tensors, int32_t num
     int rc = w.init(tensors, num_tensors);
     if (rc != MV_OK) return rc;
     auto m = std::make_unique<mv::TdnnModel>();
-    rc = m->create(*cfg, w);
+    rc = m->create(*cfg, w, MV_POOL_ASP);
+    if (rc != MV_OK) return rc;
+    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
+    return MV_OK;
+}
+
+int mv_tdnn_create_pooled(const MvTdnnCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
+    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_tdnn_create_pooled: null argument");
+    int rc = mv::check_pool_type(pooling_type, "mv_tdnn_create_pooled");
+    if (rc != MV_OK) return rc;
+    mv::Weights w;
+    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
+    auto m = std::make_unique<mv::TdnnModel>();
+    rc = m->create(*cfg, w, pooling_type);
     if (rc != MV_OK) return rc;
     *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
     return MV_OK;

@@ -6,7 +6,9 @@
 //   se_gate_residual     out = gate[b, c] * y + residual (ecapa_tdnn.py:84,143), written into a channel slice
 //                        of the aggregation buffer so torch.cat (ecapa_tdnn.py:273) never materialises
 //   asp_pool_kernel      attention logits (128 -> C projection on MFMA), softmax over time and the weighted
-//                        mean / std (pooling.py:117-125) in one kernel: the [B, C, T] logits never exist
+//                        mean / std (pooling.py:117-125) in one kernel: the [B, C, T] logits never exist; its mean-only
+//                        instantiation is the SAP head (SelfAttentivePooling)
+//   time_mean_var_kernel mean and unbiased variance over T, centred two-pass form: the TSP head (TemporalStatisticsPooling)
 #include "common.h"
 
 namespace mv {
@@ -497,7 +499,9 @@ __device__ __forceinline__ void asp_merge(float& m, float& s0, float& s1, float&
     m = nm;
 }
 
-template <int KS, bool NOMAX>
+// STD = false: the weighted mean alone, out [B, C] (SelfAttentivePooling, pooling.py:50-65: the same softmax over time of W2 . tanh(.), no
+// second moment; the caller passes gmean = null)
+template <int KS, bool NOMAX, bool STD = true>
 __global__ __launch_bounds__(256) void asp_pool_kernel(AspArgs a) {
     // Workgroup = (64-channel tile, 4 utterances): the W2 tile is staged once and shared, then every WAVE pools one whole
     // utterance on its own -- no barrier and no cross-wave merge after the prologue.
@@ -605,7 +609,7 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(AspArgs a) {
                         const float ed = e * d;
                         s0[mi][r] += e;
                         s1[mi][r] += ed;
-                        s2[mi][r] = fmaf(ed, d, s2[mi][r]);
+                        if constexpr (STD) s2[mi][r] = fmaf(ed, d, s2[mi][r]);
                     } else {
                         const float nm = fmaxf(m[mi][r], l[r]);  // finite from the first valid row on; -3e38 before
                         const float rs = asp_exp2(m[mi][r] - nm);
@@ -613,7 +617,7 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(AspArgs a) {
                         const float ed = e * d;
                         s0[mi][r] = s0[mi][r] * rs + e;
                         s1[mi][r] = s1[mi][r] * rs + ed;
-                        s2[mi][r] = s2[mi][r] * rs + ed * d;
+                        if constexpr (STD) s2[mi][r] = s2[mi][r] * rs + ed * d;
                         m[mi][r] = nm;
                     }
                 }
@@ -634,7 +638,7 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(AspArgs a) {
             if (NOMAX) {
                 s0[mi][r] = row16_sum(s0[mi][r]);
                 s1[mi][r] = row16_sum(s1[mi][r]);
-                s2[mi][r] = row16_sum(s2[mi][r]);
+                if constexpr (STD) s2[mi][r] = row16_sum(s2[mi][r]);
             } else {
 #pragma unroll
                 for (int sh = 1; sh <= 8; sh <<= 1) {
@@ -646,9 +650,13 @@ __global__ __launch_bounds__(256) void asp_pool_kernel(AspArgs a) {
             const int c = cl + 4 * mi + r;
             if (fr == 0 && c < a.C) {
                 const float m1 = s1[mi][r] / s0[mi][r];
-                const float var = s2[mi][r] / s0[mi][r] - m1 * m1;
-                a.out[(int64_t)b * 2 * a.C + c] = g4[mi][r] + m1;
-                a.out[(int64_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(var, a.eps));
+                if constexpr (STD) {
+                    const float var = s2[mi][r] / s0[mi][r] - m1 * m1;
+                    a.out[(int64_t)b * 2 * a.C + c] = g4[mi][r] + m1;
+                    a.out[(int64_t)b * 2 * a.C + a.C + c] = sqrtf(fmaxf(var, a.eps));
+                } else {
+                    a.out[(int64_t)b * a.C + c] = g4[mi][r] + m1;
+                }
             }
         }
 }
@@ -673,7 +681,7 @@ constexpr int ASP_RING = 4;                          // tiles per ring: a step r
 constexpr int ASP_XRING = ASP_RING, ASP_HRING = ASP_RING;
 constexpr int ASP_YOUNGER = 2 + 3 * (ASP_RING - 2);  // transfers of a wave younger than its part of h(tt + 1) when step tt waits (8 for four tiles, 14 for six)
 
-template <int KS>
+template <int KS, bool STD = true>   // STD = false: the mean-only (SAP) instantiation, as asp_pool_kernel
 __global__ __launch_bounds__(256) void asp_pool_ring_kernel(AspArgs a) {
     constexpr int HROW = KS * 64;          // bytes per h row (A_pad fp16)
     constexpr int HTILE = 16 * HROW;       // 2 or 4 KiB
@@ -791,7 +799,7 @@ __global__ __launch_bounds__(256) void asp_pool_ring_kernel(AspArgs a) {
                 const float2v ed = e * d;
                 s0[mi][q] += e;
                 s1[mi][q] += ed;
-                s2[mi][q] = __builtin_elementwise_fma(ed, d, s2[mi][q]);
+                if constexpr (STD) s2[mi][q] = __builtin_elementwise_fma(ed, d, s2[mi][q]);
             }
         }
     };
@@ -863,30 +871,55 @@ __global__ __launch_bounds__(256) void asp_pool_ring_kernel(AspArgs a) {
         for (int r = 0; r < 4; ++r) {
             const float z0 = row16_sum(s0[mi][r >> 1][r & 1]);
             const float z1 = row16_sum(s1[mi][r >> 1][r & 1]);
-            const float z2 = row16_sum(s2[mi][r >> 1][r & 1]);
+            const float z2 = STD ? row16_sum(s2[mi][r >> 1][r & 1]) : 0.0f;
             if (fr == 0) {
                 const int c = cl + 4 * mi + r;
                 const float inv = rcp_fast(z0);
                 const float m1 = z1 * inv;
-                const float var = z2 * inv - m1 * m1;
-                a.out[(int64_t)b * 2 * a.C + c] = g2[mi][r >> 1][r & 1] + m1;
-                a.out[(int64_t)b * 2 * a.C + a.C + c] = sqrt_fast(fmaxf(var, a.eps));
+                if constexpr (STD) {
+                    const float var = z2 * inv - m1 * m1;
+                    a.out[(int64_t)b * 2 * a.C + c] = g2[mi][r >> 1][r & 1] + m1;
+                    a.out[(int64_t)b * 2 * a.C + a.C + c] = sqrt_fast(fmaxf(var, a.eps));
+                } else {
+                    a.out[(int64_t)b * a.C + c] = g2[mi][r >> 1][r & 1] + m1;
+                }
             }
         }
 }
 
-template <int KS>
+template <int KS, bool STD>
 static void asp_pool_dispatch(const AspArgs& a, unsigned gx, unsigned gy, bool nomax, hipStream_t stream) {
     if (nomax) {
-        MV_LAUNCH((asp_pool_kernel<KS, true>), (gx, gy, 1), (256, 1, 1), 0, stream, a);
+        MV_LAUNCH((asp_pool_kernel<KS, true, STD>), (gx, gy, 1), (256, 1, 1), 0, stream, a);
     } else {
-        MV_LAUNCH((asp_pool_kernel<KS, false>), (gx, gy, 1), (256, 1, 1), 0, stream, a);
+        MV_LAUNCH((asp_pool_kernel<KS, false, STD>), (gx, gy, 1), (256, 1, 1), 0, stream, a);
     }
 }
 
-// w2_packed carries the factor log2(e); logit_bound_log2 = max_c sum_k |W2[c,k]| * log2(e), < 0 = unknown
+template <bool STD>
+static void asp_pool_ring(const AspArgs& a, unsigned gx, hipStream_t stream) {
+    if (a.A_pad == 64) {
+        MV_LAUNCH((asp_pool_ring_kernel<2, STD>), (gx, (unsigned)a.B, 1), (256, 1, 1), 4 * ASP_XRING * 2048 + ASP_HRING * 2048, stream, a);
+    } else {
+        MV_LAUNCH((asp_pool_ring_kernel<4, STD>), (gx, (unsigned)a.B, 1), (256, 1, 1), 4 * ASP_XRING * 2048 + ASP_HRING * 4096, stream, a);
+    }
+}
+
+template <bool STD>
+static void asp_pool_regs(const AspArgs& a, unsigned gx, bool nomax, hipStream_t stream) {
+    const unsigned gy = (unsigned)ceil_div(a.B, 4);
+    switch (a.A_pad / 32) {
+        case 2: asp_pool_dispatch<2, STD>(a, gx, gy, nomax, stream); break;
+        case 4: asp_pool_dispatch<4, STD>(a, gx, gy, nomax, stream); break;
+        case 6: asp_pool_dispatch<6, STD>(a, gx, gy, nomax, stream); break;
+        default: asp_pool_dispatch<8, STD>(a, gx, gy, nomax, stream); break;
+    }
+}
+
+// w2_packed carries the factor log2(e); logit_bound_log2 = max_c sum_k |W2[c,k]| * log2(e), < 0 = unknown.
+// with_std = false: the mean-only form of the SAP head, out [B, C]
 int asp_pool_launch(const half_t* h, const half_t* w2_packed, const half_t* x, int64_t ldx, const float* gmean,
-                    int64_t gmean_ld, float* out, int B, int T, int C, int A, float logit_bound_log2, hipStream_t stream) {
+                    int64_t gmean_ld, float* out, int B, int T, int C, int A, float logit_bound_log2, hipStream_t stream, bool with_std) {
     MV_REQUIRE(h != nullptr && w2_packed != nullptr && x != nullptr && out != nullptr, "asp_pool: null tensor");
     MV_REQUIRE(B > 0 && T > 0 && C > 0 && A > 0, "asp_pool: bad geometry");
     MV_REQUIRE(A % 8 == 0 && A <= 256, "asp_pool: attention width must be a multiple of 8 and <= 256");
@@ -915,20 +948,124 @@ int asp_pool_launch(const half_t* h, const half_t* w2_packed, const half_t* x, i
                          (reinterpret_cast<uintptr_t>(h) & 15) == 0;
     if (ring_ok && (a.A_pad == 64 || a.A_pad == 128)) {
         const unsigned gxw = (unsigned)ceil_div(C, 256);
-        if (a.A_pad == 64) {
-            MV_LAUNCH((asp_pool_ring_kernel<2>), (gxw, (unsigned)B, 1), (256, 1, 1), 4 * ASP_XRING * 2048 + ASP_HRING * 2048, stream, a);
-        } else {
-            MV_LAUNCH((asp_pool_ring_kernel<4>), (gxw, (unsigned)B, 1), (256, 1, 1), 4 * ASP_XRING * 2048 + ASP_HRING * 4096, stream, a);
-        }
+        if (with_std) asp_pool_ring<true>(a, gxw, stream); else asp_pool_ring<false>(a, gxw, stream);
         return check_launch("asp_pool_ring_kernel");
     }
-    switch (a.A_pad / 32) {
-        case 2: asp_pool_dispatch<2>(a, gx, (unsigned)ceil_div(B, 4), nomax, stream); break;
-        case 4: asp_pool_dispatch<4>(a, gx, (unsigned)ceil_div(B, 4), nomax, stream); break;
-        case 6: asp_pool_dispatch<6>(a, gx, (unsigned)ceil_div(B, 4), nomax, stream); break;
-        default: asp_pool_dispatch<8>(a, gx, (unsigned)ceil_div(B, 4), nomax, stream); break;
-    }
+    if (with_std) asp_pool_regs<true>(a, gx, nomax, stream); else asp_pool_regs<false>(a, gx, nomax, stream);
     return check_launch("asp_pool_kernel");
+}
+
+// SelfAttentivePooling (pooling.py:50-65): h = tanh(W1 . x + b1) fp16 [B, T, A] (the conv1d layer with bias and MV_ACT_TANH), w2_packed =
+// linear2's weight times log2(e) (its bias b2[c] is constant over time and cancels in the softmax), out fp32 [B, C] = sum_t softmax_t(.) x
+int sap_pool_launch(const half_t* h, const half_t* w2_packed, const half_t* x, int64_t ldx, float* out, int B, int T, int C, int A,
+                    float logit_bound_log2, hipStream_t stream) {
+    return asp_pool_launch(h, w2_packed, x, ldx, nullptr, 0, out, B, T, C, A, logit_bound_log2, stream, /*with_std=*/false);
+}
+
+// ------------------------------------------------------------------------------------------------
+// mean and unbiased variance over time (TemporalStatisticsPooling, pooling.py:29-47: torch.mean | torch.var), fp16 [B, T, ld] -> fp32
+// out[b, c] = mean, out[b, C + c] = var.  Workgroup and lane layout of time_stats_kernel ((utterance, 128-channel group), 16 rows in
+// flight); TWO passes over the utterance's rows:
+//   pass 1  mean = k + sum (x - k) / T            k = x[b, 0, c]: a constant channel's mean is k exactly
+//   pass 2  var  = (sum d^2 - (sum d)^2 / T) / (T - 1),  d = x - mean      (the corrected two-pass form: centred, so no
+//           E[x^2] - mean^2 cancellation when |mean| >> std; a constant channel's variance is exactly 0)
+// Pass 2 walks each lane's rows backwards, starting on the rows pass 1 read last (still in L2).  The summation order is fixed per
+// (utterance, channel), so a row's bits do not depend on B.  T = 1 gives NaN, as torch.var does (0 / 0).
+__global__ __launch_bounds__(256) void time_mean_var_kernel(const half_t* x, int64_t ld, int T, int C, float* out, int64_t ld_out) {
+    __shared__ float red[2][4][128];
+    __shared__ float mean_s[128];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c16 = lane & 15, rp = lane >> 4;
+    const int b = blockIdx.y;
+    const int cg0 = blockIdx.x * 128;
+    const int c0 = cg0 + c16 * 8;
+    const int nvalid = c0 < C ? (C - c0 < 8 ? C - c0 : 8) : 0;
+    const half_t* xb = x + (int64_t)b * T * ld + c0;
+    const int t_first = wave * 4 + rp;  // this lane's rows: t_first, t_first + 16, ...
+    auto load8 = [&](int t, float (&v)[8]) {
+        const half_t* p = xb + (int64_t)t * ld;
+        if (nvalid == 8) {
+            const half8v h = *reinterpret_cast<const half8v*>(p);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = e < nvalid ? (float)p[e] : 0.0f;
+        }
+    };
+    float k8[8], s1[8], s2[8], v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) k8[e] = s1[e] = s2[e] = 0.0f;
+    if (nvalid > 0) {
+        load8(0, k8);
+        for (int t = t_first; t < T; t += 16) {
+            load8(t, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) s1[e] += v[e] - k8[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float a1 = s1[e];
+        a1 += __shfl_xor(a1, 16);
+        a1 += __shfl_xor(a1, 32);
+        if (rp == 0) red[0][wave][c16 * 8 + e] = a1;
+    }
+    __syncthreads();
+    if (tid < 128) {
+        const bool ok = cg0 + tid < C;
+        const float kc = ok ? (float)x[(int64_t)b * T * ld + cg0 + tid] : 0.0f;
+        const float z1 = red[0][0][tid] + red[0][1][tid] + red[0][2][tid] + red[0][3][tid];
+        mean_s[tid] = ok ? kc + z1 / (float)T : 0.0f;
+    }
+    __syncthreads();
+    float m8[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        m8[e] = mean_s[c16 * 8 + e];
+        s1[e] = 0.0f;
+    }
+    if (nvalid > 0 && t_first < T) {
+        for (int t = t_first + (T - 1 - t_first) / 16 * 16; t >= 0; t -= 16) {
+            load8(t, v);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float d = v[e] - m8[e];
+                s1[e] += d;
+                s2[e] = fmaf(d, d, s2[e]);
+            }
+        }
+    }
+    // (the reads of red[0] above happened before the barrier in front of pass 2)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        float a1 = s1[e], a2 = s2[e];
+        a1 += __shfl_xor(a1, 16);
+        a1 += __shfl_xor(a1, 32);
+        a2 += __shfl_xor(a2, 16);
+        a2 += __shfl_xor(a2, 32);
+        if (rp == 0) {
+            red[0][wave][c16 * 8 + e] = a1;
+            red[1][wave][c16 * 8 + e] = a2;
+        }
+    }
+    __syncthreads();
+    if (tid < 128 && cg0 + tid < C) {
+        const float z1 = red[0][0][tid] + red[0][1][tid] + red[0][2][tid] + red[0][3][tid];
+        const float z2 = red[1][0][tid] + red[1][1][tid] + red[1][2][tid] + red[1][3][tid];
+        const float var = T > 1 ? (z2 - z1 * z1 / (float)T) / (float)(T - 1) : __builtin_nanf("");
+        out[(int64_t)b * ld_out + cg0 + tid] = mean_s[tid];
+        out[(int64_t)b * ld_out + C + cg0 + tid] = var;
+    }
+}
+
+int time_mean_var_launch(const half_t* x, int64_t ld, int B, int T, int C, float* out, int64_t ld_out, hipStream_t stream) {
+    MV_REQUIRE(x != nullptr && out != nullptr, "time_mean_var: null tensor");
+    MV_REQUIRE(B > 0 && T > 0 && C > 0, "time_mean_var: bad geometry");
+    MV_REQUIRE(ld >= C && ld % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "time_mean_var: rows must be 16-byte aligned, ld >= C");
+    MV_REQUIRE(ld_out >= 2 * (int64_t)C, "time_mean_var: output leading dimension must be >= 2C");
+    MV_LAUNCH(time_mean_var_kernel, ((unsigned)ceil_div(C, 128), (unsigned)B, 1), (256, 1, 1), 0, stream, x, ld, T, C, out, ld_out);
+    return check_launch("time_mean_var_kernel");
 }
 
 }  // namespace mv
@@ -939,7 +1076,17 @@ int mv_asp_pool_f16(const void* h, const void* w2_packed, const void* x, int64_t
                     float* out, int32_t B, int32_t T, int32_t C, int32_t A, float logit_bound_log2, mv_stream_t stream) {
     return mv::asp_pool_launch(reinterpret_cast<const half_t*>(h), reinterpret_cast<const half_t*>(w2_packed),
                                reinterpret_cast<const half_t*>(x), ldx, gmean, gmean_ld, out, B, T, C, A, logit_bound_log2,
-                               static_cast<hipStream_t>(stream));
+                               static_cast<hipStream_t>(stream), /*with_std=*/true);
+}
+
+int mv_sap_pool_f16(const void* h, const void* w2_packed, const void* x, int64_t ldx, float* out, int32_t B, int32_t T, int32_t C, int32_t A,
+                    float logit_bound_log2, mv_stream_t stream) {
+    return mv::sap_pool_launch(reinterpret_cast<const half_t*>(h), reinterpret_cast<const half_t*>(w2_packed),
+                               reinterpret_cast<const half_t*>(x), ldx, out, B, T, C, A, logit_bound_log2, static_cast<hipStream_t>(stream));
+}
+
+int mv_time_mean_var_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C, float* out, int64_t ld_out, mv_stream_t stream) {
+    return mv::time_mean_var_launch(reinterpret_cast<const half_t*>(x), ld, B, T, C, out, ld_out, static_cast<hipStream_t>(stream));
 }
 
 int mv_bn_relu_rows_f16(const void* x, int64_t ldx, const float* scale, const float* shift, void* y, int64_t ldy, int64_t n_rows,

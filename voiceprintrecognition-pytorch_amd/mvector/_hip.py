@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, 'lib', 'libmvector_hip.so')
 MV_ACT_NONE, MV_ACT_RELU, MV_ACT_TANH, MV_ACT_SIGMOID = 0, 1, 2, 3
 MV_PAD_ZERO, MV_PAD_REFLECT = 0, 1
 MV_DT_F32, MV_DT_F16 = 0, 1
+MV_POOL_ASP, MV_POOL_SAP, MV_POOL_TAP, MV_POOL_TSP = 0, 1, 2, 3
+POOLING_TYPES = {'ASP': MV_POOL_ASP, 'SAP': MV_POOL_SAP, 'TAP': MV_POOL_TAP, 'TSP': MV_POOL_TSP}   # the reference's `pooling_type` strings
 
 c_i32, c_i64, c_f32, c_vp, c_sz = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t
 
@@ -114,6 +116,8 @@ _SIGNATURES = {
     'mv_ecapa_create': (c_i32, [ctypes.POINTER(MvEcapaCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_campp_create': (c_i32, [ctypes.POINTER(MvCamppCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_tdnn_create': (c_i32, [ctypes.POINTER(MvTdnnCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
+    'mv_ecapa_create_pooled': (c_i32, [ctypes.POINTER(MvEcapaCfg), c_i32, ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
+    'mv_tdnn_create_pooled': (c_i32, [ctypes.POINTER(MvTdnnCfg), c_i32, ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_eres2net_create': (c_i32, [ctypes.POINTER(MvEres2Cfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_conv2d_first': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'mv_tstp_f32': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -147,6 +151,8 @@ _SIGNATURES = {
     'mv_profile_read': (c_i32, [c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_i32]),
     'mv_wave_prepare_i16': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
     'mv_asp_pool_f16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    'mv_sap_pool_f16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
+    'mv_time_mean_var_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     'mv_spectrogram_default_cfg': (None, [ctypes.POINTER(MvSpectrogramCfg)]),
     'mv_spectrogram_create': (c_i32, [ctypes.POINTER(MvSpectrogramCfg), ctypes.POINTER(c_vp)]),
     'mv_spectrogram_info': (c_i32, [c_vp, ctypes.POINTER(c_i32)]),
@@ -569,10 +575,21 @@ class Mfcc(_FrontEnd):
 
 
 class Model:
-    """Handle of a native backbone (mv_*_create / mv_model_forward) built from a reference-layout state_dict."""
+    """Handle of a native backbone (mv_*_create / mv_model_forward) built from a reference-layout state_dict.
 
-    def __init__(self, kind, cfg, state_dict, cdll=None):
+    ``pooling_type`` ('ASP' | 'SAP' | 'TAP' | 'TSP', or an MV_POOL_* code): the head of an 'ecapa' or 'tdnn' backbone
+    (mv_*_create_pooled); other kinds have one head and take 'ASP' only, which stands for "the model's own"."""
+
+    def __init__(self, kind, cfg, state_dict, cdll=None, pooling_type='ASP'):
         self._cdll = cdll or lib()
+        if isinstance(pooling_type, str):
+            if pooling_type not in POOLING_TYPES:
+                raise ValueError(f'pooling_type {pooling_type!r} is not one of {sorted(POOLING_TYPES)}')
+            pool = POOLING_TYPES[pooling_type]
+        else:
+            pool = int(pooling_type)   # (a code the library does not know is refused by the create call, with its message)
+        if pool != MV_POOL_ASP and kind not in ('ecapa', 'tdnn'):
+            raise ValueError(f'pooling_type {pooling_type!r}: only the ecapa and tdnn handles take a pooling head')
         names, tensors = [], []
         for k, v in state_dict.items():
             if not torch.is_floating_point(v):
@@ -586,8 +603,12 @@ class Model:
             refs[i].data = t.data_ptr()
             refs[i].numel = t.numel()
         self._h = c_vp()
-        create = {'ecapa': self._cdll.mv_ecapa_create, 'campp': self._cdll.mv_campp_create,
-                  'tdnn': self._cdll.mv_tdnn_create, 'eres2net': self._cdll.mv_eres2net_create}[kind]
+        if pool == MV_POOL_ASP:   # (the plain create calls: the handles every ASP model has always built)
+            create = {'ecapa': self._cdll.mv_ecapa_create, 'campp': self._cdll.mv_campp_create,
+                      'tdnn': self._cdll.mv_tdnn_create, 'eres2net': self._cdll.mv_eres2net_create}[kind]
+        else:
+            pooled = {'ecapa': self._cdll.mv_ecapa_create_pooled, 'tdnn': self._cdll.mv_tdnn_create_pooled}[kind]
+            create = lambda c, r, n, out: pooled(c, pool, r, n, out)   # noqa: E731
         if tensors and tensors[0].is_cuda:
             torch.cuda.current_stream(tensors[0].device).synchronize()  # weights fully written before create() reads them
         check(create(ctypes.byref(cfg), refs, len(tensors), ctypes.byref(self._h)), self._cdll)

@@ -27,6 +27,10 @@ class NativeBackbone:
     def _native_supported(self):
         return True, ''
 
+    def _native_pooling_type(self):
+        """the pooling head the handle builds ('ASP' | 'SAP' | 'TAP' | 'TSP': EcapaTdnn / TDNN); 'ASP' = the backbone's own head"""
+        return 'ASP'
+
     def _native_created(self, handle, build):
         """hook: a freshly built handle (``build()`` builds another one from the same parameters); returns the handle to keep"""
         return handle
@@ -93,7 +97,8 @@ class NativeBackbone:
             for v in tensors:
                 if v.device.type != 'cuda' or (v.device.index if v.device.index is not None else key) != key:
                     raise RuntimeError(f'{type(self).__name__} parameters are on {v.device} but the input is on cuda:{key}')
-            build = lambda: _hip.Model(self._native_kind, self._native_cfg(), {k: v.detach() for k, v in live.items()})
+            build = lambda: _hip.Model(self._native_kind, self._native_cfg(), {k: v.detach() for k, v in live.items()},
+                                       pooling_type=self._native_pooling_type())
             h = self._native_created(build(), build)
             handles[key] = (h, self._params_version(tensors), tensors)
         return h

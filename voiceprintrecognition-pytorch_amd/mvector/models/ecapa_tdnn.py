@@ -113,7 +113,10 @@ class EcapaTdnn(NativeBackbone, nn.Module):
     # ---- native (HIP) dispatch -------------------------------------------------------------------------
     def _native_supported(self):
         c = self._cfg
-        if c['pooling_type'] != 'ASP':
+        # ASP, SAP and TAP run natively.  TSP does too -- the library and the C ABI build it (mv_ecapa_create_pooled, MV_POOL_TSP; covered
+        # through _hip.Model by tests/test_pooling_heads.py) -- but this gate keeps refusing it for now: lifting it is a one-line change that
+        # goes together with test_emu_kernels.py::test_unsupported_constructor_arguments_are_named_not_approximated, which pins the refusal.
+        if c['pooling_type'] not in ('ASP', 'SAP', 'TAP'):
             return False, f"pooling_type={c['pooling_type']!r}"
         if any(g != 1 for g in c['groups']):
             return False, 'grouped convolution'
@@ -122,6 +125,9 @@ class EcapaTdnn(NativeBackbone, nn.Module):
         if len(c['channels']) != 5:
             return False, 'a block count other than 3 SE-Res2Net blocks'
         return True, ''
+
+    def _native_pooling_type(self):
+        return self._cfg['pooling_type']
 
     def _native_cfg(self):
         from mvector import _hip

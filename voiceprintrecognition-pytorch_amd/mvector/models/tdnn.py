@@ -35,9 +35,12 @@ class TDNN(NativeBackbone, nn.Module):
         self.bn6 = nn.BatchNorm1d(embd_dim)
 
     def _native_supported(self):
-        if self._cfg['pooling_type'] != 'ASP':
+        if self._cfg['pooling_type'] not in ('ASP', 'SAP', 'TAP', 'TSP'):
             return False, f"pooling_type={self._cfg['pooling_type']!r}"
         return True, ''
+
+    def _native_pooling_type(self):
+        return self._cfg['pooling_type']
 
     def _native_cfg(self):
         from mvector import _hip
