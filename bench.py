@@ -1,6 +1,6 @@
 """Benchmark of the embedding-extraction hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one process per GPU.  Under ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`` (the driver's command; RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_* from the environment) every rank runs main() directly.  Started plainly (``python bench.py --gpus N``, no WORLD_SIZE in the
@@ -13,14 +13,16 @@ One "step" = one pass of the hot path over one batch of synthetic waveforms alre
     -> (N>1: RCCL all-gather of the embedding shards) -> HIP cosine block of this rank's rows vs all rows.
 The batch dimension shards across ranks with no other exchange (weak scaling: B utterances per GPU).
 
-Output: ONE JSON line on rank 0 (metric = utterances/sec embedded, BASELINE.json) with
+Output: ONE JSON line on rank 0 (metric = utterances/sec embedded, BASELINE.json).  A plain run does only what the headline needs: set-up, the
+warm-up steps, the timed steps, --dump-outputs, the line.  Its line carries
   * per-stage times from events recorded on the launch stream inside the timed region,
   * ``roofline``: the dominant kernel class (the implicit-GEMM conv launches) against the dense MFMA peak of its operand
     type -- algorithmic FLOPs per launch over the launch durations measured with HIP events the library records on the
     launch stream around every conv launch of every 4th timed step (mv_profile_enable);
     ``roofline_fbank``: the front-end kernel against the HBM roofline the same way (algorithmic bytes 287 360 B/utt for
     Fbank-80, SURVEY.md 8(d)); ``roofline_backbone``: the whole backbone stage (all kernels) against the MFMA peak;
-    ``traffic`` = HBM bytes per launch from the committed PMC pass (profiles/pmc_traffic.json), null without one,
+    ``traffic`` = HBM bytes per launch from the committed PMC pass (profiles/pmc_traffic.json), null without one.
+``--full`` adds what takes runs of its own (--no-cpu-baseline, --no-other-configs and --no-box leave parts of it out again):
   * ``cpu_baseline`` (N=1): the oracle (torch CPU fp32 port of the reference path) timed on the whole batch on this host's
     cores with autograd off ("best case"), and ``cpu_baseline_as_shipped``: a smaller sample with the autograd graph
     recorded, as the reference's predictor runs (mvector/predict.py:228,262 never enter no_grad),
@@ -34,7 +36,8 @@ Output: ONE JSON line on rank 0 (metric = utterances/sec embedded, BASELINE.json
   * ``box``: the yard-stick of the box this run landed on, taken before the timed region (tools/boxprobe): streaming-copy GB/s over 1 GiB, bare
     fp16 MFMA TFLOP/s at the ring GEMM's residency and the shader clock sustained under it -- what makes lines of different boxes comparable,
   * ``latency_batch1`` (N=1, default model only): p50 / p90 of a ``predict()``-shaped call -- one 3 s utterance resident on the
-    device -> features -> embedding -> host -- for EcapaTdnn-1024 and CAM++, eager launches and hipGraph replay.
+    device -> features -> embedding -> host -- for EcapaTdnn-1024 and CAM++, eager launches and hipGraph replay,
+  * ``two_streams`` (N=1, default model only): the batch as two halves on two HIP streams.
 """
 import argparse
 import json
@@ -615,11 +618,13 @@ def main():
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--batch', type=int, default=256, help='utterances per GPU')
     ap.add_argument('--model', default='ecapa1024', choices=sorted(MODELS))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='skip the CAM++ / MelSpectrogram / bucketed ERes2NetV2 legs')
-    ap.add_argument('--cpu-sample', type=int, default=256, help='utterances timed on the CPU oracle (~10-20 s of CPU work)')
-    ap.add_argument('--cpu-threads', type=int, default=32, help='cap on the torch CPU threads of the oracle baseline')
-    ap.add_argument('--no-box', action='store_true', help='skip the box yard-stick (PMC passes: its launches would enter the per-kernel averages)')
+    ap.add_argument('--full', action='store_true', help='beyond the headline (N=1 unless said): the box yard-stick, parity against the oracle, the CPU '
+                    'baselines, the upload-inclusive steps, the other configs, batch-1 latency and two streams -- off by default')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines (parity over 4 rows)')
+    ap.add_argument('--no-other-configs', action='store_true', help='--full without the CAM++ / MelSpectrogram / bucketed ERes2NetV2, latency and two-stream legs')
+    ap.add_argument('--cpu-sample', type=int, default=256, help='utterances timed on the CPU oracle under --full (~10-20 s of CPU work)')
+    ap.add_argument('--cpu-threads', type=int, default=32, help='cap on the torch CPU threads of the oracle baseline (--full)')
+    ap.add_argument('--no-box', action='store_true', help='--full without the box yard-stick (PMC passes: its launches would enter the per-kernel averages)')
     ap.add_argument('--dry-launch', action='store_true', help='N ranks rendezvous (gloo), rank 0 prints what it saw, nothing runs on a device')
     ap.add_argument('--dump-outputs', metavar='DIR', help="rank 0 writes the last timed step's outputs as DIR/<name>.npy (fp32): embeddings [B, D] "
                     'and the cosine score block [B, N*B] -- inputs and weights are seeded, so two builds compare output for output')
@@ -654,7 +659,7 @@ def main():
         parallel.sync_native_choices(model, device=dev, group=group)
 
     box = None
-    if rank == 0 and not args.no_box:
+    if rank == 0 and args.full and not args.no_box:
         try:
             box = box_probe(dev)
         except Exception as ex:   # the yard-stick must never take the headline with it
@@ -811,7 +816,7 @@ def main():
                 ex = gflop_per_utt - 2 * 2 * 3072 * 128 * T / 1e9
                 out['roofline_backbone'].update({'executed_gflop_per_utt': round(ex, 3), 'achieved_executed': round(B * ex / (bb_ms * 1e-3) / 1e3, 1),
                                                  'frac_executed': round(B * ex / (bb_ms * 1e-3) / 1e3 / mfma_peak, 4)})
-        if world == 1:
+        if world == 1 and args.full:
             # ---- parity gate + CPU baseline (oracle = test infrastructure; outside the timed region) ----
             host_cores = os.cpu_count()
             threads = min(host_cores, args.cpu_threads)

@@ -1106,7 +1106,7 @@ def test_gpu_bench_under_a_launcher_runs_its_collectives_on_the_rccl_group():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT', 'MASTER_ADDR')}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY='0', OMP_NUM_THREADS='16')   # (the launcher's default of one OpenMP thread would slow the 4-row oracle check)
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port', str(port),
-                        os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-other-configs'],
+                        os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-other-configs'],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
@@ -1143,3 +1143,22 @@ def test_gpu_bench_dump_outputs_are_the_timed_steps_embeddings_and_scores(tmp_pa
     with torch.no_grad():
         ref, _ = bench.oracle_embeddings('ecapa1024', state_cpu, wav[:4])
     assert cos_dist(torch.from_numpy(emb[:4]), ref).max() < 1e-4
+
+
+def test_gpu_bench_plain_run_is_the_headline_alone():
+    """bench.py without --full: set-up, warm-up, timed steps and the line -- the headline fields and the figures taken inside the timed steps, none of
+    what takes runs of its own (box yard-stick, oracle parity, CPU baselines, upload-inclusive steps, side legs)."""
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT', 'MASTER_ADDR')}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1'],
+                       env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['metric'] == 'utterances/sec embedded (3 s@16 kHz, Fbank-80, EcapaTdnn, bs=256)' and d['unit'] == 'utterances/s'
+    assert d['higher_is_better'] is True and d['dtype'] == 'f16' and d['steps'] == 4 and d['warmup'] == 1
+    assert d['value'] > 10000 and abs(d['value'] * d['ms_per_step'] / 1e3 - 256) < 0.5
+    assert d['roofline']['launches'] > 0 and d['box'] is None
+    for key in ('parity', 'cpu_baseline', 'cpu_baseline_as_shipped', 'cpu_baseline_all_cores', 'h2d_inclusive', 'other_configs', 'latency_batch1',
+                'two_streams'):
+        assert key not in d, key

@@ -5,7 +5,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -q -p no:cacheprovi
 for rep in 1 2; do
 for m in 0 1 2; do
   for model in ecapa1024 ecapa512 campp; do
-  MV_CONV_STORE_NT=$m timeout 600 python bench.py --model $model --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_${model}_m${m}_$rep.log 2>&1
+  MV_CONV_STORE_NT=$m timeout 600 python bench.py --model $model --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_${model}_m${m}_$rep.log 2>&1
   python - <<PY
 import json
 l=[x for x in open("$OUT/bench_${model}_m${m}_$rep.log") if x.startswith("{")][-1]; j=json.loads(l)

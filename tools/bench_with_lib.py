@@ -1,5 +1,5 @@
 """bench.py on a variant build of the library (tools/build_variant.py) -- A/B arms inside one gpurun call:
-    python tools/bench_with_lib.py tools/probe/<name>.so --model eres2netv2_w96s4 --batch 64 --steps 3 --warmup 1 --no-cpu-baseline --no-other-configs
+    python tools/bench_with_lib.py tools/probe/<name>.so --model eres2netv2_w96s4 --batch 64 --steps 3 --warmup 1 --full --no-cpu-baseline --no-other-configs
 The product library stays what `import mvector` loads everywhere else; only this process binds the variant."""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
