@@ -314,6 +314,35 @@ int mv_tdnn_create(const MvTdnnCfg* cfg, const MvTensorRef* tensors, int32_t num
 #define MV_POOL_TAP 2
 #define MV_POOL_TSP 3
 int mv_ecapa_create_pooled(const MvEcapaCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
+
+/* EcapaTdnn with any number of SE-Res2Net blocks and grouped TDNN convolutions (the reference constructor's `channels` / `kernel_sizes` /
+ * `dilations` of any length >= 3 and its `groups`, ecapa_tdnn.py:146-216).  N = nblocks SE-Res2Net blocks, arrays of N + 2 entries:
+ *   entry 0       blocks.0 (input_size -> channels[0], kernel_sizes[0] taps, groups[0])
+ *   entry i       SE-Res2Net block i = 1..N (channels[i-1] -> channels[i]; its tdnn1 and tdnn2 are 1x1 with groups[i]; the Res2Net, SE and shortcut
+ *                 convolutions are not grouped)
+ *   entry N + 1   the MFA (sum of the N block widths -> channels[N + 1], which must equal that sum; groups[N + 1])
+ * Indexing is by position, as the reference's: with N = 4 and its default 5-entry `groups`, pass groups[4] for both block 4 and the MFA.
+ * Every grouped layer's in and out widths must be divisible by its group count (torch's rule).  A grouped 1x1 layer whose groups are
+ * mv_conv1d_grouped_native runs as a grouped GEMM; the other grouped layers (blocks.0, an MFA with kernel_sizes[N + 1] > 1, narrow groups) are
+ * expanded at create into their block-diagonal dense weight (exact zeros).  mv_model_info reports how many of each (MV_INFO_ECAPA_*).
+ * Refused with a message: nblocks outside 1..MV_ECAPA_MAX_BLOCKS, channels[N + 1] != sum of the block widths, a width not divisible by its
+ * groups, a non-positive group count.  MvEcapaCfg / mv_ecapa_create / mv_ecapa_create_pooled are unchanged: an extended config with nblocks = 3
+ * and every group count 1 builds the same handle as they do. */
+#define MV_ECAPA_MAX_BLOCKS 16
+typedef struct MvEcapaCfgEx {
+    int32_t input_size;          /* F, as in MvEcapaCfg */
+    int32_t embd_dim;
+    int32_t nblocks;             /* N, 1 .. MV_ECAPA_MAX_BLOCKS */
+    int32_t channels[MV_ECAPA_MAX_BLOCKS + 2];       /* first N + 2 entries used */
+    int32_t kernel_sizes[MV_ECAPA_MAX_BLOCKS + 2];
+    int32_t dilations[MV_ECAPA_MAX_BLOCKS + 2];
+    int32_t groups[MV_ECAPA_MAX_BLOCKS + 2];         /* >= 1 */
+    int32_t attention_channels;
+    int32_t res2net_scale;
+    int32_t se_channels;
+    int32_t global_context;
+} MvEcapaCfgEx;
+int mv_ecapa_create_ex(const MvEcapaCfgEx* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
 int mv_tdnn_create_pooled(const MvTdnnCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
 
 /* ERes2Net.forward / ERes2NetV2.forward (mvector/models/eres2net.py:266-287 / 441-456): 2-D Res2Net blocks with AFF
@@ -362,6 +391,15 @@ int mv_model_embd_dim(const MvModel* m, int32_t* embd_dim);
 #define MV_INFO_CAMPP_PROBE_PEAK 7
 #define MV_INFO_CAMPP_HEAD_PEAK 8
 #define MV_INFO_CAMPP_HEAD_SATURATED 9
+/* EcapaTdnn handles (mv_ecapa_create*): how their grouped convolutions run (0 on an ungrouped model)
+ *   MV_INFO_ECAPA_GROUPED_NATIVE     grouped layers on the grouped GEMM (mv_conv1d_grouped_native)
+ *   MV_INFO_ECAPA_GROUPED_EXPANDED   grouped layers expanded into a block-diagonal dense weight
+ *   MV_INFO_ECAPA_EXPANDED_1X1       of those, the 1x1 ones
+ *   MV_INFO_ECAPA_BLOCKS             N, the number of SE-Res2Net blocks */
+#define MV_INFO_ECAPA_GROUPED_NATIVE 20
+#define MV_INFO_ECAPA_GROUPED_EXPANDED 21
+#define MV_INFO_ECAPA_EXPANDED_1X1 22
+#define MV_INFO_ECAPA_BLOCKS 23
 int mv_model_info(const MvModel* m, int32_t key, float* value);
 int mv_model_workspace_bytes(const MvModel* m, int32_t B, int32_t T, size_t* bytes);
 /* feats: [B, T, F] fp32 (the AudioFeaturizer output layout); emb: [B, embd_dim] fp32. */
@@ -514,6 +552,20 @@ typedef struct MvConv1dDesc {
                                    * SUSTAINED (bench.py's `box` block prices the 2.5 PFLOP/s peak's 2.4 GHz against it).  Other kernels ignore it. */
 } MvConv1dDesc;
 int mv_conv1d_forward(const MvConv1dDesc* d, mv_stream_t stream);
+/* Grouped 1-D convolution (nn.Conv1d(groups = g), the `groups` of TDNNBlock, mvector/models/utils.py:120-138).  The weight is the grouped nn.Conv1d
+ * layout fp32 [cout][cin / g][k]; d->cin / d->cout are the layer's whole widths.  Two forms, chosen by the geometry alone:
+ *   native    (mv_conv1d_grouped_native = 1: k = 1, cin / g a multiple of 64, cout / g a multiple of 128): the weights are packed PER GROUP
+ *             (fp16 [cout_pad][cin / g], the dense packing of the grouped weight), and every tile of output channels -- all inside one group --
+ *             reads only its group's K slice of x, columns (co / (cout / g)) * (cin / g) .. + cin / g: a grouped GEMM that multiplies no zero block.
+ *             Groups of 256 and more output channels run on the dense layers' persistent ring kernel where those do (conv1d_ring_grouped_kernel),
+ *             narrower ones on the one-shot 128-channel tiles.  fp16 x only: no x2, in_scale / in_shift or fused statistics.
+ *   expanded  (everything else: narrower groups, k > 1): the pack call writes the block-diagonal dense [cout][k][cin] weight and the forward is
+ *             the dense one -- the zero weights add exact zeros, so the result is the grouped convolution's, at the dense layer's cost.
+ * mv_conv1d_grouped_packed_elems: fp16 elements of the packed weight (-1 when cin or cout is not divisible by g).  groups = 1 is the dense layer. */
+int32_t mv_conv1d_grouped_native(int32_t cout, int32_t cin, int32_t k, int32_t groups);
+int64_t mv_conv1d_grouped_packed_elems(int32_t cout, int32_t cin, int32_t k, int32_t groups);
+int mv_conv1d_pack_weight_grouped(const float* w, int32_t cout, int32_t cin, int32_t k, int32_t groups, void* packed_f16, mv_stream_t stream);
+int mv_conv1d_forward_grouped(const MvConv1dDesc* d, int32_t groups, mv_stream_t stream);
 /* floats in one partial-statistics buffer, and the reduction of the partial rows to per-utterance mean[b, c] (and
  * std[b, c] = sqrt(max(E[(y - mean)^2], clamp_eps)) when stat_sq / std are given).  `shift` = the BatchNorm shift passed to the
  * conv (the moments are taken about it), NULL if the conv had none. */

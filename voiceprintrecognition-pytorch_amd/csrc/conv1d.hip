@@ -70,6 +70,11 @@ struct ConvArgs {
     // 256 x 256 tile (tail_n_tiles x tail_co_tiles geometry) with virtual id tail_vb0 + b % tail_nv.  tail_nv == 0: the kernel's own tile walk.
     int ring_vb_end = 0;
     int tail_vb0 = 0, tail_nv = 0, tail_n_tiles = 0, tail_co_tiles = 0, tail_split = 2;   // tail_split: sub-tiles per side of a 256 x 256 tile (2: 128 x 128, 4: 64 x 64)
+    // Grouped 1x1 layer (nn.Conv1d groups = g, conv1d_launch's native grouped form): cin / cin_pad are the K of ONE group (grp_cin), the weights are
+    // packed per group ([cout][cin / g], the grouped nn.Conv1d layout), and a tile of output channels co0 .. reads the K slice of x that belongs to its
+    // group, columns (co0 / grp_cout) * grp_cin .. + grp_cin.  grp_cout is a multiple of every channel tile that runs it (128, or 256 on the ring
+    // kernel), so no tile straddles two groups.  grp_cout == 0: a dense layer.
+    int grp_cout = 0, grp_cin = 0;
 };
 
 __device__ __forceinline__ float apply_act(float v, int act) {
@@ -630,6 +635,7 @@ __global__ __launch_bounds__(64 * WC * WN) void conv1d_glds_kernel(ConvArgs a) {
         wsrc[i] = co < a.cout_pad ? a.w + (int64_t)co * a.k * a.cin_pad + kc * 8 : nullptr;
     }
     const half_t* xbase = reinterpret_cast<const half_t*>(a.x);
+    if (a.grp_cout > 0) xbase += (int64_t)(co0 / a.grp_cout) * a.grp_cin;   // grouped 1x1 layer: this channel tile's group's K slice (uniform)
     const half_t* zero = reinterpret_cast<const half_t*>(g_zero_page);
     const int kstages_per_tap = a.cin_pad / CV_BK;
     const int nstages = a.k * kstages_per_tap;
@@ -1343,7 +1349,10 @@ constexpr int CVR_LDS_BYTES = 5 * CVR_SLOT_BYTES;  // 163 840 B
 // 1x1 convolutions over a dense row range (k = 1, stride 1, no padding, T_in == T_out, cin % 64 == 0: every TDNNBlock of the backbone
 // but the first): input row = output row, so a transfer's address is  tensor + row offset (per lane, 32 bits, fixed for the tile) +
 // 128 bytes per stage (scalar) -- the loader has no vector arithmetic inside a tile at all.
-__global__ __launch_bounds__(512) void conv1d_ring_persistent_kernel(ConvArgs a) {
+// GROUPED (conv1d_ring_grouped_kernel): a grouped 1x1 layer (ConvArgs.grp_cout, a multiple of 256) -- the activation stream of a tile starts at its
+// group's K slice; nothing else differs, and the dense instantiation is the kernel it was.
+template <bool GROUPED>
+__device__ __forceinline__ void ring_persistent_body(const ConvArgs& a) {
     constexpr int MI = 8, NI = 4, TC = 256, TN = 256, NTW = 4, NTX = 4;
     MV_DYN_SMEM(smem);
     fp16_saturation_on();   // the epilogue converts with half_hwsat
@@ -1399,11 +1408,12 @@ __global__ __launch_bounds__(512) void conv1d_ring_persistent_kernel(ConvArgs a)
         x_vb = first_tile(vb, n_tile, co_tile);
         x_more = x_vb < total;
         x_stage = 0;
+        const unsigned goff = GROUPED ? (unsigned)(co_tile * TC / a.grp_cout) * (unsigned)a.grp_cin * 2u : 0u;   // the group's K slice
 #pragma unroll
         for (int i = 0; i < NTX; ++i) {
             int n = n_tile * TN + (wave * NTX + i) * 8 + lrow;
             n = n < a.n_rows ? n : a.n_rows - 1;
-            xoff[i] = (unsigned)n * xrow_bytes + (unsigned)kc * 16u;
+            xoff[i] = (unsigned)n * xrow_bytes + (unsigned)kc * 16u + goff;
         }
     };
     auto dma_x = [&](int i) {
@@ -1542,6 +1552,9 @@ __global__ __launch_bounds__(512) void conv1d_ring_persistent_kernel(ConvArgs a)
         p[3] = ref_clock_100mhz();
     }
 }
+
+__global__ __launch_bounds__(512) void conv1d_ring_persistent_kernel(ConvArgs a) { ring_persistent_body<false>(a); }
+__global__ __launch_bounds__(512) void conv1d_ring_grouped_kernel(ConvArgs a) { ring_persistent_body<true>(a); }
 
 // Wave priorities (r10k): s_setprio 1 around every group of eight MFMAs, and the opposite (priority outside the groups), as probe builds of
 // this file against the default in one call: 76.5 / 77.0 k (default), 76.5 / 76.7 k, 76.6 / 76.7 k utt/s -- no effect; the two waves of a SIMD
@@ -1696,6 +1709,28 @@ __global__ void pack_conv_weight_kernel(const float* w, int cout, int cin, int k
     }
 }
 
+// grouped fp32 [Cout][Cin / g][k] (nn.Conv1d(groups = g)) -> the DENSE packed layout of the block-diagonal [Cout][Cin][k] weight: the expanded
+// form of the grouped layers the native grouped GEMM does not take (conv1d_grouped_native); the zero weights add exact zeros
+__global__ void pack_conv_weight_grouped_kernel(const float* w, int cout, int cin, int k, int groups, int cout_pad, int cin_pad, half_t* out) {
+    const int64_t total = (int64_t)cout_pad * k * cin_pad;
+    const int cin_g = cin / groups, cout_g = cout / groups;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int ci = (int)(i % cin_pad);
+        const int j = (int)((i / cin_pad) % k);
+        const int co = (int)(i / ((int64_t)cin_pad * k));
+        float v = 0.0f;
+        if (co < cout && ci < cin && ci / cin_g == co / cout_g) v = w[((int64_t)co * cin_g + ci % cin_g) * k + j];
+        out[i] = to_half_sat(v);
+    }
+}
+
+// The grouped layers conv1d_launch runs as a grouped GEMM (ConvArgs.grp_cout): 1x1, every group's K a whole number of 64-wide K stages and its
+// output channels a whole number of 128-channel tiles.  The rest runs on the block-diagonal expansion.
+bool conv1d_grouped_native(int cout, int cin, int k, int groups) {
+    return groups > 1 && k == 1 && cin > 0 && cout > 0 && cin % groups == 0 && cout % groups == 0 && (cin / groups) % CV_BK == 0 &&
+           (cout / groups) % 128 == 0;
+}
+
 int conv1d_cin_pad(int cin) { return (int)round_up(cin, CV_BK); }
 int conv1d_cout_pad(int cout) { return (int)round_up(cout, 32); }
 
@@ -1714,7 +1749,25 @@ static int persistent_blocks(const MvConv1dDesc& d) {
     return (int)round_up(v, 8);
 }
 
-int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
+int conv1d_launch(const MvConv1dDesc& d_in, hipStream_t stream, int groups) {
+    MV_REQUIRE(groups >= 1, "conv1d: groups must be positive");
+    // A native grouped layer (conv1d_grouped_native) runs the dense machinery on ONE group's K (d.cin = cin / g) with per-group weights; the tiles
+    // find their group's K slice of x through ConvArgs.grp_cout / grp_cin.  Only the kernels that take that offset may run it: the ring kernel
+    // (grp_cout % 256 == 0), its tail and the one-shot glds kernels -- the direct fp16 path without fused statistics.
+    MvConv1dDesc d = d_in;
+    int grp_cout = 0, grp_cin = 0;
+    if (groups > 1) {
+        MV_REQUIRE(conv1d_grouped_native(d_in.cout, d_in.cin, d_in.k, groups),
+                   "conv1d: this grouped layer has no native form (1x1, cin / groups a multiple of 64, cout / groups a multiple of 128); "
+                   "run its block-diagonal expansion (mv_conv1d_pack_weight_grouped) through the dense form");
+        MV_REQUIRE(d_in.x_dtype == MV_DT_F16 && d_in.x2 == nullptr && d_in.in_scale == nullptr && d_in.stat_sum == nullptr &&
+                       d_in.stat_sq == nullptr && d_in.in_stat_sum == nullptr && d_in.in_stat_sq == nullptr,
+                   "conv1d: a grouped layer takes fp16 x without a second input, input affine or fused statistics");
+        MV_REQUIRE(d_in.ldx >= d_in.cin, "conv1d: a grouped layer needs ldx >= cin (every group's slice of x)");
+        grp_cout = d_in.cout / groups;
+        grp_cin = d_in.cin / groups;
+        d.cin = grp_cin;
+    }
     MV_REQUIRE(d.x != nullptr && d.w_packed != nullptr && d.y != nullptr, "conv1d: null tensor");
     MV_REQUIRE(d.B > 0 && d.T_in > 0 && d.T_out > 0 && d.cin > 0 && d.cout > 0 && d.k > 0, "conv1d: bad geometry");
     MV_REQUIRE(d.dilation >= 1 && d.stride >= 1 && d.pad >= 0, "conv1d: bad dilation/stride/pad");
@@ -1794,6 +1847,8 @@ int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
     a.in_sum = d.in_stat_sum;
     a.in_sq = d.in_stat_sq;
     a.clock_probe = reinterpret_cast<unsigned long long*>(d.clock_probe);
+    a.grp_cout = grp_cout;
+    a.grp_cin = grp_cin;
     MV_REQUIRE((reinterpret_cast<uintptr_t>(d.clock_probe) & 7) == 0, "conv1d: clock_probe must be 8-byte aligned");
     const bool in_stats = d.in_stat_sum != nullptr;
     MV_REQUIRE((d.in_stat_sum == nullptr) == (d.in_stat_sq == nullptr), "conv1d: in_stat_sum / in_stat_sq go together");
@@ -1803,7 +1858,7 @@ int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
     const bool has_x2 = d.x2 != nullptr, in_aff = d.in_scale != nullptr;
     // 256 x 256 tiles for wide layers with enough work to fill the chip (one workgroup per CU)
     MV_REQUIRE(d.tile == 0 || d.tile == 64 || d.tile == 128 || d.tile == 160 || d.tile == 256, "conv1d: tile must be 0 (auto), 64, 128, 160 or 256");
-    const bool big_ok = f16 && !has_x2 && !in_aff && d.cout % 256 == 0;
+    const bool big_ok = f16 && !has_x2 && !in_aff && d.cout % 256 == 0 && grp_cout % 256 == 0;
     if (d.tile == 256) MV_REQUIRE(big_ok, "conv1d: 256-wide tiles need the plain fp16 path and cout % 256 == 0");
     // (auto: from 5/8 of a round of 256 x 256 tiles on -- 48 utterances of 3 s through a 1024-channel layer are 224 tiles = 39.5 us in one round, against 57-74 us
     //  on 128-row tiles and 60 us on 64 x 64 ones: profiles/r12j_conv_tiles_by_batch.log)
@@ -1814,7 +1869,11 @@ int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
                          d.ldy % 8 == 0 && (reinterpret_cast<uintptr_t>(d.y) & 15) == 0 &&
                          (d.pre_act == MV_ACT_NONE || d.pre_act == MV_ACT_RELU) &&
                          (d.post_act == MV_ACT_NONE || d.post_act == MV_ACT_RELU) &&
-                         (int64_t)d.k * conv1d_cin_pad(d.cin) >= 2 * CV_BK;  // at least two K stages per tile
+                         (int64_t)d.k * conv1d_cin_pad(d.cin) >= 2 * CV_BK &&  // at least two K stages per tile
+                         // grouped: the ring kernel's layers only -- a grouped layer outside them (a post-activation, say) runs on the one-shot
+                         // glds kernels, which take the group offset as well; conv1d_glds_persistent_kernel does not
+                         (grp_cout == 0 || (d.stride == 1 && d.pad == 0 && d.T_in == d.T_out && d.post_act == MV_ACT_NONE &&
+                                            (int64_t)a.n_rows * d.ldx * 2 < ((int64_t)1 << 32)));
     // 128 x 160 tile of the direct path: two workgroups per CU = 2 * CUs slots; taken when it saves a whole round of
     // workgroups (B*T = 76 288 rows x 128 channels: 477 tiles in one round instead of 596 tiles in two)
     const bool direct = f16 && !has_x2 && !in_aff;
@@ -1857,7 +1916,7 @@ int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
         MvConv1dDesc d2 = d;
         d2.in_stat_sum = nullptr;
         d2.in_stat_sq = nullptr;
-        return conv1d_launch(d2, stream);
+        return conv1d_launch(d2, stream, 1);
     }
     if (in_stats) {
         MV_REQUIRE(direct && wide && d.k == 1 && d.stride == 1 && d.pad == 0 && d.T_in == d.T_out && d.cout <= CV_TC && d.tile != 128 &&
@@ -1884,6 +1943,7 @@ int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
             MV_SET_MAX_SMEM((conv1d_glds_persistent_kernel<true, 2>), CVP_LDS_BYTES) != hipSuccess ||
             MV_SET_MAX_SMEM((conv1d_glds_persistent_kernel<false, 0>), CVP_LDS_BYTES) != hipSuccess ||
             MV_SET_MAX_SMEM(conv1d_ring_persistent_kernel, CVR_LDS_BYTES) != hipSuccess ||
+            MV_SET_MAX_SMEM(conv1d_ring_grouped_kernel, CVR_LDS_BYTES) != hipSuccess ||
             MV_SET_MAX_SMEM((conv1d_mfma_kernel<float, false, false>), CV_LDS_BYTES) != hipSuccess ||
             MV_SET_MAX_SMEM((conv1d_mfma_kernel<half_t, true, false>), CV_LDS_BYTES) != hipSuccess ||
             MV_SET_MAX_SMEM((conv1d_mfma_kernel<half_t, false, true>), CV_LDS_BYTES) != hipSuccess)
@@ -1897,6 +1957,7 @@ int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
     // (a post-activation stays with the double-buffer kernel: the ring kernel's epilogue leaves the fp16 saturation to the hardware and has no v_med3 to
     //  fold a lower bound into -- no layer of the models has one behind its BatchNorm)
     const bool ring = persist && stats == 0 && dense_rows && d.post_act == MV_ACT_NONE;
+    if (grp_cout > 0) MV_REQUIRE(ring || !persist, "conv1d: internal: a grouped layer reached a persistent kernel other than the ring kernel");
     // The ring walk's tail.  A launch lasts as many tile times as its longest walk: 3600 tiles of an MFA layer (256 utterances of 300 frames x 3072
     // channels) on 256 workgroups are 14.06 rounds, so 15 -- the last one with 16 workgroups at work.  (The headline batch has 298 frames: 3576 tiles =
     // 13.97 rounds, nothing to split -- since the tile ids are dense; with the holes of the walk before round 6 it was 15 rounds as well.)  Splitting K over workgroups (stream-K) would fill it, but sums a tile
@@ -1935,7 +1996,11 @@ int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream) {
         const int pgrid = (int)(tiles < persistent_blocks(d) ? round_up(tiles, 8) : persistent_blocks(d));
         if (ring) {
             a.ring_vb_end = tail_vb0;
-            MV_LAUNCH(conv1d_ring_persistent_kernel, (pgrid, 1, 1), (512, 1, 1), CVR_LDS_BYTES, stream, a);
+            if (grp_cout > 0) {
+                MV_LAUNCH(conv1d_ring_grouped_kernel, (pgrid, 1, 1), (512, 1, 1), CVR_LDS_BYTES, stream, a);
+            } else {
+                MV_LAUNCH(conv1d_ring_persistent_kernel, (pgrid, 1, 1), (512, 1, 1), CVR_LDS_BYTES, stream, a);
+            }
             if (tail_nv > 0) {
                 prof_end(prof, stream);
                 int rc = check_launch("conv1d_ring_persistent_kernel");
@@ -2030,7 +2095,35 @@ int mv_conv1d_in_stats_finish(const float* in_stat_sum, const float* in_stat_sq,
 
 int mv_conv1d_forward(const MvConv1dDesc* d, mv_stream_t stream) {
     MV_REQUIRE(d != nullptr, "mv_conv1d_forward: null descriptor");
-    return mv::conv1d_launch(*d, static_cast<hipStream_t>(stream));
+    return mv::conv1d_launch(*d, static_cast<hipStream_t>(stream), 1);
+}
+
+int32_t mv_conv1d_grouped_native(int32_t cout, int32_t cin, int32_t k, int32_t groups) {
+    return mv::conv1d_grouped_native(cout, cin, k, groups) ? 1 : 0;
+}
+
+int64_t mv_conv1d_grouped_packed_elems(int32_t cout, int32_t cin, int32_t k, int32_t groups) {
+    if (groups < 1 || cin % groups != 0 || cout % groups != 0) return -1;
+    return mv::conv1d_grouped_native(cout, cin, k, groups) ? mv_conv1d_packed_elems(cout, cin / groups, k) : mv_conv1d_packed_elems(cout, cin, k);
+}
+
+int mv_conv1d_pack_weight_grouped(const float* w, int32_t cout, int32_t cin, int32_t k, int32_t groups, void* packed_f16, mv_stream_t stream) {
+    MV_REQUIRE(w != nullptr && packed_f16 != nullptr && cout > 0 && cin > 0 && k > 0 && groups >= 1, "mv_conv1d_pack_weight_grouped: bad argument");
+    MV_REQUIRE(cin % groups == 0 && cout % groups == 0, "mv_conv1d_pack_weight_grouped: cin and cout must be divisible by groups");
+    if (groups == 1 || mv::conv1d_grouped_native(cout, cin, k, groups)) return mv_conv1d_pack_weight(w, cout, cin / groups, k, packed_f16, stream);
+    const int64_t total = mv_conv1d_packed_elems(cout, cin, k);
+    const int grid = (int)(mv::ceil_div(total, 256) < 2048 ? mv::ceil_div(total, 256) : 2048);
+    MV_LAUNCH(mv::pack_conv_weight_grouped_kernel, (grid, 1, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), w, cout, cin, k, groups,
+              mv::conv1d_cout_pad(cout), mv::conv1d_cin_pad(cin), reinterpret_cast<half_t*>(packed_f16));
+    return mv::check_launch("pack_conv_weight_grouped_kernel");
+}
+
+int mv_conv1d_forward_grouped(const MvConv1dDesc* d, int32_t groups, mv_stream_t stream) {
+    MV_REQUIRE(d != nullptr, "mv_conv1d_forward_grouped: null descriptor");
+    MV_REQUIRE(groups >= 1, "mv_conv1d_forward_grouped: groups must be positive");
+    MV_REQUIRE(d->cin % groups == 0 && d->cout % groups == 0, "mv_conv1d_forward_grouped: cin and cout must be divisible by groups");
+    const bool native = mv::conv1d_grouped_native(d->cout, d->cin, d->k, groups);
+    return mv::conv1d_launch(*d, static_cast<hipStream_t>(stream), native ? groups : 1);   // expanded: the block-diagonal weight, a dense layer
 }
 
 }  // extern "C"

@@ -9,7 +9,9 @@ int conv1d_cout_pad(int cout);
 // finish pass of the time statistics a persistent-kernel epilogue can emit (MvConv1dDesc.stat_sum / stat_sq)
 int conv_stats_finish_launch(const float* psum, const float* psq, const float* shift, int B, int T, int C, float* mean, float* stdv,
                              int64_t ld_out, float clamp_eps, hipStream_t stream);
-int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream);
+// groups > 1: a native grouped 1x1 layer (conv1d_grouped_native; d.cin / d.cout are the layer's, w_packed the per-group packing)
+int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream, int groups = 1);
+bool conv1d_grouped_native(int cout, int cin, int k, int groups);
 // fused time statistics of a 1x1 layer's INPUT (MvConv1dDesc.in_stat_sum / in_stat_sq): partial buffer size and the finish pass
 int64_t conv_in_stats_elems(int B, int T, int cin);
 int conv_in_stats_finish_launch(const float* psum, const float* psq, int B, int T, int C, float* mean, float* stdv, int64_t ld_out,

@@ -20,6 +20,7 @@ struct ConvLayer {
     half_t* w = nullptr;    // packed fp16 [Cout_pad][k][Cin_pad]
     float* bias = nullptr;  // [cout] or null
     int cout = 0, cin = 0, k = 1;
+    int groups = 1;         // > 1: a native grouped 1x1 layer (conv1d_grouped_native): w packed per group, cin the layer's whole width
 };
 
 struct MvModelBase {

@@ -166,7 +166,7 @@ int run_conv(const ConvLayer& L, const void* x, int x_dtype, int64_t ldx, const 
     d.stride = 1;
     d.pad = pad;
     d.pad_mode = pad_mode;
-    return conv1d_launch(d, stream);
+    return conv1d_launch(d, stream, L.groups);
 }
 
 // --------------------------------------------------------------------------------------- ASP tail
@@ -360,9 +360,46 @@ int fold_final_linear(MvModelBase* m, const Weights& w, const std::string& weigh
 
 // --------------------------------------------------------------------------------------- EcapaTdnn
 
+// grouped fp32 [cout][cin / g][k] state_dict weight -> the host copy of its block-diagonal dense [cout][cin][k] form (g = 1: the weight itself)
+static int host_dense_weight(const Weights& w, const std::string& name, int cout, int cin, int k, int g, std::vector<float>& out) {
+    std::vector<float> wg;
+    const int cin_g = cin / g, cout_g = cout / g;
+    int rc = w.host(name, (int64_t)cout * cin_g * k, wg);
+    if (rc != MV_OK) return rc;
+    if (g == 1) {
+        out.swap(wg);
+        return MV_OK;
+    }
+    out.assign((size_t)cout * cin * k, 0.0f);
+    for (int co = 0; co < cout; ++co)
+        memcpy(&out[((size_t)co * cin + (size_t)(co / cout_g) * cin_g) * k], &wg[(size_t)co * cin_g * k], (size_t)cin_g * k * sizeof(float));
+    return MV_OK;
+}
+
+// MvEcapaCfg (three SE-Res2Net blocks, no groups) as the extended config
+static MvEcapaCfgEx ecapa_cfg_ex(const MvEcapaCfg& c) {
+    MvEcapaCfgEx e;
+    memset(&e, 0, sizeof(e));
+    e.input_size = c.input_size;
+    e.embd_dim = c.embd_dim;
+    e.nblocks = 3;
+    for (int i = 0; i < 5; ++i) {
+        e.channels[i] = c.channels[i];
+        e.kernel_sizes[i] = c.kernel_sizes[i];
+        e.dilations[i] = c.dilations[i];
+        e.groups[i] = 1;
+    }
+    e.attention_channels = c.attention_channels;
+    e.res2net_scale = c.res2net_scale;
+    e.se_channels = c.se_channels;
+    e.global_context = c.global_context;
+    return e;
+}
+
 struct EcapaModel : MvModelBase {
-    MvEcapaCfg cfg;
-    int nblocks = 0;  // SE-Res2Net blocks
+    MvEcapaCfgEx cfg;
+    int nblocks = 0;  // SE-Res2Net blocks: entries 1 .. nblocks of the per-layer arrays; entry nblocks + 1 is the MFA
+    int n_grouped_native = 0, n_grouped_expanded = 0, n_expanded_1x1 = 0;   // mv_model_info MV_INFO_ECAPA_*
     struct TdnnBlk {
         ConvLayer conv;
         float* scale = nullptr;
@@ -390,31 +427,90 @@ struct EcapaModel : MvModelBase {
     float* fc_b = nullptr;
     int ccat = 0, cmax = 0;
 
-    int pooled_width() const { return pool == MV_POOL_ASP ? 2 * cfg.channels[4] : head.width(); }
+    int cm() const { return cfg.channels[nblocks + 1]; }   // the MFA's width (channels[-1])
+    int pooled_width() const { return pool == MV_POOL_ASP ? 2 * cm() : head.width(); }
 
-    int make_tdnn(const Weights& w, const std::string& prefix, int cout, int cin, int k, TdnnBlk* out) {
-        int rc = make_conv(w, prefix + ".conv.conv.weight", prefix + ".conv.conv.bias", cout, cin, k, &out->conv);
+    // a TDNNBlock with `groups` (models/utils.py:120-138): 1 = dense; a grouped 1x1 layer of the native geometry is packed per group and runs as a
+    // grouped GEMM; any other grouped layer becomes its block-diagonal dense weight (exact zeros)
+    int make_tdnn(const Weights& w, const std::string& prefix, int cout, int cin, int k, TdnnBlk* out, int groups = 1) {
+        int rc;
+        const std::string wn = prefix + ".conv.conv.weight", bn = prefix + ".conv.conv.bias";
+        if (groups == 1) {
+            rc = make_conv(w, wn, bn, cout, cin, k, &out->conv);
+        } else if (conv1d_grouped_native(cout, cin, k, groups)) {
+            rc = make_conv(w, wn, bn, cout, cin / groups, k, &out->conv);
+            out->conv.cin = cin;
+            out->conv.groups = groups;
+            ++n_grouped_native;
+        } else {
+            std::vector<float> dense;
+            if ((rc = host_dense_weight(w, wn, cout, cin, k, groups, dense))) return rc;
+            float* tmp = upload(dense);
+            if (tmp == nullptr) return fail(MV_ERR_HIP, "ecapa create: upload failed");
+            rc = make_conv_from(tmp, &w, bn, cout, cin, k, &out->conv);
+            ++n_grouped_expanded;
+            n_expanded_1x1 += k == 1;
+        }
         if (rc != MV_OK) return rc;
         return make_bn(w, prefix + ".norm.norm", cout, &out->scale, &out->shift);
     }
 
-    int create(const MvEcapaCfg& c, const Weights& w, int pool_type) {
+    int info(int key, float* value) const override {
+        switch (key) {
+            case MV_INFO_ECAPA_GROUPED_NATIVE: *value = (float)n_grouped_native; return MV_OK;
+            case MV_INFO_ECAPA_GROUPED_EXPANDED: *value = (float)n_grouped_expanded; return MV_OK;
+            case MV_INFO_ECAPA_EXPANDED_1X1: *value = (float)n_expanded_1x1; return MV_OK;
+            case MV_INFO_ECAPA_BLOCKS: *value = (float)nblocks; return MV_OK;
+            default: return MvModelBase::info(key, value);
+        }
+    }
+
+    int create(const MvEcapaCfgEx& c, const Weights& w, int pool_type) {
         cfg = c;
         pool = pool_type;
         input_size = c.input_size;
         embd_dim = c.embd_dim;
         int rc;
+        MV_REQUIRE(c.nblocks >= 1 && c.nblocks <= MV_ECAPA_MAX_BLOCKS,
+                   "ecapa: nblocks must be 1 .. " + std::to_string(MV_ECAPA_MAX_BLOCKS) + " (len(channels) - 2 SE-Res2Net blocks), got " +
+                       std::to_string(c.nblocks));
+        nblocks = c.nblocks;
         MV_REQUIRE(c.res2net_scale >= 2 && c.res2net_scale <= 16, "ecapa: res2net_scale out of range");
         MV_REQUIRE(c.input_size > 0, "ecapa: input_size must be positive");
+        {
+            int sum = 0;
+            for (int i = 0; i < nblocks + 2; ++i) {
+                MV_REQUIRE(c.channels[i] > 0 && c.kernel_sizes[i] > 0 && c.dilations[i] > 0,
+                           "ecapa: channels, kernel_sizes and dilations must be positive (entry " + std::to_string(i) + ")");
+                MV_REQUIRE(c.groups[i] >= 1, "ecapa: groups must be positive (entry " + std::to_string(i) + ")");
+                if (i >= 1 && i <= nblocks) sum += c.channels[i];
+            }
+            MV_REQUIRE(sum == c.channels[nblocks + 1], "ecapa: channels[-1] must equal the sum of the SE-Res2Net block widths (" +
+                                                           std::to_string(c.channels[nblocks + 1]) + " != " + std::to_string(sum) + ")");
+            auto divisible = [&](int i, int cin, int cout) {
+                return cin % c.groups[i] == 0 && cout % c.groups[i] == 0;
+            };
+            MV_REQUIRE(divisible(0, c.input_size, c.channels[0]), "ecapa: blocks.0: input_size and channels[0] must be divisible by groups[0]");
+            for (int i = 1; i <= nblocks; ++i)
+                MV_REQUIRE(divisible(i, c.channels[i - 1], c.channels[i]),
+                           "ecapa: block " + std::to_string(i) + ": channels[" + std::to_string(i - 1) + "] and channels[" + std::to_string(i) +
+                               "] must be divisible by groups[" + std::to_string(i) + "]");
+            MV_REQUIRE(divisible(nblocks + 1, sum, c.channels[nblocks + 1]), "ecapa: mfa: channels[-1] must be divisible by groups[-1]");
+        }
         // The features enter block 0 at the pitch Fp = round_up(F, 8) (the fp16 copy of forward(); for a ragged F its channels F..Fp-1 are
         // zeros), and block 0's weights get zero input columns F..Fp-1: a zero weight times a finite feature adds an exact zero, so F = 201
         // computes the bits of F = 208 with zero-padded features and weights.  For F % 8 == 0 nothing is padded.
-        const int F = c.input_size, Fp = (int)round_up(F, 8), k0 = c.kernel_sizes[0], C0 = c.channels[0];
-        if (Fp == F) {
+        // A grouped blocks.0 (groups[0] > 1) is expanded into its block-diagonal dense weight first (host_dense_weight): the rest is the dense layer's.
+        const int F = c.input_size, Fp = (int)round_up(F, 8), k0 = c.kernel_sizes[0], C0 = c.channels[0], g0 = c.groups[0];
+        if (g0 > 1) {
+            ++n_grouped_expanded;
+            n_expanded_1x1 += k0 == 1;
+        }
+        if (Fp == F && g0 == 1) {
             if ((rc = make_tdnn(w, "blocks.0", C0, F, k0, &block0))) return rc;
         } else {
             std::vector<float> w0, wp((size_t)C0 * Fp * k0, 0.0f);
-            if ((rc = w.host("blocks.0.conv.conv.weight", (int64_t)C0 * F * k0, w0))) return rc;
+            if ((rc = host_dense_weight(w, "blocks.0.conv.conv.weight", C0, F, k0, g0, w0))) return rc;
             for (int co = 0; co < C0; ++co)
                 memcpy(&wp[(size_t)co * Fp * k0], &w0[(size_t)co * F * k0], (size_t)F * k0 * sizeof(float));
             float* tmp = upload(wp);
@@ -428,7 +524,7 @@ struct EcapaModel : MvModelBase {
         block0_window = c.dilations[0] == 1 && k0 > 1 && (k0 % 2) == 1;
         if (block0_window) {
             std::vector<float> w0, wr((size_t)C0 * k0 * Fp, 0.0f);
-            if ((rc = w.host("blocks.0.conv.conv.weight", (int64_t)C0 * F * k0, w0))) return rc;
+            if ((rc = host_dense_weight(w, "blocks.0.conv.conv.weight", C0, F, k0, g0, w0))) return rc;
             for (int co = 0; co < C0; ++co)
                 for (int ci = 0; ci < F; ++ci)
                     for (int j = 0; j < k0; ++j) wr[((size_t)co * k0 + j) * Fp + ci] = w0[((size_t)co * F + ci) * k0 + j];
@@ -436,7 +532,6 @@ struct EcapaModel : MvModelBase {
             if (tmp == nullptr) return fail(MV_ERR_HIP, "ecapa create: upload failed");
             if ((rc = make_conv_from(tmp, &w, "blocks.0.conv.conv.bias", C0, k0 * Fp, 1, &block0w))) return rc;
         }
-        nblocks = 3;
         blocks.resize(nblocks);
         ccat = 0;
         cmax = c.channels[0];
@@ -449,12 +544,12 @@ struct EcapaModel : MvModelBase {
             MV_REQUIRE(b.cout % (8 * c.res2net_scale) == 0, "ecapa: channels must be a multiple of 8 * res2net_scale");
             b.width = b.cout / c.res2net_scale;
             const std::string p = "blocks." + std::to_string(i + 1);
-            if ((rc = make_tdnn(w, p + ".tdnn1", b.cout, b.cin, 1, &b.tdnn1))) return rc;
+            if ((rc = make_tdnn(w, p + ".tdnn1", b.cout, b.cin, 1, &b.tdnn1, c.groups[i + 1]))) return rc;
             b.res2.resize(c.res2net_scale - 1);
             for (int j = 0; j < c.res2net_scale - 1; ++j)
                 if ((rc = make_tdnn(w, p + ".res2net_block.blocks." + std::to_string(j), b.width, b.width, b.k, &b.res2[j])))
                     return rc;
-            if ((rc = make_tdnn(w, p + ".tdnn2", b.cout, b.cout, 1, &b.tdnn2))) return rc;
+            if ((rc = make_tdnn(w, p + ".tdnn2", b.cout, b.cout, 1, &b.tdnn2, c.groups[i + 1]))) return rc;
             std::vector<float> t;
             if ((rc = w.host(p + ".se_block.conv1.conv.weight", (int64_t)c.se_channels * b.cout, t))) return rc;
             b.se_w1 = upload(t);
@@ -471,16 +566,17 @@ struct EcapaModel : MvModelBase {
             ccat += b.cout;
             cmax = b.cout > cmax ? b.cout : cmax;
         }
-        MV_REQUIRE(ccat == c.channels[4], "ecapa: channels[-1] must equal the sum of the SE-Res2Net block widths");
-        if ((rc = make_tdnn(w, "mfa", c.channels[4], ccat, c.kernel_sizes[4], &mfa))) return rc;
+        const int M = nblocks + 1;   // the MFA's entry
+        MV_REQUIRE(ccat == c.channels[M], "ecapa: channels[-1] must equal the sum of the SE-Res2Net block widths");
+        if ((rc = make_tdnn(w, "mfa", c.channels[M], ccat, c.kernel_sizes[M], &mfa, c.groups[M]))) return rc;
         if (pool == MV_POOL_ASP) {
-            if ((rc = asp.create(this, w, "asp", c.channels[4], c.attention_channels, c.global_context != 0))) return rc;
-            if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn.norm", "", c.embd_dim, 2 * c.channels[4],
+            if ((rc = asp.create(this, w, "asp", c.channels[M], c.attention_channels, c.global_context != 0))) return rc;
+            if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn.norm", "", c.embd_dim, 2 * c.channels[M],
                                         &fc_w, &fc_b)))
                 return rc;
         } else {
             // SAP / TAP / TSP: asp_bn is a plain BatchNorm1d over the head's width (ecapa_tdnn.py:229-250)
-            if ((rc = head.create(this, w, "asp", pool, c.channels[4]))) return rc;
+            if ((rc = head.create(this, w, "asp", pool, c.channels[M]))) return rc;
             if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn", "", c.embd_dim, head.width(), &fc_w, &fc_b)))
                 return rc;
         }
@@ -507,7 +603,7 @@ struct EcapaModel : MvModelBase {
         s.r2 = c.take<half_t>(N * cmax);
         s.t2 = c.take<half_t>(N * cmax);
         s.sc = c.take<half_t>(N * cmax);
-        s.mfa = c.take<half_t>(N * cfg.channels[4]);
+        s.mfa = c.take<half_t>(N * cm());
         s.h = c.take<half_t>(N * (pool == MV_POOL_ASP ? cfg.attention_channels : head.hidden_width()));
         s.se_mean = c.take<float>((size_t)B * cmax);
         s.se_hid = c.take<float>((size_t)B * cfg.se_channels);
@@ -530,7 +626,7 @@ struct EcapaModel : MvModelBase {
         MV_REQUIRE(feats != nullptr && emb != nullptr && ws != nullptr, "ecapa forward: null buffer");
         MV_REQUIRE(B > 0 && T > 0, "ecapa forward: empty batch");
         int maxpad = cfg.dilations[0] * (cfg.kernel_sizes[0] - 1) / 2;
-        for (int i = 1; i < 5; ++i) {
+        for (int i = 1; i < nblocks + 2; ++i) {
             const int p = cfg.dilations[i] * (cfg.kernel_sizes[i] - 1) / 2;
             maxpad = p > maxpad ? p : maxpad;
         }
@@ -623,11 +719,11 @@ struct EcapaModel : MvModelBase {
             ldin = ccat;
             cat_off += C;
         }
-        // multi-layer feature aggregation reads the three block outputs in place
-        const int Cm = cfg.channels[4];
+        // multi-layer feature aggregation reads the N block outputs in place
+        const int Cm = cm(), M = nblocks + 1;
         // (the ASP global mean / std of pooling.py:104-109 are collected by the ASP hidden conv from its own input tiles: AspLayer::forward)
-        if ((rc = run_conv(mfa.conv, s.cat, MV_DT_F16, ccat, nullptr, 0, s.mfa, MV_DT_F16, Cm, B, T, T, cfg.dilations[4],
-                           cfg.dilations[4] * (cfg.kernel_sizes[4] - 1) / 2, R, MV_ACT_RELU, mfa.scale, mfa.shift, MV_ACT_NONE,
+        if ((rc = run_conv(mfa.conv, s.cat, MV_DT_F16, ccat, nullptr, 0, s.mfa, MV_DT_F16, Cm, B, T, T, cfg.dilations[M],
+                           cfg.dilations[M] * (cfg.kernel_sizes[M] - 1) / 2, R, MV_ACT_RELU, mfa.scale, mfa.shift, MV_ACT_NONE,
                            nullptr, true, st)))
             return rc;
         if (pool == MV_POOL_ASP) {
@@ -772,7 +868,7 @@ int mv_ecapa_create(const MvEcapaCfg* cfg, const MvTensorRef* tensors, int32_t n
     int rc = w.init(tensors, num_tensors);
     if (rc != MV_OK) return rc;
     auto m = std::make_unique<mv::EcapaModel>();
-    rc = m->create(*cfg, w, MV_POOL_ASP);
+    rc = m->create(mv::ecapa_cfg_ex(*cfg), w, MV_POOL_ASP);
     if (rc != MV_OK) return rc;
     *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
     return MV_OK;
@@ -781,6 +877,19 @@ int mv_ecapa_create(const MvEcapaCfg* cfg, const MvTensorRef* tensors, int32_t n
 int mv_ecapa_create_pooled(const MvEcapaCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
     MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_ecapa_create_pooled: null argument");
     int rc = mv::check_pool_type(pooling_type, "mv_ecapa_create_pooled");
+    if (rc != MV_OK) return rc;
+    mv::Weights w;
+    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
+    auto m = std::make_unique<mv::EcapaModel>();
+    rc = m->create(mv::ecapa_cfg_ex(*cfg), w, pooling_type);
+    if (rc != MV_OK) return rc;
+    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
+    return MV_OK;
+}
+
+int mv_ecapa_create_ex(const MvEcapaCfgEx* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
+    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_ecapa_create_ex: null argument");
+    int rc = mv::check_pool_type(pooling_type, "mv_ecapa_create_ex");
     if (rc != MV_OK) return rc;
     mv::Weights w;
     if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;

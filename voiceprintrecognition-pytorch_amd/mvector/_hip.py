@@ -58,6 +58,18 @@ class MvEcapaCfg(ctypes.Structure):
                 ('se_channels', c_i32), ('global_context', c_i32)]
 
 
+MV_ECAPA_MAX_BLOCKS = 16
+MV_INFO_ECAPA_GROUPED_NATIVE, MV_INFO_ECAPA_GROUPED_EXPANDED, MV_INFO_ECAPA_EXPANDED_1X1, MV_INFO_ECAPA_BLOCKS = 20, 21, 22, 23
+
+
+class MvEcapaCfgEx(ctypes.Structure):
+    """EcapaTdnn with N = nblocks SE-Res2Net blocks and per-layer groups (mv_ecapa_create_ex): arrays of N + 2 used entries"""
+    _fields_ = [('input_size', c_i32), ('embd_dim', c_i32), ('nblocks', c_i32), ('channels', c_i32 * (MV_ECAPA_MAX_BLOCKS + 2)),
+                ('kernel_sizes', c_i32 * (MV_ECAPA_MAX_BLOCKS + 2)), ('dilations', c_i32 * (MV_ECAPA_MAX_BLOCKS + 2)),
+                ('groups', c_i32 * (MV_ECAPA_MAX_BLOCKS + 2)), ('attention_channels', c_i32), ('res2net_scale', c_i32),
+                ('se_channels', c_i32), ('global_context', c_i32)]
+
+
 class MvCamppCfg(ctypes.Structure):
     _fields_ = [('input_size', c_i32), ('embd_dim', c_i32), ('growth_rate', c_i32), ('bn_size', c_i32),
                 ('init_channels', c_i32), ('head_precision', c_i32), ('xvector_probe', c_i32)]
@@ -118,6 +130,7 @@ _SIGNATURES = {
     'mv_tdnn_create': (c_i32, [ctypes.POINTER(MvTdnnCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_ecapa_create_pooled': (c_i32, [ctypes.POINTER(MvEcapaCfg), c_i32, ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_tdnn_create_pooled': (c_i32, [ctypes.POINTER(MvTdnnCfg), c_i32, ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
+    'mv_ecapa_create_ex': (c_i32, [ctypes.POINTER(MvEcapaCfgEx), c_i32, ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_eres2net_create': (c_i32, [ctypes.POINTER(MvEres2Cfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_conv2d_first': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'mv_tstp_f32': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
@@ -138,6 +151,10 @@ _SIGNATURES = {
     'mv_conv1d_packed_elems': (c_i64, [c_i32, c_i32, c_i32]),
     'mv_conv1d_pack_weight': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'mv_conv1d_forward': (c_i32, [ctypes.POINTER(MvConv1dDesc), c_vp]),
+    'mv_conv1d_grouped_native': (c_i32, [c_i32, c_i32, c_i32, c_i32]),
+    'mv_conv1d_grouped_packed_elems': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    'mv_conv1d_pack_weight_grouped': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'mv_conv1d_forward_grouped': (c_i32, [ctypes.POINTER(MvConv1dDesc), c_i32, c_vp]),
     'mv_conv1d_stats_elems': (c_i64, [c_i32, c_i32, c_i32]),
     'mv_conv1d_in_stats_elems': (c_i64, [c_i32, c_i32, c_i32]),
     'mv_conv1d_in_stats_finish': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_f32, c_vp]),
@@ -603,7 +620,11 @@ class Model:
             refs[i].data = t.data_ptr()
             refs[i].numel = t.numel()
         self._h = c_vp()
-        if pool == MV_POOL_ASP:   # (the plain create calls: the handles every ASP model has always built)
+        if isinstance(cfg, MvEcapaCfgEx):   # EcapaTdnn with other block counts / grouped convolutions: one create call for every head
+            if kind != 'ecapa':
+                raise ValueError(f'an MvEcapaCfgEx config belongs to the ecapa handle, not {kind!r}')
+            create = lambda c, r, n, out: self._cdll.mv_ecapa_create_ex(c, pool, r, n, out)   # noqa: E731
+        elif pool == MV_POOL_ASP:   # (the plain create calls: the handles every ASP model has always built)
             create = {'ecapa': self._cdll.mv_ecapa_create, 'campp': self._cdll.mv_campp_create,
                       'tdnn': self._cdll.mv_tdnn_create, 'eres2net': self._cdll.mv_eres2net_create}[kind]
         else:
@@ -623,7 +644,8 @@ class Model:
         return n.value
 
     def info(self, key):
-        """mv_model_info: 1 = CAM++ head on fp32 maps (1.0 / 0.0), 2 = its creation-time calibration 1 - cos, 3 + p = probe p's figure"""
+        """mv_model_info: 1 = CAM++ head on fp32 maps (1.0 / 0.0), 2 = its creation-time calibration 1 - cos, 3 + p = probe p's figure;
+        EcapaTdnn: MV_INFO_ECAPA_* (20 grouped layers on the grouped GEMM, 21 expanded, 22 expanded 1x1 ones, 23 SE-Res2Net blocks)"""
         v = c_f32()
         check(self._cdll.mv_model_info(self._h, key, ctypes.byref(v)), self._cdll)
         return v.value

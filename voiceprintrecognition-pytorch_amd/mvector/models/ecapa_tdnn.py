@@ -10,6 +10,11 @@ from mvector.models.pooling import (AttentiveStatisticsPooling, SelfAttentivePoo
 from mvector.models.utils import BatchNorm1d, Conv1d, TDNNBlock, length_to_mask
 
 
+def _hip_max_blocks():
+    from mvector import _hip
+    return _hip.MV_ECAPA_MAX_BLOCKS
+
+
 class Res2NetBlock(nn.Module):
     """Hierarchical residual over `scale` channel groups; group 0 passes through."""
 
@@ -118,24 +123,35 @@ class EcapaTdnn(NativeBackbone, nn.Module):
         # goes together with test_emu_kernels.py::test_unsupported_constructor_arguments_are_named_not_approximated, which pins the refusal.
         if c['pooling_type'] not in ('ASP', 'SAP', 'TAP'):
             return False, f"pooling_type={c['pooling_type']!r}"
-        if any(g != 1 for g in c['groups']):
-            return False, 'grouped convolution'
         if not c['relu']:
             return False, 'a non-ReLU activation'
-        if len(c['channels']) != 5:
-            return False, 'a block count other than 3 SE-Res2Net blocks'
+        # any block count the native config holds, and grouped TDNN convolutions (mv_ecapa_create_ex; the library refuses, with its message,
+        # what the reference cannot run either: channels[-1] != the sum of the block widths, a width not divisible by its groups)
+        n = len(c['channels']) - 2
+        if not 1 <= n <= _hip_max_blocks():
+            return False, f'{n} SE-Res2Net blocks (the native handle takes 1 .. {_hip_max_blocks()})'
         return True, ''
 
     def _native_pooling_type(self):
         return self._cfg['pooling_type']
 
     def _native_cfg(self):
+        """MvEcapaCfg for the three-block ungrouped model (the handle it has always built), MvEcapaCfgEx for every other block count or
+        groups: the per-layer groups indexed by position as the constructor does (blocks.0: groups[0], block i: groups[i], MFA: groups[-1])"""
         from mvector import _hip
         c = self._cfg
-        cfg = _hip.MvEcapaCfg()
+        ch, n = c['channels'], len(c['channels']) - 2
+        groups = [c['groups'][i] for i in range(n + 1)] + [c['groups'][-1]]
+        if n == 3 and all(g == 1 for g in groups):
+            cfg = _hip.MvEcapaCfg()
+        else:
+            cfg = _hip.MvEcapaCfgEx()
+            cfg.nblocks = n
+            for i, g in enumerate(groups):
+                cfg.groups[i] = g
         cfg.input_size, cfg.embd_dim = c['input_size'], self.embd_dim
-        for i in range(5):
-            cfg.channels[i], cfg.kernel_sizes[i], cfg.dilations[i] = c['channels'][i], c['kernel_sizes'][i], c['dilations'][i]
+        for i in range(n + 2):
+            cfg.channels[i], cfg.kernel_sizes[i], cfg.dilations[i] = ch[i], c['kernel_sizes'][i], c['dilations'][i]
         cfg.attention_channels, cfg.res2net_scale = c['attention_channels'], c['res2net_scale']
         cfg.se_channels, cfg.global_context = c['se_channels'], int(bool(c['global_context']))
         return cfg
