@@ -792,25 +792,10 @@ struct CamppModel : MvModelBase {
         // ---- xvector.tdnn: k=5, stride 2, zero pad 2, BN, ReLU -> first slice of block 1's buffer ----
         const int T2 = s.T2;
         {
-            MvConv1dDesc d;
-            memset(&d, 0, sizeof(d));
-            d.x = s.rows;
-            d.x_dtype = MV_DT_F16;
-            d.ldx = 32 * F8;
-            d.w_packed = tdnn.w;
+            MvConv1dDesc d = conv_desc(tdnn, s.rows, 32 * F8, s.xb[0], blocks[0].c_out, B, T, T2);
             d.scale = tdnn_scale;
             d.shift = tdnn_shift;
             d.post_act = MV_ACT_RELU;
-            d.y = s.xb[0];
-            d.y_dtype = MV_DT_F16;
-            d.ldy = blocks[0].c_out;
-            d.B = B;
-            d.T_in = T;
-            d.T_out = T2;
-            d.cin = 32 * F8;
-            d.cout = cfg.init_channels;
-            d.k = 5;
-            d.dilation = 1;
             d.stride = 2;
             d.pad = 2;
             d.pad_mode = MV_PAD_ZERO;
@@ -844,28 +829,12 @@ struct CamppModel : MvModelBase {
                     continue;
                 }
                 // every other geometry (bottleneck / growth widths the fused kernels are not built for): five launches
-                MvConv1dDesc d;
-                memset(&d, 0, sizeof(d));
-                d.x = X;
-                d.x_dtype = MV_DT_F16;
-                d.ldx = ld;
+                MvConv1dDesc d = conv_desc(L.lin1, X, ld, s.h, bn_ch, B, T2, T2);
                 d.in_scale = L.bn1_s;
                 d.in_shift = L.bn1_t;
-                d.w_packed = L.lin1.w;
                 d.scale = L.bn2_s;
                 d.shift = L.bn2_t;
                 d.post_act = MV_ACT_RELU;
-                d.y = s.h;
-                d.y_dtype = MV_DT_F16;
-                d.ldy = bn_ch;
-                d.B = B;
-                d.T_in = d.T_out = T2;
-                d.cin = L.cin;
-                d.cout = bn_ch;
-                d.k = 1;
-                d.dilation = 1;
-                d.stride = 1;
-                d.pad = 0;
                 d.pad_mode = MV_PAD_ZERO;
                 if ((rc = conv1d_launch(d, st))) return rc;
                 if ((rc = seg_mean_launch(s.h, bn_ch, B, T2, bn_ch, 100, s.ctx, st))) return rc;
@@ -874,23 +843,10 @@ struct CamppModel : MvModelBase {
                     return rc;
                 if ((rc = linear_f32_launch(s.g1, bn_ch / 2, L.wb, bn_ch / 2, L.bb, MV_ACT_SIGMOID, s.gate, G, rows, bn_ch / 2, G, 0, st)))
                     return rc;
-                memset(&d, 0, sizeof(d));
-                d.x = s.h;
-                d.x_dtype = MV_DT_F16;
-                d.ldx = bn_ch;
-                d.w_packed = L.local.w;
+                d = conv_desc(L.local, s.h, bn_ch, X + L.cin, ld, B, T2, T2);
                 d.gate = s.gate;
                 d.gate_seg_len = 100;
-                d.y = X + L.cin;
-                d.y_dtype = MV_DT_F16;
-                d.ldy = ld;
-                d.B = B;
-                d.T_in = d.T_out = T2;
-                d.cin = bn_ch;
-                d.cout = G;
-                d.k = 3;
                 d.dilation = Bk.dil;
-                d.stride = 1;
                 d.pad = Bk.dil;
                 d.pad_mode = MV_PAD_ZERO;
                 if ((rc = conv1d_launch(d, st))) return rc;
@@ -901,27 +857,11 @@ struct CamppModel : MvModelBase {
             // The 512-channel block (c_out 256 after it) keeps transform-on-load (measured equal).
             const bool pre = Bk.c_out >= 512;
             if (pre && (rc = bn_relu_rows_launch(X, ld, Bk.tr_s, Bk.tr_t, s.act, Bk.c_out, (int64_t)B * T2, Bk.c_out, st))) return rc;
-            MvConv1dDesc d;
-            memset(&d, 0, sizeof(d));
-            d.x = pre ? s.act : X;
-            d.x_dtype = MV_DT_F16;
-            d.ldx = ld;  // (the pre-activated copy keeps the block buffer's leading dimension)
+            // (the pre-activated copy keeps the block buffer's leading dimension)
+            MvConv1dDesc d = conv_desc(Bk.transit, pre ? s.act : X, ld, bi < 2 ? s.xb[bi + 1] : s.last, bi < 2 ? blocks[bi + 1].c_out : cfin, B, T2, T2);
             if (pre && (Bk.c_out / 2) % 256 == 0 && (int64_t)B * T2 >= 16384) d.tile = 256;  // 256 x 256 tiles on the ring kernel even where they do not fill the chip (149 tiles for the first transit: r10i)
             d.in_scale = pre ? nullptr : Bk.tr_s;
             d.in_shift = pre ? nullptr : Bk.tr_t;
-            d.w_packed = Bk.transit.w;
-            d.bias = Bk.transit.bias;
-            d.y = bi < 2 ? s.xb[bi + 1] : s.last;
-            d.y_dtype = MV_DT_F16;
-            d.ldy = bi < 2 ? blocks[bi + 1].c_out : cfin;
-            d.B = B;
-            d.T_in = d.T_out = T2;
-            d.cin = Bk.c_out;
-            d.cout = Bk.c_out / 2;
-            d.k = 1;
-            d.dilation = 1;
-            d.stride = 1;
-            d.pad = 0;
             d.pad_mode = MV_PAD_ZERO;
             if ((rc = conv1d_launch(d, st))) return rc;
         }

@@ -1734,28 +1734,79 @@ bool conv1d_grouped_native(int cout, int cin, int k, int groups) {
 int conv1d_cin_pad(int cin) { return (int)round_up(cin, CV_BK); }
 int conv1d_cout_pad(int cout) { return (int)round_up(cout, 32); }
 
+// ---- host side: check the descriptor, plan the launches, launch --------------------------------------------------------------------------
+
+// The kernels conv1d_launch runs, one table row each: the only place that names the instantiations.  The attribute loop (dynamic LDS above 64 KiB
+// has to be requested per kernel) and every launch go through the table.
+enum ConvKernel {
+    CK_GLDS_128, CK_GLDS_64, CK_GLDS_128_TAIL, CK_GLDS_160, CK_GLDS_160_IN_STATS, CK_GLDS_256,   // one-shot direct-to-LDS kernels by tile
+    CK_PERSIST_1X1, CK_PERSIST_1X1_SUM, CK_PERSIST_1X1_SUM_SQ,   // persistent 256 x 256 kernel, 1x1 with cin % 64 == 0: no / time sums / sums and squares
+    CK_PERSIST_TAPS,                                             // ... any k, any cin
+    CK_RING, CK_RING_GROUPED,
+    CK_MFMA_F32, CK_MFMA_X2, CK_MFMA_IN_AFFINE,   // through registers: fp32 x / second input added on load / BatchNorm + ReLU on load
+    CK_IN_STATS,                                  // the input statistics without the GEMM
+    CK_COUNT
+};
+
+struct ConvKernelRow {
+    ConvKernel id;
+    void (*fn)(ConvArgs);
+    int threads, lds_bytes;
+    int tile_rows, tile_ch;   // time steps x output channels of one workgroup's tile
+    const char* name;
+};
+
+// a conv1d_glds_kernel row: threads and tile follow from the template parameters as they do inside the kernel
+template <int WC, int WN, int MI, int NI, bool INSTATS = false, int NS = 2>
+constexpr ConvKernelRow glds_row(ConvKernel id, int lds_bytes, const char* name) {
+    return {id, conv1d_glds_kernel<WC, WN, MI, NI, INSTATS, NS>, 64 * WC * WN, lds_bytes, WN * NI * 16, WC * MI * 16, name};
+}
+#define MV_GLDS_ROW(id, lds_bytes, ...) glds_row<__VA_ARGS__>(id, lds_bytes, "conv1d_glds_kernel<" #__VA_ARGS__ ">")
+#define MV_CONV_ROW(id, threads, lds_bytes, tile_rows, tile_ch, ...) {id, __VA_ARGS__, threads, lds_bytes, tile_rows, tile_ch, #__VA_ARGS__}
+constexpr ConvKernelRow CONV_KERNELS[CK_COUNT] = {
+    MV_GLDS_ROW(CK_GLDS_128, CV_LDS_BYTES, 2, 2, 4, 4),
+    MV_GLDS_ROW(CK_GLDS_64, CV_LDS_BYTES_SMALL, 2, 2, 2, 2, false, CV_SMALL_NS),
+    MV_GLDS_ROW(CK_GLDS_128_TAIL, CV_LDS_BYTES_TAIL, 4, 2, 2, 4, false, CV_TAIL_NS),
+    MV_GLDS_ROW(CK_GLDS_160, CV_LDS_BYTES_WIDE, 2, 2, 4, 5),
+    MV_GLDS_ROW(CK_GLDS_160_IN_STATS, CV_LDS_BYTES_WIDE + CV_IN_STATS_BUF_BYTES, 2, 2, 4, 5, true),
+    MV_GLDS_ROW(CK_GLDS_256, CV_LDS_BYTES_BIG, 2, 4, 8, 4),
+    MV_CONV_ROW(CK_PERSIST_1X1, 512, CVP_LDS_BYTES, 256, 256, conv1d_glds_persistent_kernel<true, 0>),
+    MV_CONV_ROW(CK_PERSIST_1X1_SUM, 512, CVP_LDS_BYTES, 256, 256, conv1d_glds_persistent_kernel<true, 1>),
+    MV_CONV_ROW(CK_PERSIST_1X1_SUM_SQ, 512, CVP_LDS_BYTES, 256, 256, conv1d_glds_persistent_kernel<true, 2>),
+    MV_CONV_ROW(CK_PERSIST_TAPS, 512, CVP_LDS_BYTES, 256, 256, conv1d_glds_persistent_kernel<false, 0>),
+    MV_CONV_ROW(CK_RING, 512, CVR_LDS_BYTES, 256, 256, conv1d_ring_persistent_kernel),
+    MV_CONV_ROW(CK_RING_GROUPED, 512, CVR_LDS_BYTES, 256, 256, conv1d_ring_grouped_kernel),
+    MV_CONV_ROW(CK_MFMA_F32, CV_THREADS, CV_LDS_BYTES, CV_TN, CV_TC, conv1d_mfma_kernel<float, false, false>),
+    MV_CONV_ROW(CK_MFMA_X2, CV_THREADS, CV_LDS_BYTES, CV_TN, CV_TC, conv1d_mfma_kernel<half_t, true, false>),
+    MV_CONV_ROW(CK_MFMA_IN_AFFINE, CV_THREADS, CV_LDS_BYTES, CV_TN, CV_TC, conv1d_mfma_kernel<half_t, false, true>),
+    MV_CONV_ROW(CK_IN_STATS, CV_THREADS, CV_IN_STATS_TN * CV_BK * 2, CV_IN_STATS_TN, CV_BK, conv1d_in_stats_kernel),
+};
+#undef MV_GLDS_ROW
+#undef MV_CONV_ROW
+constexpr bool conv_kernels_in_enum_order(int i = 0) { return i == CK_COUNT || (CONV_KERNELS[i].id == i && conv_kernels_in_enum_order(i + 1)); }
+static_assert(conv_kernels_in_enum_order(), "CONV_KERNELS has one row per ConvKernel, in the enum's order");
+
 // Streaming ("sc1 nt") output stores for the persistent kernels were measured and dropped: all workgroups reach their epilogues together, so a
 // layer's output leaves as bursts of 32 MiB (in isolation the stores cost 27 us of a 187 us K = 1024 layer); with the streaming bits a
 // K = 1024 layer alone runs 187 -> 173 us, but the layers that consume the output then miss in L2 / MALL: end to end 68.2 k -> 65.7 k
 // utterances/s (r02d), and per role with the ring kernel 76.1 k -> 74.0-75.4 k (r05s).
-static int cu_count() {
-    return device_cu_count();   // (cached per device)
-}
 
 // Resident workgroups of the persistent kernel: one per CU (a multiple of 8 keeps  id mod 8 == XCD  across the walk).
 // MvConv1dDesc.persist_blocks_hint overrides it (tests walk several tiles per workgroup on small problems; never the bits of a result).
-static int persistent_blocks(const MvConv1dDesc& d) {
-    const int v = d.persist_blocks_hint > 0 ? d.persist_blocks_hint : cu_count();
-    return (int)round_up(v, 8);
+static int persistent_blocks(const MvConv1dDesc& d, int cus) { return (int)round_up(d.persist_blocks_hint > 0 ? d.persist_blocks_hint : cus, 8); }
+
+// A native grouped layer (conv1d_grouped_native) runs the dense machinery on ONE group's K (d.cin = cin / g) with per-group weights; the tiles
+// find their group's K slice of x through ConvArgs.grp_cout / grp_cin.  Only the kernels that take that offset may run it: the ring kernel
+// (grp_cout % 256 == 0), its tail and the one-shot glds kernels -- the direct fp16 path without fused statistics.
+static MvConv1dDesc one_group(const MvConv1dDesc& d_in, int groups) {
+    MvConv1dDesc d = d_in;
+    if (groups > 1) d.cin = d_in.cin / groups;
+    return d;
 }
 
-int conv1d_launch(const MvConv1dDesc& d_in, hipStream_t stream, int groups) {
+// Every check of the arguments as such; the checks that depend on the chosen kernel are conv1d_plan's.
+static int conv1d_check(const MvConv1dDesc& d_in, int groups) {
     MV_REQUIRE(groups >= 1, "conv1d: groups must be positive");
-    // A native grouped layer (conv1d_grouped_native) runs the dense machinery on ONE group's K (d.cin = cin / g) with per-group weights; the tiles
-    // find their group's K slice of x through ConvArgs.grp_cout / grp_cin.  Only the kernels that take that offset may run it: the ring kernel
-    // (grp_cout % 256 == 0), its tail and the one-shot glds kernels -- the direct fp16 path without fused statistics.
-    MvConv1dDesc d = d_in;
-    int grp_cout = 0, grp_cin = 0;
     if (groups > 1) {
         MV_REQUIRE(conv1d_grouped_native(d_in.cout, d_in.cin, d_in.k, groups),
                    "conv1d: this grouped layer has no native form (1x1, cin / groups a multiple of 64, cout / groups a multiple of 128); "
@@ -1764,10 +1815,8 @@ int conv1d_launch(const MvConv1dDesc& d_in, hipStream_t stream, int groups) {
                        d_in.stat_sq == nullptr && d_in.in_stat_sum == nullptr && d_in.in_stat_sq == nullptr,
                    "conv1d: a grouped layer takes fp16 x without a second input, input affine or fused statistics");
         MV_REQUIRE(d_in.ldx >= d_in.cin, "conv1d: a grouped layer needs ldx >= cin (every group's slice of x)");
-        grp_cout = d_in.cout / groups;
-        grp_cin = d_in.cin / groups;
-        d.cin = grp_cin;
     }
+    const MvConv1dDesc d = one_group(d_in, groups);
     MV_REQUIRE(d.x != nullptr && d.w_packed != nullptr && d.y != nullptr, "conv1d: null tensor");
     MV_REQUIRE(d.B > 0 && d.T_in > 0 && d.T_out > 0 && d.cin > 0 && d.cout > 0 && d.k > 0, "conv1d: bad geometry");
     MV_REQUIRE(d.dilation >= 1 && d.stride >= 1 && d.pad >= 0, "conv1d: bad dilation/stride/pad");
@@ -1802,7 +1851,173 @@ int conv1d_launch(const MvConv1dDesc& d_in, hipStream_t stream, int groups) {
                        (reinterpret_cast<uintptr_t>(d.sum_dst) & 7) == 0,
                    "conv1d: second output alignment");
     MV_REQUIRE((int64_t)d.B * d.T_out < ((int64_t)1 << 31) - CV_TN, "conv1d: too many rows for 32-bit indexing");
+    MV_REQUIRE((reinterpret_cast<uintptr_t>(d.clock_probe) & 7) == 0, "conv1d: clock_probe must be 8-byte aligned");
+    MV_REQUIRE((d.in_stat_sum == nullptr) == (d.in_stat_sq == nullptr), "conv1d: in_stat_sum / in_stat_sq go together");
+    if (d.stat_sq != nullptr) MV_REQUIRE(d.stat_sum != nullptr, "conv1d: stat_sq needs stat_sum");
+    MV_REQUIRE(d.tile == 0 || d.tile == 64 || d.tile == 128 || d.tile == 160 || d.tile == 256, "conv1d: tile must be 0 (auto), 64, 128, 160 or 256");
+    return MV_OK;
+}
 
+// What conv1d_launch launches for a checked descriptor on a chip of `cus` compute units.
+struct ConvPlan {
+    ConvKernel kernel = CK_GLDS_128, tail_kernel = CK_GLDS_64;
+    int n_tiles = 0, co_tiles = 0;         // the kernel's tiles over rows and output channels
+    int grid = 0;                          // workgroups: one per tile, or the resident ones of a persistent kernel
+    int per_utt = 0, tiles_per_utt = 1;    // ConvArgs: tiles that never straddle utterances (the fused input statistics)
+    // the input statistics from a launch of their own (CK_IN_STATS) in front of a conv planned without them
+    bool in_stats_first = false;
+    int in_stats_tiles_per_utt = 0, in_stats_grid_x = 0, in_stats_grid_y = 0;
+    // the ring walk's last partial round as sub-tiles on tail_kernel (tail_nv == 0: none)
+    int tail_vb0 = 0, tail_nv = 0, tail_split = 0;
+    double tail_work = 0.0;
+    int prof_class = MV_PROF_CONV1D;
+    double work = 0.0;                     // of `kernel`'s launch (the tail's is tail_work)
+};
+
+// The choice of kernel and tile.  Every tile family accumulates in one order, so a different choice gives the same bits at another speed.
+// `d` is one group's view of the layer (one_group).  Pure: no HIP call, no state; pointers are looked at for their alignment only.
+static int conv1d_plan(const MvConv1dDesc& d, int groups, int cus, int blocks, ConvPlan* plan) {
+    ConvPlan p;
+    const int grp_cout = groups > 1 ? d.cout / groups : 0;
+    const int n_rows = d.B * d.T_out, cin_pad = conv1d_cin_pad(d.cin);
+    const int stats = d.stat_sum == nullptr ? 0 : (d.stat_sq == nullptr ? 1 : 2);
+    const bool f16 = d.x_dtype == MV_DT_F16, has_x2 = d.x2 != nullptr, in_aff = d.in_scale != nullptr;
+    // the direct path (global -> LDS without a pass through registers): plain fp16 x
+    const bool direct = f16 && !has_x2 && !in_aff;
+
+    // ---- input statistics: from their own launch for a small batch (then the conv is planned without them), else fused into the 160-row tile
+    if (d.in_stat_sum != nullptr && direct && d.k == 1 && d.stride == 1 && d.pad == 0 && d.T_in == d.T_out && d.cout <= CV_TC && d.tile == 0 && d.cin % 8 == 0 &&
+        (reinterpret_cast<uintptr_t>(d.in_stat_sum) & 15) == 0 && (reinterpret_cast<uintptr_t>(d.in_stat_sq) & 15) == 0 &&
+        (int64_t)d.B * ceil_div(d.T_out, CV_IN_STATS_TN) * 2 <= (int64_t)cus && d.B <= 16384) {
+        // small batch: the statistics from their own launch (bit-identical partial rows), the conv on small tiles
+        p.in_stats_first = true;
+        p.in_stats_tiles_per_utt = (int)ceil_div(d.T_out, CV_IN_STATS_TN);
+        p.in_stats_grid_x = d.B * p.in_stats_tiles_per_utt;
+        p.in_stats_grid_y = cin_pad / CV_BK;
+    }
+    const bool in_stats = d.in_stat_sum != nullptr && !p.in_stats_first;
+
+    // ---- 256 x 256 tiles for wide layers with enough work to fill the chip (one workgroup per CU)
+    const bool big_ok = f16 && !has_x2 && !in_aff && d.cout % 256 == 0 && grp_cout % 256 == 0;
+    if (d.tile == 256) MV_REQUIRE(big_ok, "conv1d: 256-wide tiles need the plain fp16 path and cout % 256 == 0");
+    // (auto: from 5/8 of a round of 256 x 256 tiles on -- 48 utterances of 3 s through a 1024-channel layer are 224 tiles = 39.5 us in one round, against 57-74 us
+    //  on 128-row tiles and 60 us on 64 x 64 ones: profiles/r12j_conv_tiles_by_batch.log)
+    const bool big = !in_stats && big_ok && d.tile != 128 && d.tile != 64 && d.tile != 160 &&
+                     (d.tile == 256 || (int64_t)ceil_div(n_rows, 256) * (d.cout / 256) * 8 >= (int64_t)cus * 5);
+    // ... on the persistent kernels: fp16 output, plain bias / ReLU / affine epilogue
+    const bool plain = big && d.y_dtype == MV_DT_F16 && d.sum_dst == nullptr && d.row_bias == nullptr && d.gate == nullptr &&
+                       d.ldy % 8 == 0 && (reinterpret_cast<uintptr_t>(d.y) & 15) == 0 &&
+                       (d.pre_act == MV_ACT_NONE || d.pre_act == MV_ACT_RELU) &&
+                       (d.post_act == MV_ACT_NONE || d.post_act == MV_ACT_RELU) &&
+                       (int64_t)d.k * cin_pad >= 2 * CV_BK;  // at least two K stages per tile
+    const bool simple = d.k == 1 && d.cin % CV_BK == 0;
+    // dense 1x1 rows (input row == output row) with 32-bit byte offsets into both tensors: the ring kernel's loader
+    const bool dense_rows = simple && d.stride == 1 && d.pad == 0 && d.T_in == d.T_out &&
+                            (int64_t)n_rows * d.ldx * 2 < ((int64_t)1 << 32) && (int64_t)d.cout * cin_pad * 2 < ((int64_t)1 << 32);
+    // (a post-activation stays with the double-buffer kernel: the ring kernel's epilogue leaves the fp16 saturation to the hardware and has no v_med3 to
+    //  fold a lower bound into -- no layer of the models has one behind its BatchNorm)
+    const bool ring = plain && stats == 0 && dense_rows && d.post_act == MV_ACT_NONE;
+    // grouped: the ring kernel's layers only -- a grouped layer outside them (a post-activation, say) runs on the one-shot
+    // glds kernels, which take the group offset as well; conv1d_glds_persistent_kernel does not
+    const bool persist = ring || (plain && grp_cout == 0);
+
+    // ---- 128 x 160 tile of the direct path: two workgroups per CU = 2 * CUs slots; taken when it saves a whole round of
+    // workgroups (B*T = 76 288 rows x 128 channels: 477 tiles in one round instead of 596 tiles in two)
+    bool wide = false;
+    if (direct && !big) {
+        if (d.tile == 160 || in_stats) {
+            wide = true;
+        } else if (d.tile == 0) {
+            const int64_t slots = 2 * (int64_t)cus, cot = ceil_div(d.cout, CV_TC);
+            const int64_t cost128 = ceil_div(ceil_div(n_rows, 128) * cot, slots) * 128;
+            const int64_t cost160 = ceil_div(ceil_div(n_rows, 160) * cot, slots) * 160;
+            wide = cost160 < cost128;
+        }
+    }
+    if (d.tile == 160) MV_REQUIRE(direct && !big, "conv1d: the 160-row tile belongs to the plain fp16 path");
+    // ---- Small problems (one utterance, a handful: predict() / small predict_batch calls): 128 x 128 tiles leave most of the chip idle -- one 3 s
+    // utterance through a 1024 -> 1024 layer is 3 x 8 = 24 workgroups walking 16 serial K stages each.  64 x 64 tiles give four times the
+    // workgroups (each K stage is a quarter of the bytes: shorter round trips), still one launch.
+    const bool small = direct && !big && !wide && d.cout >= 64 &&
+                       (d.tile == 64 || (d.tile == 0 && ceil_div(n_rows, CV_TN) * ceil_div(d.cout, CV_TC) * 2 <= (int64_t)cus));
+    if (stats)
+        MV_REQUIRE(persist && d.k == 1 && d.cin % CV_BK == 0 && d.T_out >= 64,
+                   "conv1d: fused time statistics need the persistent 1x1 kernel (fp16 in/out, cout % 256 == 0, cin % 64 == 0, "
+                   "plain bias / ReLU / affine epilogue, T_out >= 64)");
+    if (in_stats) {
+        MV_REQUIRE(direct && wide && d.k == 1 && d.stride == 1 && d.pad == 0 && d.T_in == d.T_out && d.cout <= CV_TC && d.tile != 128 &&
+                       d.tile != 256 && (reinterpret_cast<uintptr_t>(d.in_stat_sum) & 15) == 0 && (reinterpret_cast<uintptr_t>(d.in_stat_sq) & 15) == 0,
+                   "conv1d: fused input statistics need the direct fp16 1x1 path with the 160-row tile (stride 1, no padding, cout <= 128)");
+        p.per_utt = 1;
+        p.tiles_per_utt = (int)ceil_div(d.T_out, CV_IN_STATS_TN);
+    }
+
+    // ---- the kernel; its table row carries the tile
+    if (ring) {
+        p.kernel = grp_cout > 0 ? CK_RING_GROUPED : CK_RING;
+    } else if (persist) {
+        p.kernel = stats == 2 ? CK_PERSIST_1X1_SUM_SQ : (stats == 1 ? CK_PERSIST_1X1_SUM : (simple ? CK_PERSIST_1X1 : CK_PERSIST_TAPS));
+    } else if (big) {
+        p.kernel = CK_GLDS_256;
+    } else if (wide) {
+        p.kernel = in_stats ? CK_GLDS_160_IN_STATS : CK_GLDS_160;
+    } else if (small) {
+        p.kernel = CK_GLDS_64;
+    } else if (direct) {
+        p.kernel = CK_GLDS_128;
+    } else if (f16 && has_x2 && !in_aff) {
+        p.kernel = CK_MFMA_X2;
+    } else if (f16 && !has_x2 && in_aff) {
+        p.kernel = CK_MFMA_IN_AFFINE;
+    } else if (!f16 && !has_x2 && !in_aff) {
+        p.kernel = CK_MFMA_F32;
+    } else {
+        return fail(MV_ERR_UNSUPPORTED, "conv1d: this combination of input dtype / second input / pre-activation is not built");
+    }
+    const ConvKernelRow& row = CONV_KERNELS[p.kernel];
+    p.n_tiles = p.per_utt ? d.B * p.tiles_per_utt : (int)ceil_div(n_rows, row.tile_rows);
+    p.co_tiles = (int)ceil_div(d.cout, row.tile_ch);
+    const int64_t tiles = (int64_t)p.n_tiles * p.co_tiles;
+    p.grid = !persist ? (int)tiles : (int)(tiles < blocks ? round_up(tiles, 8) : blocks);   // blocks: the persistent kernels' resident workgroups
+
+    // ---- The ring walk's tail.  A launch lasts as many tile times as its longest walk: 3600 tiles of an MFA layer (256 utterances of 300 frames x 3072
+    // channels) on 256 workgroups are 14.06 rounds, so 15 -- the last one with 16 workgroups at work.  (The headline batch has 298 frames: 3576 tiles =
+    // 13.97 rounds, nothing to split -- since the tile ids are dense; with the holes of the walk before round 6 it was 15 rounds as well.)  Splitting K over workgroups (stream-K) would fill it, but sums a tile
+    // in another order, and WHICH tiles are split follows the batch: a row's bits would depend on its neighbours.  Splitting a tile's ROWS and CHANNELS
+    // keeps every output element's sum as it is (test_gpu_embedding_bits_do_not_depend_on_the_batch_size holds the 64 / 128 / 256 tiles to one
+    // accumulation order): when the last partial round's tiles, cut into sixteen 64 x 64 or four 128 x 128 sub-tiles, still fit one round of the chip,
+    // the ring kernel walks the whole rounds only and the sub-tiles run at once on the small-tile kernels (four-stage rings).
+    // Measured (r15ae / r15ag, per-launch events, MFA layer of the headline batch): the last round of the unsplit launch costs 50-55 us, not a tile time
+    // of 84 -- its workgroups have the memory system to themselves; 192 quarters (48 tiles: the walk with holes of r15ae) take 44 us on eight waves of
+    // 32 channels x 64 rows (60 on four of 64 x 64: one wave per SIMD cannot overlap its fragment reads with its MFMAs; two instead of three stages in
+    // flight change nothing: the 128 x 128 tile is bound by LDS bandwidth, 96 KiB of fragment reads + 32 KiB of transfers per K stage = ~0.9 us where
+    // the ring kernel's stage of four times the FLOPs takes 1.7).  So a tail that needs more than one round of sub-tiles does not pay (the K = 1024
+    // layers: 176 tiles in the last round), and K stages below eight are not worth a second launch.
+    if (ring) {
+        const int total_ids = p.n_tiles * p.co_tiles;
+        const int whole = total_ids / blocks * blocks;
+        const int left = total_ids - whole;
+        if (whole > 0 && left > 0 && 4 * left <= blocks && cin_pad / CV_BK >= 8) {
+            p.tail_vb0 = whole;
+            p.tail_nv = left;
+            p.tail_split = 16 * left <= blocks ? 4 : 2;
+            p.tail_kernel = p.tail_split == 4 ? CK_GLDS_64 : CK_GLDS_128_TAIL;
+            for (int v = whole; v < total_ids; ++v) {
+                int nt = 0, ct = 0;
+                tile_of_index_geom(p.n_tiles, p.co_tiles, v, nt, ct);
+                const int rows = n_rows - nt * 256 < 256 ? n_rows - nt * 256 : 256;
+                p.tail_work += 2.0 * rows * 256.0 * (double)d.cin;
+            }
+        }
+    }
+    p.prof_class = ring ? MV_PROF_CONV1D_RING : MV_PROF_CONV1D;
+    p.work = 2.0 * n_rows * (double)d.cin * d.cout * d.k - p.tail_work;
+    *plan = p;
+    return MV_OK;
+}
+
+// the kernels' argument block: the descriptor field by field, the group geometry and the plan's tiling
+static ConvArgs conv_args(const MvConv1dDesc& d, int groups, const ConvPlan& p) {
     ConvArgs a;
     a.x = d.x;
     a.x2 = d.x2;
@@ -1840,222 +2055,70 @@ int conv1d_launch(const MvConv1dDesc& d_in, hipStream_t stream, int groups) {
     a.gate_seg_len = d.gate_seg_len > 0 ? d.gate_seg_len : 1;
     a.gate_nseg = (int)ceil_div(d.T_out, a.gate_seg_len);
     a.n_rows = d.B * d.T_out;
+    a.n_tiles = p.n_tiles;
+    a.co_tiles = p.co_tiles;
     a.stat_sum = d.stat_sum;
     a.stat_sq = d.stat_sq;
-    a.per_utt = 0;
-    a.tiles_per_utt = 1;
+    a.per_utt = p.per_utt;
+    a.tiles_per_utt = p.tiles_per_utt;
     a.in_sum = d.in_stat_sum;
     a.in_sq = d.in_stat_sq;
     a.clock_probe = reinterpret_cast<unsigned long long*>(d.clock_probe);
-    a.grp_cout = grp_cout;
-    a.grp_cin = grp_cin;
-    MV_REQUIRE((reinterpret_cast<uintptr_t>(d.clock_probe) & 7) == 0, "conv1d: clock_probe must be 8-byte aligned");
-    const bool in_stats = d.in_stat_sum != nullptr;
-    MV_REQUIRE((d.in_stat_sum == nullptr) == (d.in_stat_sq == nullptr), "conv1d: in_stat_sum / in_stat_sq go together");
-    const int stats = d.stat_sum == nullptr ? 0 : (d.stat_sq == nullptr ? 1 : 2);
-    if (d.stat_sq != nullptr) MV_REQUIRE(d.stat_sum != nullptr, "conv1d: stat_sq needs stat_sum");
-    const bool f16 = d.x_dtype == MV_DT_F16;
-    const bool has_x2 = d.x2 != nullptr, in_aff = d.in_scale != nullptr;
-    // 256 x 256 tiles for wide layers with enough work to fill the chip (one workgroup per CU)
-    MV_REQUIRE(d.tile == 0 || d.tile == 64 || d.tile == 128 || d.tile == 160 || d.tile == 256, "conv1d: tile must be 0 (auto), 64, 128, 160 or 256");
-    const bool big_ok = f16 && !has_x2 && !in_aff && d.cout % 256 == 0 && grp_cout % 256 == 0;
-    if (d.tile == 256) MV_REQUIRE(big_ok, "conv1d: 256-wide tiles need the plain fp16 path and cout % 256 == 0");
-    // (auto: from 5/8 of a round of 256 x 256 tiles on -- 48 utterances of 3 s through a 1024-channel layer are 224 tiles = 39.5 us in one round, against 57-74 us
-    //  on 128-row tiles and 60 us on 64 x 64 ones: profiles/r12j_conv_tiles_by_batch.log)
-    const bool big = !in_stats && big_ok && d.tile != 128 && d.tile != 64 && d.tile != 160 &&
-                     (d.tile == 256 || (int64_t)ceil_div(a.n_rows, 256) * (d.cout / 256) * 8 >= (int64_t)cu_count() * 5);
-    // persistent form of the 256^2 kernel: fp16 output, plain bias / ReLU / affine epilogue
-    const bool persist = big && d.y_dtype == MV_DT_F16 && d.sum_dst == nullptr && d.row_bias == nullptr && d.gate == nullptr &&
-                         d.ldy % 8 == 0 && (reinterpret_cast<uintptr_t>(d.y) & 15) == 0 &&
-                         (d.pre_act == MV_ACT_NONE || d.pre_act == MV_ACT_RELU) &&
-                         (d.post_act == MV_ACT_NONE || d.post_act == MV_ACT_RELU) &&
-                         (int64_t)d.k * conv1d_cin_pad(d.cin) >= 2 * CV_BK &&  // at least two K stages per tile
-                         // grouped: the ring kernel's layers only -- a grouped layer outside them (a post-activation, say) runs on the one-shot
-                         // glds kernels, which take the group offset as well; conv1d_glds_persistent_kernel does not
-                         (grp_cout == 0 || (d.stride == 1 && d.pad == 0 && d.T_in == d.T_out && d.post_act == MV_ACT_NONE &&
-                                            (int64_t)a.n_rows * d.ldx * 2 < ((int64_t)1 << 32)));
-    // 128 x 160 tile of the direct path: two workgroups per CU = 2 * CUs slots; taken when it saves a whole round of
-    // workgroups (B*T = 76 288 rows x 128 channels: 477 tiles in one round instead of 596 tiles in two)
-    const bool direct = f16 && !has_x2 && !in_aff;
-    bool wide = false;
-    if (direct && !big) {
-        if (d.tile == 160 || in_stats) {
-            wide = true;
-        } else if (d.tile == 0) {
-            const int64_t slots = 2 * (int64_t)cu_count(), cot = ceil_div(d.cout, CV_TC);
-            const int64_t cost128 = ceil_div(ceil_div(a.n_rows, 128) * cot, slots) * 128;
-            const int64_t cost160 = ceil_div(ceil_div(a.n_rows, 160) * cot, slots) * 160;
-            wide = cost160 < cost128;
-        }
-    }
-    if (d.tile == 160) MV_REQUIRE(direct && !big, "conv1d: the 160-row tile belongs to the plain fp16 path");
-    // Small problems (one utterance, a handful: predict() / small predict_batch calls): 128 x 128 tiles leave most of the chip idle -- one 3 s
-    // utterance through a 1024 -> 1024 layer is 3 x 8 = 24 workgroups walking 16 serial K stages each.  64 x 64 tiles give four times the
-    // workgroups (each K stage is a quarter of the bytes: shorter round trips), still one launch.
-    const bool small = direct && !big && !wide && d.cout >= 64 &&
-                       (d.tile == 64 || (d.tile == 0 && ceil_div(a.n_rows, CV_TN) * ceil_div(d.cout, CV_TC) * 2 <= (int64_t)cu_count()));
-    if (stats)
-        MV_REQUIRE(persist && d.k == 1 && d.cin % CV_BK == 0 && d.T_out >= 64,
-                   "conv1d: fused time statistics need the persistent 1x1 kernel (fp16 in/out, cout % 256 == 0, cin % 64 == 0, "
-                   "plain bias / ReLU / affine epilogue, T_out >= 64)");
-    if (in_stats && direct && d.k == 1 && d.stride == 1 && d.pad == 0 && d.T_in == d.T_out && d.cout <= CV_TC && d.tile == 0 && d.cin % 8 == 0 &&
-        (reinterpret_cast<uintptr_t>(d.in_stat_sum) & 15) == 0 && (reinterpret_cast<uintptr_t>(d.in_stat_sq) & 15) == 0 &&
-        (int64_t)d.B * ceil_div(d.T_out, CV_IN_STATS_TN) * 2 <= (int64_t)cu_count() && d.B <= 16384) {
-        // small batch: the statistics from their own launch (bit-identical partial rows), the conv on small tiles
-        a.per_utt = 1;
-        a.tiles_per_utt = (int)ceil_div(d.T_out, CV_IN_STATS_TN);
-        static DeviceOnce once;
-        int slot;
-        if (device_once_pending(once, &slot)) {
-            if (MV_SET_MAX_SMEM(conv1d_in_stats_kernel, CV_IN_STATS_TN * CV_BK * 2) != hipSuccess) return fail(MV_ERR_HIP, "conv1d: cannot reserve dynamic LDS");
-            device_once_done(once, slot);
-        }
-        MV_LAUNCH(conv1d_in_stats_kernel, ((unsigned)(d.B * a.tiles_per_utt), (unsigned)(a.cin_pad / CV_BK), 1), (CV_THREADS, 1, 1), CV_IN_STATS_TN * CV_BK * 2, stream, a);
-        int rc = check_launch("conv1d_in_stats_kernel");
-        if (rc != MV_OK) return rc;
-        MvConv1dDesc d2 = d;
-        d2.in_stat_sum = nullptr;
-        d2.in_stat_sq = nullptr;
-        return conv1d_launch(d2, stream, 1);
-    }
-    if (in_stats) {
-        MV_REQUIRE(direct && wide && d.k == 1 && d.stride == 1 && d.pad == 0 && d.T_in == d.T_out && d.cout <= CV_TC && d.tile != 128 &&
-                       d.tile != 256 && (reinterpret_cast<uintptr_t>(d.in_stat_sum) & 15) == 0 && (reinterpret_cast<uintptr_t>(d.in_stat_sq) & 15) == 0,
-                   "conv1d: fused input statistics need the direct fp16 1x1 path with the 160-row tile (stride 1, no padding, cout <= 128)");
-        a.per_utt = 1;
-        a.tiles_per_utt = (int)ceil_div(d.T_out, CV_IN_STATS_TN);
-    }
-    const int tn = big ? 256 : (wide ? 160 : (small ? 64 : CV_TN)), tc = big ? 256 : (small ? 64 : CV_TC);
-    a.n_tiles = a.per_utt ? d.B * a.tiles_per_utt : (int)ceil_div(a.n_rows, tn);
-    a.co_tiles = (int)ceil_div(d.cout, tc);
-    const int grid = a.n_tiles * a.co_tiles;
+    a.ring_vb_end = p.tail_vb0;
+    a.grp_cout = groups > 1 ? d.cout / groups : 0;
+    a.grp_cin = groups > 1 ? d.cin : 0;
+    return a;
+}
+
+static void launch_conv_kernel(ConvKernel k, int grid_x, int grid_y, const ConvArgs& a, hipStream_t stream) {
+    const ConvKernelRow& row = CONV_KERNELS[k];
+    MV_LAUNCH(row.fn, (grid_x, grid_y, 1), (row.threads, 1, 1), row.lds_bytes, stream, a);
+}
+
+int conv1d_launch(const MvConv1dDesc& d_in, hipStream_t stream, int groups) {
+    int rc = conv1d_check(d_in, groups);
+    if (rc != MV_OK) return rc;
+    const MvConv1dDesc d = one_group(d_in, groups);
+    const int cus = device_cu_count();   // (cached per device)
+    ConvPlan p;
+    if ((rc = conv1d_plan(d, groups, cus, persistent_blocks(d, cus), &p))) return rc;
     static DeviceOnce smem_set;   // (per device: the attribute belongs to the current device's code object)
     int smem_set_slot;
     if (device_once_pending(smem_set, &smem_set_slot)) {
-        if (MV_SET_MAX_SMEM((conv1d_glds_kernel<2, 2, 4, 4>), CV_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_kernel<2, 2, 2, 2, false, CV_SMALL_NS>), CV_LDS_BYTES_SMALL) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_kernel<4, 2, 2, 4, false, CV_TAIL_NS>), CV_LDS_BYTES_TAIL) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_kernel<2, 2, 4, 5>), CV_LDS_BYTES_WIDE) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_kernel<2, 2, 4, 5, true>), CV_LDS_BYTES_WIDE + CV_IN_STATS_BUF_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_kernel<2, 4, 8, 4>), CV_LDS_BYTES_BIG) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_persistent_kernel<true, 0>), CVP_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_persistent_kernel<true, 1>), CVP_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_persistent_kernel<true, 2>), CVP_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_glds_persistent_kernel<false, 0>), CVP_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM(conv1d_ring_persistent_kernel, CVR_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM(conv1d_ring_grouped_kernel, CVR_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_mfma_kernel<float, false, false>), CV_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_mfma_kernel<half_t, true, false>), CV_LDS_BYTES) != hipSuccess ||
-            MV_SET_MAX_SMEM((conv1d_mfma_kernel<half_t, false, true>), CV_LDS_BYTES) != hipSuccess)
-            return fail(MV_ERR_HIP, "conv1d: cannot reserve dynamic LDS");
+        for (const ConvKernelRow& row : CONV_KERNELS)
+            if (MV_SET_MAX_SMEM(row.fn, row.lds_bytes) != hipSuccess) return fail(MV_ERR_HIP, "conv1d: cannot reserve dynamic LDS");
         device_once_done(smem_set, smem_set_slot);
     }
-    const bool simple = d.k == 1 && d.cin % CV_BK == 0;
-    // dense 1x1 rows (input row == output row) with 32-bit byte offsets into both tensors: the ring kernel's loader
-    const bool dense_rows = simple && d.stride == 1 && d.pad == 0 && d.T_in == d.T_out &&
-                            (int64_t)a.n_rows * d.ldx * 2 < ((int64_t)1 << 32) && (int64_t)d.cout * a.cin_pad * 2 < ((int64_t)1 << 32);
-    // (a post-activation stays with the double-buffer kernel: the ring kernel's epilogue leaves the fp16 saturation to the hardware and has no v_med3 to
-    //  fold a lower bound into -- no layer of the models has one behind its BatchNorm)
-    const bool ring = persist && stats == 0 && dense_rows && d.post_act == MV_ACT_NONE;
-    if (grp_cout > 0) MV_REQUIRE(ring || !persist, "conv1d: internal: a grouped layer reached a persistent kernel other than the ring kernel");
-    // The ring walk's tail.  A launch lasts as many tile times as its longest walk: 3600 tiles of an MFA layer (256 utterances of 300 frames x 3072
-    // channels) on 256 workgroups are 14.06 rounds, so 15 -- the last one with 16 workgroups at work.  (The headline batch has 298 frames: 3576 tiles =
-    // 13.97 rounds, nothing to split -- since the tile ids are dense; with the holes of the walk before round 6 it was 15 rounds as well.)  Splitting K over workgroups (stream-K) would fill it, but sums a tile
-    // in another order, and WHICH tiles are split follows the batch: a row's bits would depend on its neighbours.  Splitting a tile's ROWS and CHANNELS
-    // keeps every output element's sum as it is (test_gpu_embedding_bits_do_not_depend_on_the_batch_size holds the 64 / 128 / 256 tiles to one
-    // accumulation order): when the last partial round's tiles, cut into sixteen 64 x 64 or four 128 x 128 sub-tiles, still fit one round of the chip,
-    // the ring kernel walks the whole rounds only and the sub-tiles run at once on the small-tile kernels (four-stage rings).
-    // Measured (r15ae / r15ag, per-launch events, MFA layer of the headline batch): the last round of the unsplit launch costs 50-55 us, not a tile time
-    // of 84 -- its workgroups have the memory system to themselves; 192 quarters (48 tiles: the walk with holes of r15ae) take 44 us on eight waves of
-    // 32 channels x 64 rows (60 on four of 64 x 64: one wave per SIMD cannot overlap its fragment reads with its MFMAs; two instead of three stages in
-    // flight change nothing: the 128 x 128 tile is bound by LDS bandwidth, 96 KiB of fragment reads + 32 KiB of transfers per K stage = ~0.9 us where
-    // the ring kernel's stage of four times the FLOPs takes 1.7).  So a tail that needs more than one round of sub-tiles does not pay (the K = 1024
-    // layers: 176 tiles in the last round), and K stages below eight are not worth a second launch.
-    int tail_vb0 = 0, tail_nv = 0, tail_split = 0;
-    double tail_work = 0.0;
-    if (ring) {
-        const int blocks = persistent_blocks(d);
-        const int total_ids = a.n_tiles * a.co_tiles;
-        const int whole = total_ids / blocks * blocks;
-        const int left = total_ids - whole;
-        if (whole > 0 && left > 0 && 4 * left <= blocks && a.cin_pad / CV_BK >= 8) {
-            tail_vb0 = whole;
-            tail_nv = left;
-            tail_split = 16 * left <= blocks ? 4 : 2;
-            for (int v = whole; v < total_ids; ++v) {
-                int nt = 0, ct = 0;
-                tile_of_index_geom(a.n_tiles, a.co_tiles, v, nt, ct);
-                const int rows = a.n_rows - nt * 256 < 256 ? a.n_rows - nt * 256 : 256;
-                tail_work += 2.0 * rows * 256.0 * (double)d.cin;
-            }
-        }
+    ConvArgs a = conv_args(d, groups, p);
+    if (p.in_stats_first) {
+        ConvArgs s = a;
+        s.per_utt = 1;
+        s.tiles_per_utt = p.in_stats_tiles_per_utt;
+        launch_conv_kernel(CK_IN_STATS, p.in_stats_grid_x, p.in_stats_grid_y, s, stream);
+        if ((rc = check_launch(CONV_KERNELS[CK_IN_STATS].name))) return rc;
+        a.in_sum = nullptr;
+        a.in_sq = nullptr;
     }
-    const int prof = prof_begin(ring ? MV_PROF_CONV1D_RING : MV_PROF_CONV1D, 2.0 * a.n_rows * (double)d.cin * d.cout * d.k - tail_work, stream);
-    if (persist) {
-        const int64_t tiles = (int64_t)a.n_tiles * a.co_tiles;
-        const int pgrid = (int)(tiles < persistent_blocks(d) ? round_up(tiles, 8) : persistent_blocks(d));
-        if (ring) {
-            a.ring_vb_end = tail_vb0;
-            if (grp_cout > 0) {
-                MV_LAUNCH(conv1d_ring_grouped_kernel, (pgrid, 1, 1), (512, 1, 1), CVR_LDS_BYTES, stream, a);
-            } else {
-                MV_LAUNCH(conv1d_ring_persistent_kernel, (pgrid, 1, 1), (512, 1, 1), CVR_LDS_BYTES, stream, a);
-            }
-            if (tail_nv > 0) {
-                prof_end(prof, stream);
-                int rc = check_launch("conv1d_ring_persistent_kernel");
-                if (rc != MV_OK) return rc;
-                ConvArgs t = a;
-                t.ring_vb_end = 0;
-                t.clock_probe = nullptr;
-                t.tail_vb0 = tail_vb0;
-                t.tail_nv = tail_nv;
-                t.tail_n_tiles = a.n_tiles;
-                t.tail_co_tiles = a.co_tiles;
-                t.tail_split = tail_split;
-                const int tprof = prof_begin(MV_PROF_CONV1D, tail_work, stream);
-                if (tail_split == 4) {
-                    t.n_tiles = (int)ceil_div(a.n_rows, 64);
-                    t.co_tiles = (int)ceil_div(d.cout, 64);
-                    MV_LAUNCH((conv1d_glds_kernel<2, 2, 2, 2, false, CV_SMALL_NS>), (16 * tail_nv, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES_SMALL, stream, t);
-                } else {
-                    t.n_tiles = (int)ceil_div(a.n_rows, CV_TN);
-                    t.co_tiles = (int)ceil_div(d.cout, CV_TC);
-                    MV_LAUNCH((conv1d_glds_kernel<4, 2, 2, 4, false, CV_TAIL_NS>), (4 * tail_nv, 1, 1), (512, 1, 1), CV_LDS_BYTES_TAIL, stream, t);
-                }
-                prof_end(tprof, stream);
-                return check_launch("conv1d_glds_kernel (ring tail)");
-            }
-        } else if (stats == 2) {
-            MV_LAUNCH((conv1d_glds_persistent_kernel<true, 2>), (pgrid, 1, 1), (512, 1, 1), CVP_LDS_BYTES, stream, a);
-        } else if (stats == 1) {
-            MV_LAUNCH((conv1d_glds_persistent_kernel<true, 1>), (pgrid, 1, 1), (512, 1, 1), CVP_LDS_BYTES, stream, a);
-        } else if (simple) {
-            MV_LAUNCH((conv1d_glds_persistent_kernel<true, 0>), (pgrid, 1, 1), (512, 1, 1), CVP_LDS_BYTES, stream, a);
-        } else {
-            MV_LAUNCH((conv1d_glds_persistent_kernel<false, 0>), (pgrid, 1, 1), (512, 1, 1), CVP_LDS_BYTES, stream, a);
-        }
-    } else if (big) {
-        MV_LAUNCH((conv1d_glds_kernel<2, 4, 8, 4>), (grid, 1, 1), (512, 1, 1), CV_LDS_BYTES_BIG, stream, a);
-    } else if (wide && in_stats) {
-        MV_LAUNCH((conv1d_glds_kernel<2, 2, 4, 5, true>), (grid, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES_WIDE + CV_IN_STATS_BUF_BYTES, stream, a);
-    } else if (wide) {
-        MV_LAUNCH((conv1d_glds_kernel<2, 2, 4, 5>), (grid, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES_WIDE, stream, a);
-    } else if (small) {
-        MV_LAUNCH((conv1d_glds_kernel<2, 2, 2, 2, false, CV_SMALL_NS>), (grid, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES_SMALL, stream, a);
-    } else if (f16 && !has_x2 && !in_aff) {
-        MV_LAUNCH((conv1d_glds_kernel<2, 2, 4, 4>), (grid, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES, stream, a);
-    } else if (f16 && has_x2 && !in_aff) {
-        MV_LAUNCH((conv1d_mfma_kernel<half_t, true, false>), (grid, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES, stream, a);
-    } else if (f16 && !has_x2 && in_aff) {
-        MV_LAUNCH((conv1d_mfma_kernel<half_t, false, true>), (grid, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES, stream, a);
-    } else if (!f16 && !has_x2 && !in_aff) {
-        MV_LAUNCH((conv1d_mfma_kernel<float, false, false>), (grid, 1, 1), (CV_THREADS, 1, 1), CV_LDS_BYTES, stream, a);
-    } else {
-        return fail(MV_ERR_UNSUPPORTED, "conv1d: this combination of input dtype / second input / pre-activation is not built");
-    }
+    const int prof = prof_begin(p.prof_class, p.work, stream);
+    launch_conv_kernel(p.kernel, p.grid, 1, a, stream);
     prof_end(prof, stream);
-    return check_launch("conv1d_mfma_kernel");
+    if ((rc = check_launch(CONV_KERNELS[p.kernel].name)) || p.tail_nv == 0) return rc;
+    // the ring walk's last partial round: sub-tile b / tail_nv of the 256 x 256 tile with virtual id tail_vb0 + b % tail_nv (tile_of_block)
+    const ConvKernelRow& tail = CONV_KERNELS[p.tail_kernel];
+    ConvArgs t = a;
+    t.ring_vb_end = 0;
+    t.clock_probe = nullptr;
+    t.tail_vb0 = p.tail_vb0;
+    t.tail_nv = p.tail_nv;
+    t.tail_n_tiles = a.n_tiles;
+    t.tail_co_tiles = a.co_tiles;
+    t.tail_split = p.tail_split;
+    t.n_tiles = (int)ceil_div(a.n_rows, tail.tile_rows);
+    t.co_tiles = (int)ceil_div(d.cout, tail.tile_ch);
+    const int tprof = prof_begin(MV_PROF_CONV1D, p.tail_work, stream);
+    launch_conv_kernel(p.tail_kernel, p.tail_split * p.tail_split * p.tail_nv, 1, t, stream);
+    prof_end(tprof, stream);
+    return check_launch(tail.name);
 }
 
 }  // namespace mv
@@ -2066,11 +2129,15 @@ int64_t mv_conv1d_packed_elems(int32_t cout, int32_t cin, int32_t k) {
     return (int64_t)mv::conv1d_cout_pad(cout) * k * mv::conv1d_cin_pad(cin);
 }
 
+// workgroups of the two grid-stride weight packers
+static int pack_grid(int32_t cout, int32_t cin, int32_t k) {
+    const int64_t blocks = mv::ceil_div(mv_conv1d_packed_elems(cout, cin, k), 256);
+    return (int)(blocks < 2048 ? blocks : 2048);
+}
+
 int mv_conv1d_pack_weight(const float* w, int32_t cout, int32_t cin, int32_t k, void* packed_f16, mv_stream_t stream) {
     MV_REQUIRE(w != nullptr && packed_f16 != nullptr && cout > 0 && cin > 0 && k > 0, "mv_conv1d_pack_weight: bad argument");
-    const int64_t total = mv_conv1d_packed_elems(cout, cin, k);
-    const int grid = (int)(mv::ceil_div(total, 256) < 2048 ? mv::ceil_div(total, 256) : 2048);
-    MV_LAUNCH(mv::pack_conv_weight_kernel, (grid, 1, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), w, cout, cin, k,
+    MV_LAUNCH(mv::pack_conv_weight_kernel, (pack_grid(cout, cin, k), 1, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), w, cout, cin, k,
               mv::conv1d_cout_pad(cout), mv::conv1d_cin_pad(cin), reinterpret_cast<half_t*>(packed_f16));
     return mv::check_launch("pack_conv_weight_kernel");
 }
@@ -2111,9 +2178,7 @@ int mv_conv1d_pack_weight_grouped(const float* w, int32_t cout, int32_t cin, int
     MV_REQUIRE(w != nullptr && packed_f16 != nullptr && cout > 0 && cin > 0 && k > 0 && groups >= 1, "mv_conv1d_pack_weight_grouped: bad argument");
     MV_REQUIRE(cin % groups == 0 && cout % groups == 0, "mv_conv1d_pack_weight_grouped: cin and cout must be divisible by groups");
     if (groups == 1 || mv::conv1d_grouped_native(cout, cin, k, groups)) return mv_conv1d_pack_weight(w, cout, cin / groups, k, packed_f16, stream);
-    const int64_t total = mv_conv1d_packed_elems(cout, cin, k);
-    const int grid = (int)(mv::ceil_div(total, 256) < 2048 ? mv::ceil_div(total, 256) : 2048);
-    MV_LAUNCH(mv::pack_conv_weight_grouped_kernel, (grid, 1, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), w, cout, cin, k, groups,
+    MV_LAUNCH(mv::pack_conv_weight_grouped_kernel, (pack_grid(cout, cin, k), 1, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), w, cout, cin, k, groups,
               mv::conv1d_cout_pad(cout), mv::conv1d_cin_pad(cin), reinterpret_cast<half_t*>(packed_f16));
     return mv::check_launch("pack_conv_weight_grouped_kernel");
 }

@@ -47,11 +47,10 @@ int fold_bn(const Weights& w, const std::string& prefix, int C, std::vector<floa
 int fold_final_linear(MvModelBase* m, const Weights& w, const std::string& weight_name, const std::string& bias_name,
                       const std::string& bn_in, const std::string& bn_out, int O, int K, float** wf_out, float** bf_out);
 
-int run_conv(const ConvLayer& L, const void* x, int x_dtype, int64_t ldx, const void* x2, int64_t ldx2, void* y, int y_dtype,
-             int64_t ldy, int B, int T_in, int T_out, int dil, int pad, int pad_mode, int pre_act, const float* scale,
-             const float* shift, int post_act, const float* row_bias, bool use_bias, hipStream_t stream,
-             const half_t* add_src = nullptr, int64_t ld_add = 0, half_t* sum_dst = nullptr, int64_t ld_sum = 0,
-             float* stat_sum = nullptr, float* stat_sq = nullptr);
+// A layer's conv descriptor from what every layer has -- its weights, bias and geometry, x [B, T_in, ldx] and y [B, T_out, ldy] -- with the models'
+// defaults: fp16 in / out, stride 1, dilation 1, no padding (reflect mode), no activations.  A call site names what differs (d.pre_act, d.scale, ...)
+// and ends in conv1d_launch(d, stream, L.groups).
+MvConv1dDesc conv_desc(const ConvLayer& L, const void* x, int64_t ldx, void* y, int64_t ldy, int B, int T_in, int T_out);
 
 // bump allocator over the caller-provided workspace (256-byte aligned slices)
 struct Carver {
@@ -100,6 +99,25 @@ struct PoolHead {
     int width() const { return type == MV_POOL_TSP ? 2 * C : C; }
     int hidden_width() const { return type == MV_POOL_SAP ? SAP_A : 0; }   // fp16 [B, T, .] scratch the forward needs
     int forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, float* pooled, hipStream_t stream) const;
+};
+
+// The pooling head of EcapaTdnn and TDNN, whichever pooling_type (MV_POOL_*) names: x [B, T, ldx] fp16 -> pooled fp32 [B, width()]
+struct Pooling {
+    int type = MV_POOL_ASP;
+    AspLayer asp;     // MV_POOL_ASP
+    PoolHead head;    // the other heads
+    int create(MvModelBase* m, const Weights& w, const std::string& prefix, int type_, int C, int A, bool global_ctx) {   // A, global_ctx: the ASP's
+        type = type_;
+        return type == MV_POOL_ASP ? asp.create(m, w, prefix, C, A, global_ctx) : head.create(m, w, prefix, type, C);
+    }
+    int width() const { return type == MV_POOL_ASP ? 2 * asp.C : head.width(); }
+    int hidden_width() const { return type == MV_POOL_ASP ? asp.A : head.hidden_width(); }   // fp16 [B, T, .] scratch the forward needs
+    size_t workspace_floats(int B, int T) const { return type == MV_POOL_ASP ? asp.workspace_floats(B, T) : 0; }
+    int forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, float* fws, float* pooled, hipStream_t st) const {
+        return type == MV_POOL_ASP ? asp.forward(x, ldx, B, T, h, fws, pooled, st) : head.forward(x, ldx, B, T, h, pooled, st);
+    }
+    // EcapaTdnn's norm behind the head: BatchNorm1d wrapped in a module of the reference's behind ASP, a plain one behind the others (ecapa_tdnn.py:229-250)
+    const char* ecapa_bn_name() const { return type == MV_POOL_ASP ? "asp_bn.norm" : "asp_bn"; }
 };
 
 }  // namespace mv

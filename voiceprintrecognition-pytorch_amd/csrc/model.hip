@@ -128,45 +128,32 @@ int MvModelBase::make_bn(const Weights& w, const std::string& prefix, int C, flo
     return MV_OK;
 }
 
-// y = BN(ReLU(conv(x)))  -- TDNNBlock (models/utils.py:138) and TDNN.forward (tdnn.py:57-64)
-int run_conv(const ConvLayer& L, const void* x, int x_dtype, int64_t ldx, const void* x2, int64_t ldx2, void* y, int y_dtype,
-             int64_t ldy, int B, int T_in, int T_out, int dil, int pad, int pad_mode, int pre_act, const float* scale,
-             const float* shift, int post_act, const float* row_bias, bool use_bias, hipStream_t stream,
-             const half_t* add_src, int64_t ld_add, half_t* sum_dst, int64_t ld_sum, float* stat_sum, float* stat_sq) {
-    MvConv1dDesc d;
-    memset(&d, 0, sizeof(d));
-    d.stat_sum = stat_sum;
-    d.stat_sq = stat_sq;
-    d.add_src = add_src;
-    d.sum_dst = sum_dst;
-    d.ld_add = ld_add;
-    d.ld_sum = ld_sum;
+MvConv1dDesc conv_desc(const ConvLayer& L, const void* x, int64_t ldx, void* y, int64_t ldy, int B, int T_in, int T_out) {
+    MvConv1dDesc d = {};
     d.x = x;
-    d.x2 = x2;
-    d.x_dtype = x_dtype;
     d.ldx = ldx;
-    d.ldx2 = ldx2;
-    d.w_packed = L.w;
-    d.bias = use_bias ? L.bias : nullptr;
-    d.row_bias = row_bias;
-    d.pre_act = pre_act;
-    d.scale = scale;
-    d.shift = shift;
-    d.post_act = post_act;
     d.y = y;
-    d.y_dtype = y_dtype;
     d.ldy = ldy;
+    d.x_dtype = d.y_dtype = MV_DT_F16;
+    d.w_packed = L.w;
+    d.bias = L.bias;
     d.B = B;
     d.T_in = T_in;
     d.T_out = T_out;
     d.cin = L.cin;
     d.cout = L.cout;
     d.k = L.k;
-    d.dilation = dil;
-    d.stride = 1;
-    d.pad = pad;
-    d.pad_mode = pad_mode;
-    return conv1d_launch(d, stream, L.groups);
+    d.dilation = d.stride = 1;
+    d.pad_mode = MV_PAD_REFLECT;
+    return d;
+}
+
+// first-layer weight [cout][F][k] with zero input columns F..Fp-1: a zero weight times a finite feature adds an exact zero, so a ragged feature
+// size F computes the bits of Fp = round_up(F, 8) with zero-padded features and weights
+static std::vector<float> pad_input_columns(const std::vector<float>& w, int cout, int F, int Fp, int k) {
+    std::vector<float> wp((size_t)cout * Fp * k, 0.0f);
+    for (int co = 0; co < cout; ++co) memcpy(&wp[(size_t)co * Fp * k], &w[(size_t)co * F * k], (size_t)F * k * sizeof(float));
+    return wp;
 }
 
 // --------------------------------------------------------------------------------------- ASP tail
@@ -221,7 +208,6 @@ int make_attention_projection(MvModelBase* m, const Weights& w, const std::strin
 // [B, 2C] global mean | std, [B, A] context bias, the two partial buffers of the hidden conv's fused input statistics, the K slices of the
 // context-bias layer (linear.hip, split-K form: [2C -> A] over B rows)
 size_t AspLayer::workspace_floats(int B, int T) const {
-    (void)T;
     return (size_t)B * (2 * C + A) + 2 * (size_t)conv_in_stats_elems(B, T, C) + linear_f32_splitk_floats(B, 2 * C, A);
 }
 
@@ -233,7 +219,8 @@ int AspLayer::forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, flo
     float* ctxb = fws + (size_t)B * 2 * C;   // [B, A]
     float* lin_ws = fws + (size_t)B * (2 * C + A) + 2 * (size_t)conv_in_stats_elems(B, T, C);
     const size_t lin_ws_floats = linear_f32_splitk_floats(B, 2 * C, A);
-    const float* gmean = nullptr;
+    MvConv1dDesc d = conv_desc(tdnn, x, ldx, h, A, B, T, T);   // the hidden layer: h = tanh(BN(ReLU(Wx . x + bias)))
+    if (global_ctx) d.bias = nullptr;   // (it is part of the context bias)
     if (global_ctx && !have_gstats && A <= 128 && A % 8 == 0 && ldx % 8 == 0) {
         // x is streamed ONCE for the global statistics and the hidden layer: the 1x1 conv over x collects the time sums of its own x
         // tiles and leaves the pre-activation z = Wx . x in h; the context columns [mean; std] enter as a per-utterance bias that
@@ -241,22 +228,6 @@ int AspLayer::forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, flo
         // statistics pass over x (469 MB at the bench shape).
         float* psum = ctxb + (size_t)B * A;
         float* psq = psum + conv_in_stats_elems(B, T, C);
-        MvConv1dDesc d;
-        memset(&d, 0, sizeof(d));
-        d.x = x;
-        d.x_dtype = MV_DT_F16;
-        d.ldx = ldx;
-        d.w_packed = tdnn.w;
-        d.y = h;
-        d.y_dtype = MV_DT_F16;
-        d.ldy = A;
-        d.B = B;
-        d.T_in = d.T_out = T;
-        d.cin = C;
-        d.cout = A;
-        d.k = 1;
-        d.dilation = d.stride = 1;
-        d.pad_mode = MV_PAD_REFLECT;
         d.in_stat_sum = psum;
         d.in_stat_sq = psq;
         if ((rc = conv1d_launch(d, stream))) return rc;
@@ -268,19 +239,18 @@ int AspLayer::forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, flo
     if (!have_gstats) {  // else: already written by the producer's fused epilogue statistics
         if ((rc = time_stats_launch(x, ldx, B, T, C, gstats, gstats + C, 2 * C, 0, 1e-12f, stream))) return rc;
     }
-    gmean = gstats;
-    const float* row_bias = nullptr;
     if (global_ctx) {
         // context bias = W[:, C:3C] . [mean; std] + b  (pooling.py:104-117 with the T-constant columns hoisted)
         if ((rc = linear_f32_launch(gstats, 2 * C, wms, 2 * C, tdnn.bias, MV_ACT_NONE, ctxb, A, B, 2 * C, A, 0, stream, lin_ws, lin_ws_floats)))
             return rc;
-        row_bias = ctxb;
+        d.row_bias = ctxb;
     }
-    // h = tanh(BN(ReLU(Wx . x + bias)))
-    if ((rc = run_conv(tdnn, x, MV_DT_F16, ldx, nullptr, 0, h, MV_DT_F16, A, B, T, T, 1, 0, MV_PAD_REFLECT, MV_ACT_RELU,
-                       bn_scale, bn_shift, MV_ACT_TANH, row_bias, /*use_bias=*/!global_ctx, stream)))
-        return rc;
-    return asp_pool_launch(h, conv.w, x, ldx, gmean, 2 * C, pooled, B, T, C, A, logit_bound_log2, stream);
+    d.pre_act = MV_ACT_RELU;
+    d.scale = bn_scale;
+    d.shift = bn_shift;
+    d.post_act = MV_ACT_TANH;
+    if ((rc = conv1d_launch(d, stream))) return rc;
+    return asp_pool_launch(h, conv.w, x, ldx, gstats, 2 * C, pooled, B, T, C, A, logit_bound_log2, stream);
 }
 
 // --------------------------------------------------------------------------------------- SAP / TAP / TSP heads
@@ -299,11 +269,12 @@ int PoolHead::create(MvModelBase* m, const Weights& w, const std::string& prefix
 int PoolHead::forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, float* pooled, hipStream_t st) const {
     int rc;
     switch (type) {
-        case MV_POOL_SAP:
-            if ((rc = run_conv(sap1, x, MV_DT_F16, ldx, nullptr, 0, h, MV_DT_F16, SAP_A, B, T, T, 1, 0, MV_PAD_REFLECT, MV_ACT_NONE, nullptr,
-                               nullptr, MV_ACT_TANH, nullptr, true, st)))
-                return rc;
+        case MV_POOL_SAP: {
+            MvConv1dDesc d = conv_desc(sap1, x, ldx, h, SAP_A, B, T, T);
+            d.post_act = MV_ACT_TANH;
+            if ((rc = conv1d_launch(d, st))) return rc;
             return sap_pool_launch(h, sap2.w, x, ldx, pooled, B, T, C, SAP_A, logit_bound_log2, st);
+        }
         case MV_POOL_TAP:   // the SE squeeze's time mean (time_stats_kernel, mean only)
             return time_stats_launch(x, ldx, B, T, C, pooled, nullptr, C, 0, 0.0f, st);
         case MV_POOL_TSP:
@@ -311,13 +282,6 @@ int PoolHead::forward(const half_t* x, int64_t ldx, int B, int T, half_t* h, flo
         default:
             return fail(MV_ERR_INVALID_ARGUMENT, "pooling head: not SAP, TAP or TSP");
     }
-}
-
-static int check_pool_type(int32_t pooling_type, const char* fn) {
-    if (pooling_type < MV_POOL_ASP || pooling_type > MV_POOL_TSP)
-        return fail(MV_ERR_INVALID_ARGUMENT, std::string(fn) + ": pooling_type " + std::to_string(pooling_type) +
-                                                 " is not MV_POOL_ASP (0), MV_POOL_SAP (1), MV_POOL_TAP (2) or MV_POOL_TSP (3)");
-    return MV_OK;
 }
 
 // fold y = BN_out( W . BN_in(p) + b ) into one affine map (either BN optional)
@@ -420,15 +384,12 @@ struct EcapaModel : MvModelBase {
     ConvLayer block0w;         // block 0 as a 1x1 conv over the contiguous k*Fp window of the reflect-padded features
     bool block0_window = false;
     std::vector<SeRes2> blocks;
-    int pool = MV_POOL_ASP;
-    AspLayer asp;      // pool == MV_POOL_ASP
-    PoolHead head;     // the other heads
+    Pooling pool;
     float* fc_w = nullptr;
     float* fc_b = nullptr;
     int ccat = 0, cmax = 0;
 
     int cm() const { return cfg.channels[nblocks + 1]; }   // the MFA's width (channels[-1])
-    int pooled_width() const { return pool == MV_POOL_ASP ? 2 * cm() : head.width(); }
 
     // a TDNNBlock with `groups` (models/utils.py:120-138): 1 = dense; a grouped 1x1 layer of the native geometry is packed per group and runs as a
     // grouped GEMM; any other grouped layer becomes its block-diagonal dense weight (exact zeros)
@@ -455,6 +416,17 @@ struct EcapaModel : MvModelBase {
         return make_bn(w, prefix + ".norm.norm", cout, &out->scale, &out->shift);
     }
 
+    // TDNNBlock (models/utils.py:138): y = BN(ReLU(conv(x))) with the "same" reflect padding of its dilation
+    static MvConv1dDesc tdnn_desc(const TdnnBlk& t, const half_t* x, int64_t ldx, half_t* y, int64_t ldy, int B, int T, int dil = 1) {
+        MvConv1dDesc d = conv_desc(t.conv, x, ldx, y, ldy, B, T, T);
+        d.dilation = dil;
+        d.pad = dil * (t.conv.k - 1) / 2;
+        d.pre_act = MV_ACT_RELU;
+        d.scale = t.scale;
+        d.shift = t.shift;
+        return d;
+    }
+
     int info(int key, float* value) const override {
         switch (key) {
             case MV_INFO_ECAPA_GROUPED_NATIVE: *value = (float)n_grouped_native; return MV_OK;
@@ -465,9 +437,9 @@ struct EcapaModel : MvModelBase {
         }
     }
 
+    int create(const MvEcapaCfg& c, const Weights& w, int pool_type) { return create(ecapa_cfg_ex(c), w, pool_type); }
     int create(const MvEcapaCfgEx& c, const Weights& w, int pool_type) {
         cfg = c;
-        pool = pool_type;
         input_size = c.input_size;
         embd_dim = c.embd_dim;
         int rc;
@@ -509,11 +481,9 @@ struct EcapaModel : MvModelBase {
         if (Fp == F && g0 == 1) {
             if ((rc = make_tdnn(w, "blocks.0", C0, F, k0, &block0))) return rc;
         } else {
-            std::vector<float> w0, wp((size_t)C0 * Fp * k0, 0.0f);
+            std::vector<float> w0;
             if ((rc = host_dense_weight(w, "blocks.0.conv.conv.weight", C0, F, k0, g0, w0))) return rc;
-            for (int co = 0; co < C0; ++co)
-                memcpy(&wp[(size_t)co * Fp * k0], &w0[(size_t)co * F * k0], (size_t)F * k0 * sizeof(float));
-            float* tmp = upload(wp);
+            float* tmp = upload(pad_input_columns(w0, C0, F, Fp, k0));
             if (tmp == nullptr) return fail(MV_ERR_HIP, "ecapa create: upload failed");
             if ((rc = make_conv_from(tmp, &w, "blocks.0.conv.conv.bias", C0, Fp, k0, &block0.conv))) return rc;
             if ((rc = make_bn(w, "blocks.0.norm.norm", C0, &block0.scale, &block0.shift))) return rc;
@@ -569,17 +539,9 @@ struct EcapaModel : MvModelBase {
         const int M = nblocks + 1;   // the MFA's entry
         MV_REQUIRE(ccat == c.channels[M], "ecapa: channels[-1] must equal the sum of the SE-Res2Net block widths");
         if ((rc = make_tdnn(w, "mfa", c.channels[M], ccat, c.kernel_sizes[M], &mfa, c.groups[M]))) return rc;
-        if (pool == MV_POOL_ASP) {
-            if ((rc = asp.create(this, w, "asp", c.channels[M], c.attention_channels, c.global_context != 0))) return rc;
-            if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn.norm", "", c.embd_dim, 2 * c.channels[M],
-                                        &fc_w, &fc_b)))
-                return rc;
-        } else {
-            // SAP / TAP / TSP: asp_bn is a plain BatchNorm1d over the head's width (ecapa_tdnn.py:229-250)
-            if ((rc = head.create(this, w, "asp", pool, c.channels[M]))) return rc;
-            if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", "asp_bn", "", c.embd_dim, head.width(), &fc_w, &fc_b)))
-                return rc;
-        }
+        if ((rc = pool.create(this, w, "asp", pool_type, c.channels[M], c.attention_channels, c.global_context != 0))) return rc;
+        if ((rc = fold_final_linear(this, w, "fc.conv.weight", "fc.conv.bias", pool.ecapa_bn_name(), "", c.embd_dim, pool.width(), &fc_w, &fc_b)))
+            return rc;
         MV_HIP_OK(hipDeviceSynchronize());
         return MV_OK;
     }
@@ -604,13 +566,13 @@ struct EcapaModel : MvModelBase {
         s.t2 = c.take<half_t>(N * cmax);
         s.sc = c.take<half_t>(N * cmax);
         s.mfa = c.take<half_t>(N * cm());
-        s.h = c.take<half_t>(N * (pool == MV_POOL_ASP ? cfg.attention_channels : head.hidden_width()));
+        s.h = c.take<half_t>(N * pool.hidden_width());
         s.se_mean = c.take<float>((size_t)B * cmax);
         s.se_hid = c.take<float>((size_t)B * cfg.se_channels);
         s.gate = c.take<float>((size_t)B * cmax);
-        s.asp_f = c.take<float>(pool == MV_POOL_ASP ? asp.workspace_floats(B, T) : 0);
-        s.pooled = c.take<float>((size_t)B * pooled_width());
-        s.fc_ws_floats = linear_f32_splitk_floats(B, pooled_width(), cfg.embd_dim);   // K slices of the final layer (linear.hip)
+        s.asp_f = c.take<float>(pool.workspace_floats(B, T));
+        s.pooled = c.take<float>((size_t)B * pool.width());
+        s.fc_ws_floats = linear_f32_splitk_floats(B, pool.width(), cfg.embd_dim);   // K slices of the final layer (linear.hip)
         s.fc_ws = c.take<float>(s.fc_ws_floats);
         s.bytes = c.total();
         return s;
@@ -634,7 +596,7 @@ struct EcapaModel : MvModelBase {
         const Ws s = carve(ws, B, T);
         if (s.bytes > ws_bytes) return fail(MV_ERR_WORKSPACE, "ecapa forward: workspace too small");
         int rc;
-        const int R = MV_PAD_REFLECT;
+        MvConv1dDesc d;
         // features to fp16 once (12 MB) at the pitch ldf = round_up(F, 8) (zeros in channels F..ldf-1), then blocks.0 on the direct-to-LDS path
         const int F = cfg.input_size;
         const int64_t ldf = round_up(F, 8);
@@ -645,15 +607,16 @@ struct EcapaModel : MvModelBase {
             } else {
                 if ((rc = cast_reflect_pad_ragged_launch(feats, s.x16, B, T, F, (int)ldf, pad0, st))) return rc;
             }
-            if ((rc = run_conv(block0w, s.x16, MV_DT_F16, ldf, nullptr, 0, s.a0, MV_DT_F16, cfg.channels[0], B, T + 2 * pad0, T,
-                               1, 0, MV_PAD_ZERO, MV_ACT_RELU, block0.scale, block0.shift, MV_ACT_NONE, nullptr, true, st)))
-                return rc;
+            d = conv_desc(block0w, s.x16, ldf, s.a0, cfg.channels[0], B, T + 2 * pad0, T);   // (the window form: a 1x1 conv over the padded rows)
+            d.pad_mode = MV_PAD_ZERO;
+            d.pre_act = MV_ACT_RELU;
+            d.scale = block0.scale;
+            d.shift = block0.shift;
         } else {
             if ((rc = cast_rows_f32_f16_launch(feats, F, s.x16, ldf, (int64_t)B * T, F, st))) return rc;
-            if ((rc = run_conv(block0.conv, s.x16, MV_DT_F16, ldf, nullptr, 0, s.a0, MV_DT_F16, cfg.channels[0], B, T, T,
-                               cfg.dilations[0], pad0, R, MV_ACT_RELU, block0.scale, block0.shift, MV_ACT_NONE, nullptr, true, st)))
-                return rc;
+            d = tdnn_desc(block0, s.x16, ldf, s.a0, cfg.channels[0], B, T, cfg.dilations[0]);
         }
+        if ((rc = conv1d_launch(d, st))) return rc;
         const half_t* xin = s.a0;
         int64_t ldin = cfg.channels[0];
         int cat_off = 0;
@@ -663,15 +626,13 @@ struct EcapaModel : MvModelBase {
             const half_t* res = xin;
             int64_t ldres = ldin;
             if (b.has_shortcut) {
-                if ((rc = run_conv(b.shortcut, xin, MV_DT_F16, ldin, nullptr, 0, s.sc, MV_DT_F16, C, B, T, T, 1, 0, R, MV_ACT_NONE,
-                                   nullptr, nullptr, MV_ACT_NONE, nullptr, true, st)))
-                    return rc;
+                d = conv_desc(b.shortcut, xin, ldin, s.sc, C, B, T, T);
+                if ((rc = conv1d_launch(d, st))) return rc;
                 res = s.sc;
                 ldres = C;
             }
-            if ((rc = run_conv(b.tdnn1.conv, xin, MV_DT_F16, ldin, nullptr, 0, s.t1, MV_DT_F16, C, B, T, T, 1, 0, R, MV_ACT_RELU,
-                               b.tdnn1.scale, b.tdnn1.shift, MV_ACT_NONE, nullptr, true, st)))
-                return rc;
+            d = tdnn_desc(b.tdnn1, xin, ldin, s.t1, C, B, T);
+            if ((rc = conv1d_launch(d, st, b.tdnn1.conv.groups))) return rc;
             const int steps = cfg.res2net_scale - 1;
             if (res2_chain_supported(T, b.width, steps, b.k, b.dil)) {
                 // whole chain in one launch, one workgroup per utterance (res2.hip)
@@ -688,24 +649,22 @@ struct EcapaModel : MvModelBase {
                 // Res2Net: slice 0 passes through, slice j = blk_{j-1}(x_j [+ y_{j-1}]).  Step j's epilogue also emits the next
                 // step's input x_{j+1} + y_j into a ping-pong scratch slice, so every step reads one plain fp16 tensor.
                 if ((rc = copy_slice_launch(s.t1, C, s.r2, C, b.width, (int64_t)B * T, st))) return rc;
-                const int pad = b.dil * (b.k - 1) / 2;
                 for (int j = 1; j < cfg.res2net_scale; ++j) {
-                    const half_t* in = j == 1 ? s.t1 + (size_t)b.width : s.rs[j & 1];
-                    const int64_t ldin_j = j == 1 ? C : b.width;
                     const bool more = j + 1 < cfg.res2net_scale;
-                    if ((rc = run_conv(b.res2[j - 1].conv, in, MV_DT_F16, ldin_j, nullptr, 0, s.r2 + (size_t)j * b.width, MV_DT_F16, C, B,
-                                       T, T, b.dil, pad, R, MV_ACT_RELU, b.res2[j - 1].scale, b.res2[j - 1].shift, MV_ACT_NONE, nullptr,
-                                       true, st, more ? s.t1 + (size_t)(j + 1) * b.width : nullptr, C, more ? s.rs[(j + 1) & 1] : nullptr,
-                                       b.width)))
-                        return rc;
+                    const half_t* in = j == 1 ? s.t1 + (size_t)b.width : s.rs[j & 1];
+                    d = tdnn_desc(b.res2[j - 1], in, j == 1 ? C : b.width, s.r2 + (size_t)j * b.width, C, B, T, b.dil);
+                    d.add_src = more ? s.t1 + (size_t)(j + 1) * b.width : nullptr;
+                    d.ld_add = C;
+                    d.sum_dst = more ? s.rs[(j + 1) & 1] : nullptr;
+                    d.ld_sum = b.width;
+                    if ((rc = conv1d_launch(d, st))) return rc;
                 }
             }
             // SE: squeeze -> FC/ReLU -> FC/sigmoid -> gate * y + residual, written into the aggregation slice.  The squeeze (mean over
             // time, ecapa_tdnn.py:79) is its own single pass: taken in tdnn2's epilogue (MvConv1dDesc.stat_sum) it costs that layer as
             // much as the pass it replaces (r02a: +32 us against 29 us).
-            if ((rc = run_conv(b.tdnn2.conv, s.r2, MV_DT_F16, C, nullptr, 0, s.t2, MV_DT_F16, C, B, T, T, 1, 0, R, MV_ACT_RELU,
-                               b.tdnn2.scale, b.tdnn2.shift, MV_ACT_NONE, nullptr, true, st)))
-                return rc;
+            d = tdnn_desc(b.tdnn2, s.r2, C, s.t2, C, B, T);
+            if ((rc = conv1d_launch(d, st, b.tdnn2.conv.groups))) return rc;
             if ((rc = time_stats_launch(s.t2, C, B, T, C, s.se_mean, nullptr, C, 0, 0.0f, st))) return rc;
             if ((rc = linear_f32_launch(s.se_mean, C, b.se_w1, C, b.se_b1, MV_ACT_RELU, s.se_hid, cfg.se_channels, B, C,
                                         cfg.se_channels, 0, st)))
@@ -722,17 +681,11 @@ struct EcapaModel : MvModelBase {
         // multi-layer feature aggregation reads the N block outputs in place
         const int Cm = cm(), M = nblocks + 1;
         // (the ASP global mean / std of pooling.py:104-109 are collected by the ASP hidden conv from its own input tiles: AspLayer::forward)
-        if ((rc = run_conv(mfa.conv, s.cat, MV_DT_F16, ccat, nullptr, 0, s.mfa, MV_DT_F16, Cm, B, T, T, cfg.dilations[M],
-                           cfg.dilations[M] * (cfg.kernel_sizes[M] - 1) / 2, R, MV_ACT_RELU, mfa.scale, mfa.shift, MV_ACT_NONE,
-                           nullptr, true, st)))
-            return rc;
-        if (pool == MV_POOL_ASP) {
-            if ((rc = asp.forward(s.mfa, Cm, B, T, s.h, s.asp_f, s.pooled, st))) return rc;
-        } else if ((rc = head.forward(s.mfa, Cm, B, T, s.h, s.pooled, st))) {
-            return rc;
-        }
+        d = tdnn_desc(mfa, s.cat, ccat, s.mfa, Cm, B, T, cfg.dilations[M]);
+        if ((rc = conv1d_launch(d, st, mfa.conv.groups))) return rc;
+        if ((rc = pool.forward(s.mfa, Cm, B, T, s.h, s.asp_f, s.pooled, st))) return rc;
         // asp_bn folded into fc
-        const int P = pooled_width();
+        const int P = pool.width();
         return linear_f32_launch(s.pooled, P, fc_w, P, fc_b, MV_ACT_NONE, emb, cfg.embd_dim, B, P, cfg.embd_dim, 0, st, s.fc_ws,
                                  s.fc_ws_floats);
     }
@@ -745,19 +698,14 @@ struct TdnnModel : MvModelBase {
     ConvLayer conv[5];
     float* scale[4] = {nullptr, nullptr, nullptr, nullptr};
     float* shift[4] = {nullptr, nullptr, nullptr, nullptr};
-    int pool = MV_POOL_ASP;
-    AspLayer asp;      // pool == MV_POOL_ASP
-    PoolHead head;     // the other heads
+    Pooling pool;
     float* fc_w = nullptr;
     float* fc_b = nullptr;
     static constexpr int K[5] = {5, 3, 3, 1, 1};
     static constexpr int D[5] = {1, 2, 3, 1, 1};
 
-    int pooled_width() const { return pool == MV_POOL_ASP ? 2 * cfg.channels : head.width(); }
-
     int create(const MvTdnnCfg& c, const Weights& w, int pool_type) {
         cfg = c;
-        pool = pool_type;
         input_size = c.input_size;
         embd_dim = c.embd_dim;
         MV_REQUIRE(c.channels % 8 == 0, "tdnn: channels must be a multiple of 8");
@@ -769,11 +717,9 @@ struct TdnnModel : MvModelBase {
         for (int i = 0; i < 5; ++i) {
             const std::string p = "td_layer" + std::to_string(i + 1);
             if (i == 0 && Fp != F) {
-                std::vector<float> w0, wp((size_t)c.channels * Fp * K[0], 0.0f);
+                std::vector<float> w0;
                 if ((rc = w.host(p + ".weight", (int64_t)c.channels * F * K[0], w0))) return rc;
-                for (int co = 0; co < c.channels; ++co)
-                    memcpy(&wp[(size_t)co * Fp * K[0]], &w0[(size_t)co * F * K[0]], (size_t)F * K[0] * sizeof(float));
-                float* tmp = upload(wp);
+                float* tmp = upload(pad_input_columns(w0, c.channels, F, Fp, K[0]));
                 if (tmp == nullptr) return fail(MV_ERR_HIP, "tdnn create: upload failed");
                 if ((rc = make_conv_from(tmp, &w, p + ".bias", c.channels, Fp, K[0], &conv[0]))) return rc;
             } else if ((rc = make_conv(w, p + ".weight", p + ".bias", c.channels, i == 0 ? F : c.channels, K[i], &conv[i]))) {
@@ -782,14 +728,8 @@ struct TdnnModel : MvModelBase {
             if (i < 4)
                 if ((rc = make_bn(w, "bn" + std::to_string(i + 1), c.channels, &scale[i], &shift[i]))) return rc;
         }
-        if (pool == MV_POOL_ASP) {
-            if ((rc = asp.create(this, w, "pooling", c.channels, 128, true))) return rc;
-        } else if ((rc = head.create(this, w, "pooling", pool, c.channels))) {
-            return rc;
-        }
-        if ((rc = fold_final_linear(this, w, "linear.weight", "linear.bias", "bn5", "bn6", c.embd_dim, pooled_width(), &fc_w,
-                                    &fc_b)))
-            return rc;
+        if ((rc = pool.create(this, w, "pooling", pool_type, c.channels, 128, true))) return rc;
+        if ((rc = fold_final_linear(this, w, "linear.weight", "linear.bias", "bn5", "bn6", c.embd_dim, pool.width(), &fc_w, &fc_b))) return rc;
         MV_HIP_OK(hipDeviceSynchronize());
         return MV_OK;
     }
@@ -806,9 +746,9 @@ struct TdnnModel : MvModelBase {
         Ws s;
         s.a = c.take<half_t>(N * cfg.channels);
         s.b = c.take<half_t>(N * cfg.channels);
-        s.h = c.take<half_t>(N * (pool == MV_POOL_ASP ? 128 : head.hidden_width()));
-        s.asp_f = c.take<float>(pool == MV_POOL_ASP ? asp.workspace_floats(B, T) : 0);
-        s.pooled = c.take<float>((size_t)B * pooled_width());
+        s.h = c.take<half_t>(N * pool.hidden_width());
+        s.asp_f = c.take<float>(pool.workspace_floats(B, T));
+        s.pooled = c.take<float>((size_t)B * pool.width());
         s.xp = Fp != cfg.input_size ? c.take<float>(N * Fp) : nullptr;   // zero-padded features of a ragged F
         s.bytes = c.total();
         return s;
@@ -837,92 +777,64 @@ struct TdnnModel : MvModelBase {
         for (int i = 0; i < 5; ++i) {
             const int Tout = Tin - D[i] * (K[i] - 1);
             half_t* y = bufs[i & 1];
-            if ((rc = run_conv(conv[i], x, xdt, ldx, nullptr, 0, y, MV_DT_F16, cfg.channels, B, Tin, Tout, D[i], 0, MV_PAD_ZERO,
-                               MV_ACT_RELU, i < 4 ? scale[i] : nullptr, i < 4 ? shift[i] : nullptr, MV_ACT_NONE, nullptr, true,
-                               st)))
-                return rc;
+            // y = BN(ReLU(conv(x))), unpadded (tdnn.py:57-64); no BN behind td_layer5
+            MvConv1dDesc d = conv_desc(conv[i], x, ldx, y, cfg.channels, B, Tin, Tout);
+            d.x_dtype = xdt;
+            d.dilation = D[i];
+            d.pad_mode = MV_PAD_ZERO;
+            d.pre_act = MV_ACT_RELU;
+            d.scale = i < 4 ? scale[i] : nullptr;
+            d.shift = i < 4 ? shift[i] : nullptr;
+            if ((rc = conv1d_launch(d, st))) return rc;
             x = y;
             xdt = MV_DT_F16;
             ldx = cfg.channels;
             Tin = Tout;
         }
-        if (pool == MV_POOL_ASP) {
-            if ((rc = asp.forward(static_cast<const half_t*>(x), cfg.channels, B, Tin, s.h, s.asp_f, s.pooled, st))) return rc;
-        } else if ((rc = head.forward(static_cast<const half_t*>(x), cfg.channels, B, Tin, s.h, s.pooled, st))) {
-            return rc;
-        }
-        const int P = pooled_width();
+        if ((rc = pool.forward(static_cast<const half_t*>(x), cfg.channels, B, Tin, s.h, s.asp_f, s.pooled, st))) return rc;
+        const int P = pool.width();
         return linear_f32_launch(s.pooled, P, fc_w, P, fc_b, MV_ACT_NONE, emb, cfg.embd_dim, B, P, cfg.embd_dim, 0, st);
     }
 };
-constexpr int TdnnModel::K[5];
-constexpr int TdnnModel::D[5];
+
+// the mv_*_create* entry points: the checks under the entry point's own name `fn`, the state_dict, the model
+template <typename Model, typename Cfg>
+static int create_model(const char* fn, const Cfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
+    MV_REQUIRE(cfg != nullptr && out != nullptr, std::string(fn) + ": null argument");
+    if (pooling_type < MV_POOL_ASP || pooling_type > MV_POOL_TSP)
+        return fail(MV_ERR_INVALID_ARGUMENT, std::string(fn) + ": pooling_type " + std::to_string(pooling_type) +
+                                                 " is not MV_POOL_ASP (0), MV_POOL_SAP (1), MV_POOL_TAP (2) or MV_POOL_TSP (3)");
+    int rc;
+    Weights w;
+    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
+    auto m = std::make_unique<Model>();
+    if ((rc = m->create(*cfg, w, pooling_type)) != MV_OK) return rc;
+    *out = reinterpret_cast<MvModel*>(static_cast<MvModelBase*>(m.release()));
+    return MV_OK;
+}
 
 }  // namespace mv
 
 extern "C" {
 
 int mv_ecapa_create(const MvEcapaCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_ecapa_create: null argument");
-    mv::Weights w;
-    int rc = w.init(tensors, num_tensors);
-    if (rc != MV_OK) return rc;
-    auto m = std::make_unique<mv::EcapaModel>();
-    rc = m->create(mv::ecapa_cfg_ex(*cfg), w, MV_POOL_ASP);
-    if (rc != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
-    return MV_OK;
+    return mv::create_model<mv::EcapaModel>("mv_ecapa_create", cfg, MV_POOL_ASP, tensors, num_tensors, out);
 }
 
 int mv_ecapa_create_pooled(const MvEcapaCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_ecapa_create_pooled: null argument");
-    int rc = mv::check_pool_type(pooling_type, "mv_ecapa_create_pooled");
-    if (rc != MV_OK) return rc;
-    mv::Weights w;
-    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
-    auto m = std::make_unique<mv::EcapaModel>();
-    rc = m->create(mv::ecapa_cfg_ex(*cfg), w, pooling_type);
-    if (rc != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
-    return MV_OK;
+    return mv::create_model<mv::EcapaModel>("mv_ecapa_create_pooled", cfg, pooling_type, tensors, num_tensors, out);
 }
 
 int mv_ecapa_create_ex(const MvEcapaCfgEx* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_ecapa_create_ex: null argument");
-    int rc = mv::check_pool_type(pooling_type, "mv_ecapa_create_ex");
-    if (rc != MV_OK) return rc;
-    mv::Weights w;
-    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
-    auto m = std::make_unique<mv::EcapaModel>();
-    rc = m->create(*cfg, w, pooling_type);
-    if (rc != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
-    return MV_OK;
+    return mv::create_model<mv::EcapaModel>("mv_ecapa_create_ex", cfg, pooling_type, tensors, num_tensors, out);
 }
 
 int mv_tdnn_create(const MvTdnnCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_tdnn_create: null argument");
-    mv::Weights w;
-    int rc = w.init(tensors, num_tensors);
-    if (rc != MV_OK) return rc;
-    auto m = std::make_unique<mv::TdnnModel>();
-    rc = m->create(*cfg, w, MV_POOL_ASP);
-    if (rc != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
-    return MV_OK;
+    return mv::create_model<mv::TdnnModel>("mv_tdnn_create", cfg, MV_POOL_ASP, tensors, num_tensors, out);
 }
 
 int mv_tdnn_create_pooled(const MvTdnnCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_tdnn_create_pooled: null argument");
-    int rc = mv::check_pool_type(pooling_type, "mv_tdnn_create_pooled");
-    if (rc != MV_OK) return rc;
-    mv::Weights w;
-    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
-    auto m = std::make_unique<mv::TdnnModel>();
-    rc = m->create(*cfg, w, pooling_type);
-    if (rc != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
-    return MV_OK;
+    return mv::create_model<mv::TdnnModel>("mv_tdnn_create_pooled", cfg, pooling_type, tensors, num_tensors, out);
 }
 
 int mv_model_destroy(MvModel* m) {
