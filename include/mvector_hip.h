@@ -178,6 +178,22 @@ size_t mv_melspec_workspace_bytes(const MvMelSpec* h, int32_t B, int64_t L);
 int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
                        const float* lens_ratio, float* out, void* workspace, size_t workspace_bytes,
                        mv_stream_t stream);
+/* Variable-length batch (additive since ABI 5; also mv_spectrogram_forward_varlen and mv_mfcc_forward_varlen below): row b holds
+ * n_b = clamp(num_samples[b], 0, L) valid samples (device array, int64, B entries; NULL is refused).  Row b is featurised exactly as the
+ * same handle's forward featurises it alone as a [1, n_b] batch without a ratio, and BIT FOR BIT so -- the reference's evaluation path,
+ * which featurises per utterance (mvector/data_utils/reader.py:100-106) and zero-pads the features (collate_fn.py:11-19):
+ *   - T_b = what *_num_frames(h, n_b) returns; the output keeps the shape [B, T(L), F] and its rows t >= T_b are zero;
+ *   - the samples behind n_b are never read into a result;
+ *   - centre padding takes the mirror / edge value / wrap-around / zeros at n_b (every pad_mode, and pad > 0), center = 0 frames lie inside n_b;
+ *   - the time mean is taken over the row's T_b frames, summed in an order that depends on T_b alone (not on T(L), B or the stream);
+ *   - MFCC with log_mels = 0: the dB floor is (the ROW's loudest value) - top_db.  The batch coupling of mv_mfcc_forward stays as it is.
+ * A row the reference cannot featurise -- torch.stft raises (n_b + 2 pad <= n_fft / 2 under reflect, < n_fft / 2 under circular padding),
+ * there is nothing to pad (n_b + 2 pad == 0, any pad_mode), or no frame fits (n_b + 2 pad < n_fft with center = 0) -- yields an all-zero row
+ * and no fault, whatever subtract_time_mean says; the reference's dataset skips such items.
+ * The geometry checks are those of the forward on (B, L); the workspace is the one mv_*_workspace_bytes(h, B, L) reports. */
+int mv_melspec_forward_varlen(const MvMelSpec* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                              const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes,
+                              mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Front-end 3: Spectrogram (power STFT, the linear-frequency bins are the features) + time-mean
@@ -211,6 +227,10 @@ size_t mv_spectrogram_workspace_bytes(const MvSpectrogram* h, int32_t B, int64_t
 int mv_spectrogram_forward(const MvSpectrogram* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
                            const float* lens_ratio, float* out, void* workspace, size_t workspace_bytes,
                            mv_stream_t stream);
+/* every row on its own length: the semantics of mv_melspec_forward_varlen */
+int mv_spectrogram_forward_varlen(const MvSpectrogram* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                                  const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes,
+                                  mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Front-end 4: MFCC (mel power -> dB with a top_db floor, or log(mel + 1e-6) -> DCT-II) + time-mean
@@ -243,6 +263,10 @@ size_t mv_mfcc_workspace_bytes(const MvMfcc* h, int32_t B, int64_t L);
 int mv_mfcc_forward(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
                     const float* lens_ratio, float* out, void* workspace, size_t workspace_bytes,
                     mv_stream_t stream);
+/* every row on its own length, its own dB floor included: the semantics of mv_melspec_forward_varlen */
+int mv_mfcc_forward_varlen(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                           const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes,
+                           mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Backbones.  A model handle is built from the reference-layout fp32 ``state_dict`` (same key names

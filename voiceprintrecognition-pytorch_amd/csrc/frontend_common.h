@@ -107,6 +107,36 @@ __device__ __forceinline__ cplx lds_read_single(const cplx* p) {
 
 constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHL4 = 0x104, DPP_ROW_SHL8 = 0x108;
 
+// ---- variable-length batches of the STFT front-ends (mv_melspec / mv_spectrogram / mv_mfcc _forward_varlen) ---------------
+// Every kernel of that path takes one of these.  num_samples == nullptr is the batch form: every row has the kernel's own L
+// samples and T frames.  Otherwise row b has clamp(num_samples[b], 0, L) samples and is transformed exactly as a [1, n_b] batch
+// would be: its own frame count (the rule of mv_melspec_num_frames), its own padding at n_b, its own time mean.
+struct RowLens {
+    const int64_t* num_samples;   // [B] on the device, or nullptr
+    int64_t L;                    // the caller's row length (the clamp)
+    int64_t extra;                // samples melspec_extend_kernel puts around every row (0: the transform kernels pad themselves)
+    int32_t cfg_pad, center, n_fft, hop;
+    int32_t min_len;              // fewest samples, cfg.pad included, that the centre padding accepts (torch.stft raises below it)
+};
+
+__device__ __forceinline__ int64_t row_samples(const RowLens& v, int b) {
+    const int64_t n = v.num_samples[b];
+    return n < 0 ? 0 : (n > v.L ? v.L : n);
+}
+
+// Row b as a transform kernel sees it: *len = its samples (extension included), return = its frames.  A row the reference cannot
+// featurise (torch.stft raises, or no frame fits) has no frames: its output rows are all zero.  Batch form: (L_all, T_all).
+__device__ __forceinline__ int row_frames(const RowLens& v, int b, int64_t L_all, int T_all, int64_t* len) {
+    if (v.num_samples == nullptr) {
+        *len = L_all;
+        return T_all;
+    }
+    const int64_t n = row_samples(v, b), lp = n + 2 * (int64_t)v.cfg_pad;
+    *len = n + v.extra;
+    if (v.center) return (lp < v.min_len || lp == 0) ? 0 : (int)(1 + lp / v.hop);   // (nothing to pad: F.pad's replicate raises on an empty signal too)
+    return lp < v.n_fft ? 0 : (int)(1 + (lp - v.n_fft) / v.hop);
+}
+
 // ---- banded mel stage on v_mfma_f32_4x4x1 -------------------------------------------------------------------------------
 // One MFMA pass = 16 blocks x (4 frames x 4 adjacent filters); every block walks `steps` consecutive bins of the power row
 // from its own start (a multiple of 4, so operands are 16-byte LDS reads; start + steps <= row_len keeps the walk inside

@@ -24,6 +24,7 @@ struct MelFftArgs {
     const float* melb;        // MFMA B-operand order (frontend_common.h), passes back to back
     int B, T, n_fft, hop, pad, n_mels, cmn, tile_rows;
     MelPlan plan;
+    RowLens rows;             // per-row lengths (variable-length form) or none
 };
 
 size_t melfft_fixed_lds_bytes();

@@ -87,12 +87,15 @@ __global__ __launch_bounds__(MF_WAVES * 64) void melspec_pow2_kernel(MelFftArgs 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, fs = lane >> 4;
     const int b = blockIdx.x;
-    const int T = a.T, nm = a.n_mels, n_fft = a.n_fft;
+    const int nm = a.n_mels, n_fft = a.n_fft;
+    // T frames of Lb samples: the batch's, or this row's own (variable-length form; the output keeps a.T rows, zero behind T)
+    int64_t Lb;
+    const int T = row_frames(a.rows, b, a.L, a.T, &Lb);
     const int sb = 1024 / n_fft;       // bin k of the n_fft-point transform = bin k * sb of the 1024-point one
     const int sbl = 31 - __builtin_clz(sb);  // sb = 1 << sbl (a run-time division per stored bin would cost more than the split itself)
     const int nrun = n_fft >> 5;       // 32-sample runs per frame (n1 < nrun carry samples)
     const float* x = a.wav + (int64_t)b * a.wav_stride;
-    float* orow = a.out + (int64_t)b * T * nm;
+    float* orow = a.out + (int64_t)b * a.T * nm;
 
     for (int i = tid; i < 1024; i += THREADS) {
         lwin[i] = i < n_fft ? a.window[i] : 0.0f;
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(MF_WAVES * 64) void melspec_pow2_kernel(MelFftArgs 
         const int64_t start = (int64_t)f * a.hop - a.pad;
         const int qs = MV_UNIFORM(q);
         const int f_last = qs * 4 + 3 < T ? qs * 4 + 3 : T - 1;
-        const bool interior = (int64_t)qs * 4 * a.hop - a.pad >= 0 && (int64_t)f_last * a.hop - a.pad + n_fft <= a.L;
+        const bool interior = (int64_t)qs * 4 * a.hop - a.pad >= 0 && (int64_t)f_last * a.hop - a.pad + n_fft <= Lb;
         if (interior) {       // (one branch around all loads: inside the unrolled loop the compiler turns it into two loads + selects each)
 #pragma unroll
             for (int h = 0; h < 16; ++h) {
@@ -157,9 +160,9 @@ __global__ __launch_bounds__(MF_WAVES * 64) void melspec_pow2_kernel(MelFftArgs 
             auto edge = [&](int64_t i) {
                 if (a.pad > 0) {
                     if (i < 0) i = -i;
-                    if (i >= a.L) i = 2 * (a.L - 1) - i;
+                    if (i >= Lb) i = 2 * (Lb - 1) - i;
                 }
-                return (i >= 0 && i < a.L) ? x[i] : 0.0f;
+                return (i >= 0 && i < Lb) ? x[i] : 0.0f;
             };
 #pragma unroll 1
             for (int h = 0; h < 16; ++h) {   // rolled: the utterance's first and last frames only
@@ -339,7 +342,7 @@ __global__ __launch_bounds__(MF_WAVES * 64) void melspec_pow2_kernel(MelFftArgs 
         float s = 0.0f;
 #pragma unroll
         for (int w = 0; w < MF_WAVES; ++w) s += colsum[w * 256 + tid];
-        mean[tid] = (a.cmn && tid < nm) ? s / (float)T : 0.0f;
+        mean[tid] = (a.cmn && tid < nm && T > 0) ? s / (float)T : 0.0f;
     }
     __syncthreads();
     int mask_len = T;
@@ -360,6 +363,8 @@ __global__ __launch_bounds__(MF_WAVES * 64) void melspec_pow2_kernel(MelFftArgs 
             const float4v raw = *gp;
             *gp = t < mask_len ? raw - m4 : zero4;
         }
+        for (t = T + r0; t < a.T; t += rows_per_pass)         // variable-length form: the rows behind the row's own frames
+            *(reinterpret_cast<float4v*>(orow + (int64_t)t * nm) + cg) = zero4;
     }
 }
 

@@ -35,15 +35,24 @@ struct StftArgs {
     float* P;             // [B*T][nbin_pad]
     int B, T, n_fft, kpad, hop, pad, nbin, nbin_pad;
     float power;   // exponent of |X|
+    RowLens rows;  // per-row lengths (variable-length form) or none
 };
 
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));  // 16-byte load from a 4-byte aligned address
 
 // pad / pad_mode (torchaudio.functional.spectrogram: F.pad(waveform, (pad, pad)) with zeros, then torch.stft(center=True, pad_mode=...) extends by
 // n_fft / 2 on either side): the extended signal, written once; the transform kernels then see a centre = False problem
+// num_samples (variable-length form): row b is extended at its own length n_b -- the mirror, edge value, wrap-around or zeros are taken at n_b, the
+// samples behind n_b are never read, and the row is zero behind its own n_b + 2 pad + 2 centre samples
 __global__ __launch_bounds__(256) void melspec_extend_kernel(const float* wav, int64_t wav_stride, int64_t L, float* dst, int64_t dst_stride, int64_t L2,
-                                                             int pad, int centre, int mode) {
+                                                             int pad, int centre, int mode, const int64_t* num_samples) {
     const int b = blockIdx.y;
+    if (num_samples != nullptr) {   // uniform
+        int64_t n = num_samples[b];
+        n = n < 0 ? 0 : (n > L ? L : n);
+        L2 -= L - n;
+        L = n;
+    }
     const int64_t Lp = L + 2 * (int64_t)pad;
     const float* src = wav + (int64_t)b * wav_stride;
     float* row = dst + (int64_t)b * dst_stride;
@@ -94,10 +103,13 @@ __global__ __launch_bounds__(256) void stft_power_kernel(StftArgs a) {
     const int t = (int)(row - (int64_t)b * a.T);
     const float* x = a.wav + (int64_t)b * a.wav_stride;
     const int64_t start = (int64_t)t * a.hop - a.pad;
-    const bool interior = start >= 0 && start + a.n_fft <= a.L;
+    int64_t Lb;   // this row's samples and frames (variable-length form: a frame behind the row's own count reads nothing and has power 0)
+    const bool live = t < row_frames(a.rows, b, a.L, a.T, &Lb);
+    const bool interior = live && start >= 0 && start + a.n_fft <= Lb;
     const int N = a.n_fft, kfold = N / 2 + 1;
     auto xw = [&](int n) {  // windowed sample n of this lane's frame
-        const int64_t idx = interior ? start + n : reflect_index(start + n, a.L);
+        if (!live) return 0.0f;
+        const int64_t idx = interior ? start + n : reflect_index(start + n, Lb);
         return x[idx] * a.window[n];
     };
 
@@ -169,7 +181,7 @@ __global__ __launch_bounds__(256) void stft_power_kernel(StftArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int64_t orow = row0 + 4 * g + r;
                 if (orow < nframes) {
-                    const float p = re[j][r] * re[j][r] + im[j][r] * im[j][r];
+                    const float p = fmaf(re[j][r], re[j][r], im[j][r] * im[j][r]);   // (spelled out: one rounding order for every r and every compiler)
                     a.P[orow * a.nbin_pad + bin] = a.power == 2.0f ? p : (a.power == 1.0f ? sqrtf(p) : powf(p, 0.5f * a.power));   // uniform
                 }
             }
@@ -213,6 +225,7 @@ struct MelTileArgs {
     int B, T, hop, pad, n_mels, cmn, tile_rows;   // SPEC: n_mels = 201 bins
     MelPlan plan;
     float power;              // SPEC: exponent of |X| (the mel instantiation takes 2)
+    RowLens rows;             // per-row lengths (variable-length form) or none
 };
 
 // real 5-point DFT: X[d] = sum_a v[a] W5^(a d); returns X[0] (real) and X[1], X[2] (X[5-d] = conj X[d])
@@ -270,9 +283,12 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, fs = lane >> 4;
     const int b = blockIdx.x;
-    const int T = a.T, nm = a.n_mels;
+    const int nm = a.n_mels;
+    // T frames of Lb samples: the batch's, or this row's own (variable-length form; the output keeps a.T rows, zero behind T)
+    int64_t Lb;
+    const int T = row_frames(a.rows, b, a.L, a.T, &Lb);
     const float* x = a.wav + (int64_t)b * a.wav_stride;
-    float* orow = a.out + (int64_t)b * T * nm;
+    float* orow = a.out + (int64_t)b * a.T * nm;
 
     // ---- per-lane constants ----
     float cwin[25];
@@ -321,7 +337,7 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
         // branch would emit both paths behind exec masks and make the edge path wait for every interior load it overwrites
         const int qs = MV_UNIFORM(q);
         const int f_last = qs * 4 + 3 < T ? qs * 4 + 3 : T - 1;
-        const bool interior = (int64_t)qs * 4 * a.hop - a.pad >= 0 && (int64_t)f_last * a.hop - a.pad + 400 <= a.L;
+        const bool interior = (int64_t)qs * 4 * a.hop - a.pad >= 0 && (int64_t)f_last * a.hop - a.pad + 400 <= Lb;
         if (interior) {
             const float* fp = x + start + l16;
 #pragma unroll
@@ -332,9 +348,9 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
                 int64_t i = start + 16 * n1 + l16;
                 if (a.pad > 0) {
                     if (i < 0) i = -i;
-                    if (i >= a.L) i = 2 * (a.L - 1) - i;
+                    if (i >= Lb) i = 2 * (Lb - 1) - i;
                 }
-                raw[n1] = (i >= 0 && i < a.L) ? x[i] : 0.0f;
+                raw[n1] = (i >= 0 && i < Lb) ? x[i] : 0.0f;
             }
         }
     };
@@ -511,7 +527,7 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
         float s = 0.0f;
 #pragma unroll
         for (int w = 0; w < MST_WAVES; ++w) s += colsum[w * 256 + tid];
-        mean[tid] = (a.cmn && tid < nm) ? s / (float)T : 0.0f;
+        mean[tid] = (a.cmn && tid < nm && T > 0) ? s / (float)T : 0.0f;
     }
     __syncthreads();
     int mask_len = T;
@@ -526,6 +542,7 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
             const int t = i / nm, c = i - t * nm;
             orow[i] = t < mask_len ? orow[i] - mean[c] : 0.0f;
         }
+        for (int i = T * nm + tid; i < a.T * nm; i += THREADS) orow[i] = 0.0f;   // variable-length form: the rows behind the row's own frames
         return;
     }
     const int qn = nm >> 2;  // n_mels % 4 == 0 for this kernel
@@ -544,17 +561,22 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
             const float4v raw = *gp;
             *gp = t < mask_len ? raw - m4 : zero4;
         }
+        for (t = T + r0; t < a.T; t += rows_per_pass)         // variable-length form: the rows behind the row's own frames
+            *(reinterpret_cast<float4v*>(orow + (int64_t)t * nm) + cg) = zero4;
     }
 }
 
-// out[b, t, c] -= mean_t out[b, :, c]; frames t >= mask_len zeroed.  One workgroup per utterance.
-__global__ __launch_bounds__(256) void cmn_mask_kernel(float* out, int T, int C, const float* lens_ratio, int cmn) {
+// out[b, t, c] -= mean_t out[b, :, c]; frames t >= mask_len zeroed.  One workgroup per utterance.  Variable-length form (rows): the mean is taken
+// over the row's own Tb frames -- four time phases whose members depend on Tb alone -- and the frames behind them are zeroed.
+__global__ __launch_bounds__(256) void cmn_mask_kernel(float* out, int T, int C, const float* lens_ratio, int cmn, RowLens rows) {
     __shared__ float part[4][256];
     __shared__ float mean[256];
     const int b = blockIdx.x;
     float* o = out + (int64_t)b * T * C;
     const int tid = threadIdx.x;
-    int mask_len = T;
+    int64_t Lb;
+    const int Tb = row_frames(rows, b, 0, T, &Lb);
+    int mask_len = Tb;
     if (lens_ratio != nullptr) mask_len = (int)rintf(lens_ratio[b] * (float)T);
     for (int c0 = 0; c0 < C; c0 += 64) {
         // 64 columns x 4 time phases
@@ -562,10 +584,10 @@ __global__ __launch_bounds__(256) void cmn_mask_kernel(float* out, int T, int C,
         const int ph = tid >> 6;
         float s = 0.0f;
         if (c < C)
-            for (int t = ph; t < T; t += 4) s += o[(int64_t)t * C + c];
+            for (int t = ph; t < Tb; t += 4) s += o[(int64_t)t * C + c];
         part[ph][tid & 63] = s;
         __syncthreads();
-        if (tid < 64) mean[tid] = cmn ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)T : 0.0f;
+        if (tid < 64) mean[tid] = cmn && Tb > 0 ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)Tb : 0.0f;
         __syncthreads();
         if (c < C) {
             const float m = mean[tid & 63];
@@ -580,24 +602,27 @@ __global__ __launch_bounds__(256) void cmn_mask_kernel(float* out, int T, int C,
 
 // Spectrogram rows: P [b * T + t][ldp] (stft_power_kernel's padded bin rows) -> out [b][t][C] minus the time mean over ALL frames, frames
 // t >= round_half_even(ratio * T) zeroed.  One workgroup per utterance; sums in the fixed order of cmn_mask_kernel.
-__global__ __launch_bounds__(256) void spec_cmn_mask_kernel(const float* P, int ldp, float* out, int T, int C, const float* lens_ratio, int cmn) {
+// Variable-length form (rows): as cmn_mask_kernel.
+__global__ __launch_bounds__(256) void spec_cmn_mask_kernel(const float* P, int ldp, float* out, int T, int C, const float* lens_ratio, int cmn, RowLens rows) {
     __shared__ float part[4][64];
     __shared__ float mean[64];
     const int b = blockIdx.x;
     const float* p = P + (int64_t)b * T * ldp;
     float* o = out + (int64_t)b * T * C;
     const int tid = threadIdx.x;
-    int mask_len = T;
+    int64_t Lb;
+    const int Tb = row_frames(rows, b, 0, T, &Lb);
+    int mask_len = Tb;
     if (lens_ratio != nullptr) mask_len = (int)rintf(lens_ratio[b] * (float)T);
     for (int c0 = 0; c0 < C; c0 += 64) {
         const int c = c0 + (tid & 63);
         const int ph = tid >> 6;
         float s = 0.0f;
         if (c < C)
-            for (int t = ph; t < T; t += 4) s += p[(int64_t)t * ldp + c];
+            for (int t = ph; t < Tb; t += 4) s += p[(int64_t)t * ldp + c];
         part[ph][tid & 63] = s;
         __syncthreads();
-        if (tid < 64) mean[tid] = cmn ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)T : 0.0f;
+        if (tid < 64) mean[tid] = cmn && Tb > 0 ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)Tb : 0.0f;
         __syncthreads();
         if (c < C) {
             const float m = mean[tid & 63];
@@ -875,12 +900,42 @@ size_t mv_melspec_workspace_bytes(const MvMelSpec* h, int32_t B, int64_t L) {
 
 int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
                        const float* lens_ratio, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    return mv::melspec_forward_rows(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int mv_melspec_forward_varlen(const MvMelSpec* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                              const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    MV_REQUIRE(num_samples != nullptr, "mv_melspec_forward_varlen: null length array");
+    return mv::melspec_forward_rows(h, wav, B, L, wav_stride, nullptr, num_samples, out, workspace, workspace_bytes, stream);
+}
+
+}  // extern "C"
+
+mv::RowLens mv::melspec_row_lens(const MvMelSpec* h, const int64_t* num_samples, int64_t L) {
+    mv::RowLens v = {};
+    v.num_samples = num_samples;
+    v.L = L;
+    v.extra = h->pre_pad ? 2 * (int64_t)h->cfg.pad + 2 * (int64_t)h->pad : 0;
+    v.cfg_pad = h->cfg.pad;
+    v.center = h->cfg.center;
+    v.n_fft = h->cfg.n_fft;
+    v.hop = h->cfg.hop_length;
+    // what the batch form refuses for the whole call: reflect needs more than n_fft / 2 samples, circular at least n_fft / 2
+    v.min_len = !h->cfg.center ? 0 : (h->cfg.pad_mode == MV_STFT_PAD_REFLECT ? h->pad + 1 : (h->cfg.pad_mode == MV_STFT_PAD_CIRCULAR ? h->pad : 0));
+    return v;
+}
+
+// the forward of both forms: lens_ratio (batch form, or neither) or num_samples (variable-length form), never both
+int mv::melspec_forward_rows(const MvMelSpec* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
+                             const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
     MV_REQUIRE(h != nullptr, "mv_melspec_forward: null handle");
     MV_REQUIRE(B >= 0 && L >= 0 && wav_stride >= L, "mv_melspec_forward: bad batch geometry");
+    MV_REQUIRE(lens_ratio == nullptr || num_samples == nullptr, "mv_melspec_forward: lens_ratio and num_samples are mutually exclusive");
     int64_t T = 0;
     mv_melspec_num_frames(h, L, &T);
     if (B == 0 || T == 0) return MV_OK;
     MV_REQUIRE(wav != nullptr && out != nullptr && workspace != nullptr, "mv_melspec_forward: null buffer");
+    const mv::RowLens rows = mv::melspec_row_lens(h, num_samples, L);
     int centre_pad = h->pad;   // what the transform kernels still have to reflect themselves
     if (h->pre_pad) {
         const int64_t Lp = L + 2 * (int64_t)h->cfg.pad;
@@ -892,7 +947,7 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
         const int64_t L2 = melspec_extended_len(h, L), stride2 = melspec_extended_stride(h, L);
         float* dst = static_cast<float*>(workspace);
         MV_LAUNCH(mv::melspec_extend_kernel, ((unsigned)mv::ceil_div(L2, (int64_t)1024), (unsigned)B, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), wav, wav_stride, L,
-                  dst, stride2, L2, h->cfg.pad, h->pad, h->cfg.pad_mode);
+                  dst, stride2, L2, h->cfg.pad, h->pad, h->cfg.pad_mode, num_samples);
         int rc = mv::check_launch("melspec_extend_kernel");
         if (rc != MV_OK) return rc;
         wav = dst;
@@ -910,6 +965,7 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
         t.window = h->d_window; t.tw400 = h->d_tw400; t.melb = nullptr;
         t.B = B; t.T = (int)T; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->nbin; t.cmn = h->cfg.subtract_time_mean;
         t.power = h->cfg.power;
+        t.rows = rows;
         // as many 201-float rows as fit next to the wave slots stay in LDS (136); the rest go through global memory
         const size_t slots = (size_t)mv::MST_WAVES * mv::MST_SLOT_FLOATS * sizeof(float);
         int64_t rows = (int64_t)((160 * 1024 - slots) / ((size_t)h->nbin * sizeof(float))) & ~(int64_t)3;
@@ -926,6 +982,7 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
         t.B = B; t.T = (int)T; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->cfg.n_mels; t.cmn = h->cfg.subtract_time_mean;
         t.plan = h->plan;
         t.power = 2.0f;
+        t.rows = rows;
         // feature rows that fit next to the wave slots stay in LDS until the time mean is known; the rest go through global memory
         const size_t slots = (size_t)mv::MST_WAVES * mv::MST_SLOT_FLOATS * sizeof(float);
         int64_t rows = (int64_t)((160 * 1024 - slots) / ((size_t)h->cfg.n_mels * sizeof(float))) & ~(int64_t)3;
@@ -944,6 +1001,7 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
         t.B = B; t.T = (int)T; t.n_fft = h->cfg.n_fft; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->cfg.n_mels;
         t.cmn = h->cfg.subtract_time_mean;
         t.plan = h->plan;
+        t.rows = rows;
         const size_t fixed = mv::melfft_fixed_lds_bytes();
         int64_t rows = (int64_t)((160 * 1024 - fixed) / ((size_t)h->cfg.n_mels * sizeof(float))) & ~(int64_t)3;
         const int64_t need = (T + 3) & ~(int64_t)3;
@@ -974,6 +1032,7 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
     a.nbin = h->nbin;
     a.nbin_pad = h->nbin_pad;
     a.power = h->cfg.power;
+    a.rows = rows;
     const int64_t nframes = (int64_t)B * T;
     const unsigned gx = (unsigned)mv::ceil_div(nframes, 64);  // 4 waves x 16 frames
     // 7 bin tiles per wave (56 accumulator registers for re + im: four waves per SIMD); the default n_fft = 400 has 13 tiles
@@ -983,18 +1042,16 @@ int mv_melspec_forward(const MvMelSpec* h, const float* wav, int32_t B, int64_t 
     if (rc != MV_OK) return rc;
     if (h->spectrogram) {
         MV_LAUNCH(mv::spec_cmn_mask_kernel, ((unsigned)B, 1, 1), (256, 1, 1), 0, st, a.P, h->nbin_pad, out, (int)T, h->nbin, lens_ratio,
-                  h->cfg.subtract_time_mean);
+                  h->cfg.subtract_time_mean, rows);
         return mv::check_launch("spec_cmn_mask_kernel");
     }
     rc = mv::linear_f32_launch(a.P, h->nbin_pad, h->d_fbT, h->nbin_pad, nullptr, MV_ACT_NONE, out, h->cfg.n_mels, (int)nframes,
                                h->nbin, h->cfg.n_mels, 0, st);
     if (rc != MV_OK) return rc;
-    if (h->cfg.subtract_time_mean || lens_ratio != nullptr) {
+    if (h->cfg.subtract_time_mean || lens_ratio != nullptr || num_samples != nullptr) {
         MV_LAUNCH(mv::cmn_mask_kernel, ((unsigned)B, 1, 1), (256, 1, 1), 0, st, out, (int)T, h->cfg.n_mels, lens_ratio,
-                  h->cfg.subtract_time_mean);
+                  h->cfg.subtract_time_mean, rows);
         rc = mv::check_launch("cmn_mask_kernel");
     }
     return rc;
 }
-
-}  // extern "C"

@@ -15,6 +15,7 @@
 // The batch-wide maximum is a global dependency: it is a launch boundary, not a grid barrier, and it never leaves the device.
 #include <vector>
 
+#include "frontend_common.h"
 #include "kernels.h"
 #include "spectral.h"
 
@@ -27,10 +28,13 @@ constexpr size_t MFCC_LDS = 150 * 1024;   // dynamic LDS budget of mfcc_dct_kern
 
 __device__ __forceinline__ float mfcc_db(float x) { return 10.0f * log10f(fmaxf(x, 1e-10f)); }
 
-// rowmax[b] = max over T x n_mels of mfcc_db(mel).  max is exact, so the reduction order does not matter.
-__global__ __launch_bounds__(MFCC_THREADS) void mfcc_db_max_kernel(const float* mel, int64_t n, float* rowmax) {
+// rowmax[b] = max over the row's frames x n_mels of mfcc_db(mel): all T frames, or the row's own (variable-length form; -inf for a row
+// without frames).  max is exact, so the reduction order does not matter.
+__global__ __launch_bounds__(MFCC_THREADS) void mfcc_db_max_kernel(const float* mel, int T, int n_mels, RowLens rows, float* rowmax) {
     __shared__ float red[MFCC_THREADS / 64];
-    const float* p = mel + (int64_t)blockIdx.x * n;
+    const float* p = mel + (int64_t)blockIdx.x * T * n_mels;
+    int64_t Lb;
+    const int64_t n = (int64_t)row_frames(rows, blockIdx.x, 0, T, &Lb) * n_mels;
     float m = -INFINITY;
     for (int64_t i = threadIdx.x; i < n; i += MFCC_THREADS) m = fmaxf(m, mfcc_db(p[i]));
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
@@ -51,6 +55,7 @@ struct MfccArgs {
     float* out;              // [B, T, n_mfcc]
     int B, T, n_mels, n_mfcc, log_mels, cmn, tile_rows;
     float top_db;
+    RowLens rows;            // per-row lengths (variable-length form) or none
 };
 
 // One workgroup per utterance.  LDS: [DCT table if DCT_LDS][MFCC_FR][n_mels] dB rows, [tile_rows][n_mfcc] coefficients waiting for the
@@ -61,7 +66,11 @@ __global__ __launch_bounds__(MFCC_THREADS) void mfcc_dct_kernel(MfccArgs a) {
     __shared__ float part[4][64];
     __shared__ float mean[256];
     const int tid = threadIdx.x, b = blockIdx.x;
-    const int T = a.T, nm = a.n_mels, nc = a.n_mfcc;
+    const int nm = a.n_mels, nc = a.n_mfcc;
+    // T frames: the batch's, or this row's own (variable-length form: the chunks, the time mean and its summation order follow T alone;
+    // the output keeps a.T rows, zero behind T)
+    int64_t Lb;
+    const int T = row_frames(a.rows, b, 0, a.T, &Lb);
     float* base = reinterpret_cast<float*>(smem);
     const float* dct = a.dct;
     if constexpr (DCT_LDS) {
@@ -71,12 +80,13 @@ __global__ __launch_bounds__(MFCC_THREADS) void mfcc_dct_kernel(MfccArgs a) {
     }
     float* xs = base;                      // [MFCC_FR][n_mels]
     float* tile = xs + MFCC_FR * nm;       // [tile_rows][n_mfcc]
-    const float* mel = a.mel + (int64_t)b * T * nm;
-    float* orow = a.out + (int64_t)b * T * nc;
+    const float* mel = a.mel + (int64_t)b * a.T * nm;
+    float* orow = a.out + (int64_t)b * a.T * nc;
     float floor_db = -INFINITY;
     if (!a.log_mels) {
         float m = -INFINITY;
-        for (int i = 0; i < a.B; ++i) m = fmaxf(m, a.rowmax[i]);   // uniform: scalar loads
+        if (a.rows.num_samples != nullptr) m = a.rowmax[b];            // variable-length form: the row's own loudest value
+        else for (int i = 0; i < a.B; ++i) m = fmaxf(m, a.rowmax[i]);   // uniform: scalar loads
         floor_db = m - a.top_db;
     }
     for (int t0 = 0; t0 < T; t0 += MFCC_FR) {
@@ -110,12 +120,12 @@ __global__ __launch_bounds__(MFCC_THREADS) void mfcc_dct_kernel(MfccArgs a) {
             for (int t = ph; t < T; t += 4) s += raw(t, c);
         part[ph][tid & 63] = s;
         __syncthreads();
-        if (tid < 64 && c0 + tid < nc) mean[c0 + tid] = a.cmn ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)T : 0.0f;
+        if (tid < 64 && c0 + tid < nc) mean[c0 + tid] = a.cmn && T > 0 ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)T : 0.0f;
         __syncthreads();
     }
     int mask_len = T;
     if (a.lens_ratio != nullptr) mask_len = (int)rintf(a.lens_ratio[b] * (float)T);
-    for (int i = tid; i < T * nc; i += MFCC_THREADS) {
+    for (int i = tid; i < a.T * nc; i += MFCC_THREADS) {
         const int t = i / nc, c = i - t * nc;
         MV_AS_GLOBAL(float, orow)[i] = t < mask_len ? raw(t, c) - mean[c] : 0.0f;
     }
@@ -218,6 +228,13 @@ int mv_spectrogram_forward(const MvSpectrogram* h, const float* wav, int32_t B, 
     return mv_melspec_forward(h->core, wav, B, L, wav_stride, lens_ratio, out, workspace, workspace_bytes, stream);
 }
 
+int mv_spectrogram_forward_varlen(const MvSpectrogram* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                                  const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    MV_REQUIRE(h != nullptr, "mv_spectrogram_forward_varlen: null handle");
+    MV_REQUIRE(num_samples != nullptr, "mv_spectrogram_forward_varlen: null length array");
+    return mv_melspec_forward_varlen(h->core, wav, B, L, wav_stride, num_samples, out, workspace, workspace_bytes, stream);
+}
+
 void mv_mfcc_default_cfg(MvMfccCfg* cfg) {
     mv_melspec_default_cfg(&cfg->mel);
     cfg->mel.subtract_time_mean = 0;
@@ -298,10 +315,26 @@ size_t mv_mfcc_workspace_bytes(const MvMfcc* h, int32_t B, int64_t L) {
     return align256(mv_melspec_workspace_bytes(h->mel, B, L)) + mfcc_mel_bytes(h, B, T) + mfcc_max_bytes(B);
 }
 
+static int mfcc_forward_rows(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
+                             const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+
 int mv_mfcc_forward(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
                     const float* lens_ratio, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    return mfcc_forward_rows(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, workspace, workspace_bytes, stream);
+}
+
+int mv_mfcc_forward_varlen(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                           const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    MV_REQUIRE(num_samples != nullptr, "mv_mfcc_forward_varlen: null length array");
+    return mfcc_forward_rows(h, wav, B, L, wav_stride, nullptr, num_samples, out, workspace, workspace_bytes, stream);
+}
+
+// both forms: lens_ratio (batch form, or neither) or num_samples (variable-length form: own frames, time mean and dB floor per row)
+static int mfcc_forward_rows(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
+                             const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
     MV_REQUIRE(h != nullptr, "mv_mfcc_forward: null handle");
     MV_REQUIRE(B >= 0 && L >= 0 && wav_stride >= L, "mv_mfcc_forward: bad batch geometry");
+    MV_REQUIRE(lens_ratio == nullptr || num_samples == nullptr, "mv_mfcc_forward: lens_ratio and num_samples are mutually exclusive");
     int64_t T = 0;
     mv_melspec_num_frames(h->mel, L, &T);
     if (B == 0 || T == 0) return MV_OK;
@@ -313,12 +346,13 @@ int mv_mfcc_forward(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int
     char* ws = static_cast<char*>(workspace);
     float* mel = reinterpret_cast<float*>(ws + mel_ws);
     float* rowmax = reinterpret_cast<float*>(ws + mel_ws + mfcc_mel_bytes(h, B, T));
-    int rc = mv_melspec_forward(h->mel, wav, B, L, wav_stride, nullptr, mel, ws, mel_ws, stream);
+    int rc = mv::melspec_forward_rows(h->mel, wav, B, L, wav_stride, nullptr, num_samples, mel, ws, mel_ws, stream);
     if (rc != MV_OK) return rc;
+    const mv::RowLens row_lens = mv::melspec_row_lens(h->mel, num_samples, L);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nm = h->cfg.mel.n_mels, nc = h->cfg.n_mfcc;
     if (!h->cfg.log_mels) {
-        MV_LAUNCH(mv::mfcc_db_max_kernel, ((unsigned)B, 1, 1), (mv::MFCC_THREADS, 1, 1), 0, st, mel, (int64_t)T * nm, rowmax);
+        MV_LAUNCH(mv::mfcc_db_max_kernel, ((unsigned)B, 1, 1), (mv::MFCC_THREADS, 1, 1), 0, st, mel, (int)T, nm, row_lens, rowmax);
         rc = mv::check_launch("mfcc_db_max_kernel");
         if (rc != MV_OK) return rc;
     }
@@ -326,6 +360,7 @@ int mv_mfcc_forward(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int
     a.mel = mel; a.rowmax = rowmax; a.dct = h->d_dct; a.lens_ratio = lens_ratio; a.out = out;
     a.B = B; a.T = (int)T; a.n_mels = nm; a.n_mfcc = nc; a.log_mels = h->cfg.log_mels; a.cmn = h->cfg.subtract_time_mean ? 1 : 0;
     a.top_db = h->cfg.top_db;
+    a.rows = row_lens;
     const size_t fixed = ((h->dct_lds ? (size_t)((nm * nc + 3) & ~3) : 0) + (size_t)mv::MFCC_FR * nm) * sizeof(float);
     const int64_t rows = (int64_t)((mv::MFCC_LDS - fixed) / ((size_t)nc * sizeof(float)));
     a.tile_rows = (int)(rows < T ? rows : T);

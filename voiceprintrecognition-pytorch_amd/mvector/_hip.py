@@ -125,6 +125,7 @@ _SIGNATURES = {
     'mv_melspec_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
     'mv_melspec_workspace_bytes': (c_sz, [c_vp, c_i32, c_i64]),
     'mv_melspec_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_melspec_forward_varlen': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_ecapa_create': (c_i32, [ctypes.POINTER(MvEcapaCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_campp_create': (c_i32, [ctypes.POINTER(MvCamppCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
     'mv_tdnn_create': (c_i32, [ctypes.POINTER(MvTdnnCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
@@ -177,6 +178,7 @@ _SIGNATURES = {
     'mv_spectrogram_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
     'mv_spectrogram_workspace_bytes': (c_sz, [c_vp, c_i32, c_i64]),
     'mv_spectrogram_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_spectrogram_forward_varlen': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_mfcc_default_cfg': (None, [ctypes.POINTER(MvMfccCfg)]),
     'mv_mfcc_create': (c_i32, [ctypes.POINTER(MvMfccCfg), ctypes.POINTER(c_vp)]),
     'mv_mfcc_info': (c_i32, [c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32)]),
@@ -184,6 +186,7 @@ _SIGNATURES = {
     'mv_mfcc_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
     'mv_mfcc_workspace_bytes': (c_sz, [c_vp, c_i32, c_i64]),
     'mv_mfcc_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_mfcc_forward_varlen': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_fcm_conv3x3_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'mv_fcm_block_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
     'mv_fcm_block_c1_f16': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
@@ -356,6 +359,36 @@ class Fbank:
             pass
 
 
+def _stft_forward(handle, prefix, dim, wav, lens_ratio, num_samples):
+    """the forward of the MelSpec / Spectrogram / Mfcc handles: the caller's stream, a workspace per call; the batch form (``lens_ratio`` or
+    neither) or the variable-length form (``num_samples``), one native call either way"""
+    if lens_ratio is not None and num_samples is not None:
+        raise ValueError('lens_ratio and num_samples are mutually exclusive')
+    assert wav.dim() == 2 and wav.dtype == torch.float32
+    cdll = handle._cdll
+    if wav.stride(1) != 1:
+        wav = wav.contiguous()
+    B, L = wav.shape
+    T = handle.num_frames(L)
+    out = torch.empty((B, T, dim), dtype=torch.float32, device=wav.device)
+    if B == 0 or T == 0:
+        return out
+    nbytes = getattr(cdll, prefix + 'workspace_bytes')(handle._h, B, L)
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=wav.device)
+    if num_samples is not None:
+        num_samples = num_samples.to(device=wav.device, dtype=torch.int64).contiguous()
+        if num_samples.shape != (B,):
+            raise ValueError(f'num_samples must have shape ({B},), got {tuple(num_samples.shape)}')
+        check(getattr(cdll, prefix + 'forward_varlen')(handle._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
+                                                       ws.data_ptr(), nbytes, current_stream(wav)), cdll)
+        return out
+    if lens_ratio is not None:
+        lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
+    check(getattr(cdll, prefix + 'forward')(handle._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(),
+                                            ws.data_ptr(), nbytes, current_stream(wav)), cdll)
+    return out
+
+
 class MelSpec:
     """Handle of the MelSpectrogram + CMN + mask path (mv_melspec_*)."""
 
@@ -429,22 +462,10 @@ class MelSpec:
         check(self._cdll.mv_melspec_num_frames(self._h, num_samples, ctypes.byref(t)), self._cdll)
         return t.value
 
-    def __call__(self, wav, lens_ratio=None):
-        assert wav.dim() == 2 and wav.dtype == torch.float32
-        if wav.stride(1) != 1:
-            wav = wav.contiguous()
-        B, L = wav.shape
-        T = self.num_frames(L)
-        out = torch.empty((B, T, self.n_mels), dtype=torch.float32, device=wav.device)
-        if B == 0 or T == 0:
-            return out
-        if lens_ratio is not None:
-            lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
-        nbytes = self._cdll.mv_melspec_workspace_bytes(self._h, B, L)
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=wav.device)
-        check(self._cdll.mv_melspec_forward(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(),
-                                            ws.data_ptr(), nbytes, current_stream(wav)), self._cdll)
-        return out
+    def __call__(self, wav, lens_ratio=None, num_samples=None):
+        """wav [B, L] fp32 -> [B, T(L), n_mels].  ``lens_ratio``: the reference's batched semantics (mean over all T frames, then mask).
+        ``num_samples`` (int64 [B]): every row featurised on its own length, zero rows beyond it (mv_melspec_forward_varlen)."""
+        return _stft_forward(self, 'mv_melspec_', self.n_mels, wav, lens_ratio, num_samples)
 
     def __del__(self):
         try:
@@ -496,22 +517,9 @@ class _FrontEnd:
         check(getattr(self._cdll, self._prefix + 'num_frames')(self._h, num_samples, ctypes.byref(t)), self._cdll)
         return t.value
 
-    def __call__(self, wav, lens_ratio=None):
-        assert wav.dim() == 2 and wav.dtype == torch.float32
-        if wav.stride(1) != 1:
-            wav = wav.contiguous()
-        B, L = wav.shape
-        T = self.num_frames(L)
-        out = torch.empty((B, T, self.dim), dtype=torch.float32, device=wav.device)
-        if B == 0 or T == 0:
-            return out
-        if lens_ratio is not None:
-            lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
-        nbytes = getattr(self._cdll, self._prefix + 'workspace_bytes')(self._h, B, L)
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=wav.device)
-        check(getattr(self._cdll, self._prefix + 'forward')(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(),
-                                                            ws.data_ptr(), nbytes, current_stream(wav)), self._cdll)
-        return out
+    def __call__(self, wav, lens_ratio=None, num_samples=None):
+        """wav [B, L] fp32 -> [B, T(L), dim]; ``lens_ratio`` (batch form) or ``num_samples`` (int64 [B]: every row on its own length), as MelSpec"""
+        return _stft_forward(self, self._prefix, self.dim, wav, lens_ratio, num_samples)
 
     def __del__(self):
         try:

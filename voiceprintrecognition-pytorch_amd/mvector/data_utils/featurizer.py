@@ -6,7 +6,8 @@ Device rule
 * CUDA (ROCm) tensors: ``mv_fbank_forward`` / ``mv_melspec_forward`` / ``mv_spectrogram_forward`` / ``mv_mfcc_forward`` --
   waveform batch in HBM -> STFT (+ mel + log / dB + DCT) + time-mean subtraction + length mask, output on the same device.
   MFCC with ``log_mels=False`` floors the dB at (loudest value of the whole call) - 80, as torchaudio does on a batch: a row's
-  MFCC features depend on the other rows of the same call (``forward_varlen`` featurises each row alone).
+  MFCC features depend on the other rows of the same call (``forward_varlen`` featurises each row alone, through
+  ``mv_*_forward_varlen``: one call per batch for all four methods).
   There is no fallback on this path: a missing libmvector_hip.so raises.
 * CPU tensors (``use_gpu=False`` predictors, DataLoader worker processes after fork -- they must not touch
   HIP): a batched torch implementation of the same arithmetic (``_cpu_frontend``), as the reference itself
@@ -79,11 +80,13 @@ class AudioFeaturizer(nn.Module):
 
     def forward_varlen(self, waveforms, num_samples):
         """Zero-padded waveforms [B, L] + true lengths int64 [B] -> [B, T(L), feature_dim]: every row is featurised on its
-        own length (own frame count, own time mean) and rows beyond it are zero -- what the reference's evaluation path
-        gets from per-utterance featurisation + ``collate_fn`` padding, in one launch (Fbank only on the GPU)."""
+        own length (own frame count, own padding, own time mean, own MFCC dB floor) and rows beyond it are zero -- what the
+        reference's evaluation path gets from per-utterance featurisation + ``collate_fn`` padding.  CUDA tensors: one native
+        call per batch for every method (``mv_*_forward_varlen``), no per-row loop and no host synchronisation; a row too short
+        for the transform is all zero.  CPU tensors: the per-row loop."""
         if waveforms.dtype != torch.float32:
             waveforms = waveforms.float()
-        if waveforms.is_cuda and self._feature_method == 'Fbank':
+        if waveforms.is_cuda:
             with torch.cuda.device(waveforms.device):
                 return self._handle(waveforms.device)(waveforms, None, num_samples)
         T = self.forward(waveforms[:1]).size(1)

@@ -171,7 +171,7 @@ class MVectorPredictor:
     @torch.no_grad()
     def _predict_batch_pcm16(self, pcms, batch_size):
         """GPU fast path of predict_batch: same padding / length-ratio semantics (predict.py:244-255), int16 upload from
-        pinned memory, int16 -> float + dB normalisation + Fbank + CMN + mask + backbone on the device."""
+        pinned memory, int16 -> float + dB normalisation + front-end + CMN + mask + backbone on the device."""
         from mvector import _hip
         dataset = self.configs.dataset_conf.dataset
         lens = [p.shape[0] for p in pcms]
@@ -197,7 +197,7 @@ class MVectorPredictor:
     def predict_batch(self, audios_data, sample_rate=16000, batch_size=32):
         """预测一批音频的特征 -> np.ndarray [B, embd_dim] (row order = input order)"""
         self._last_batch_path = 'host'
-        if self.device.type == 'cuda' and self.configs.preprocess_conf.feature_method == 'Fbank':
+        if self.device.type == 'cuda':   # every feature method: wave_prepare and the ratio form of the front-end serve all four
             pcms = self._pcm16_batch(audios_data)
             if pcms is not None:
                 self._last_batch_path = 'pcm16'

@@ -3,10 +3,11 @@
 Only the evaluation of a trained model is on the MI355X embedding path; ``train`` / ``export`` / ``extract_features``
 raise.  What changed underneath ``evaluate`` (not in its contract):
 
-* GPU: utterances travel as zero-padded waveform batches; one variable-length Fbank launch per batch featurises every
-  row on its own length (``mv_fbank_forward_varlen`` = per-utterance featurisation + ``collate_fn`` zero padding of the
-  reference), the native backbone embeds the batch, and the trials x enrolment score matrix is one HIP cosine launch
-  instead of a Python loop over sklearn calls (trainer.py:452-461).
+* GPU: utterances travel as zero-padded waveform batches; one variable-length front-end call per batch featurises every
+  row on its own length (``mv_fbank_forward_varlen`` / ``mv_melspec_`` / ``mv_spectrogram_`` / ``mv_mfcc_forward_varlen`` =
+  per-utterance featurisation + ``collate_fn`` zero padding of the reference), the native backbone embeds the batch, and
+  the trials x enrolment score matrix is one HIP cosine launch instead of a Python loop over sklearn calls
+  (trainer.py:452-461).
 * CPU (``use_gpu=False``): the reference's flow -- per-item featurisation in the dataset, padded feature batches, torch
   graphs.
 The metrics (EER, minDCF, threshold) are computed on the host from the same flattened score / label arrays.
@@ -49,8 +50,9 @@ class MVectorTrainer(object):
         self.audio_featurizer = AudioFeaturizer(feature_method=self.configs.preprocess_conf.feature_method,
                                                 use_hf_model=self.configs.preprocess_conf.get('use_hf_model', False),
                                                 method_args=self.configs.preprocess_conf.get('method_args', {}))
-        # the GPU path batches raw waveforms; that is implemented for audio lists (not pre-extracted .npy features)
-        self._waveform_batches = use_gpu and self.configs.preprocess_conf.feature_method == 'Fbank'
+        # the GPU path batches raw waveforms (every feature method has a variable-length native call); that is implemented for audio
+        # lists (not pre-extracted .npy features)
+        self._waveform_batches = bool(use_gpu)
 
     # ---- out of scope -------------------------------------------------------------------------------------------
     def train(self, *args, **kwargs):
