@@ -269,6 +269,60 @@ int mv_mfcc_forward_varlen(const MvMfcc* h, const float* wav, int32_t B, int64_t
                            mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Front-end 5: a HuggingFace Wav2Vec2 / WavLM model's `extract_features` + time-mean subtraction + mask.  Replaces
+ * AudioFeaturizer(use_hf_model=True) (featurizer.py:20-39: AutoModel + AutoFeatureExtractor; forward :60-76 keeps
+ * outputs.extract_features alone) and featurizer.py:77-90.  What is evaluated: the processor's per-row z-score
+ * (x - mean) / sqrt(var + 1e-7) over the whole padded row (do_normalize), the convolutional feature encoder
+ * (feature_extractor.conv_layers.*: unpadded strided Conv1d -> GroupNorm on layer 0 ("group") or LayerNorm on every layer
+ * ("layer") -> exact GELU) and feature_projection.layer_norm; the transformer behind them, whose output the reference
+ * discards, is not.  Layer 0 runs in exact fp32; the other layers are fp16-operand convolutions on channel-last fp16
+ * activations (csrc/hfencoder.hip).  Output [B, T', conv_dim[last]] fp32.  Additive since ABI 5.
+ * ------------------------------------------------------------------------------------------------ */
+#define MV_HFENC_MAX_LAYERS 8
+#define MV_HF_NORM_GROUP 0
+#define MV_HF_NORM_LAYER 1
+#define MV_ACT_GELU 4 /* exact (erf) GELU: the only feat_extract_activation the encoder is built for (not an MvConv1dDesc activation) */
+typedef struct MvHfEncoderCfg {
+    int32_t num_layers;                         /* 7; 1 .. MV_HFENC_MAX_LAYERS */
+    int32_t conv_dim[MV_HFENC_MAX_LAYERS];      /* {512 x 7}: multiples of 64 up to 1024 (other widths are refused by name) */
+    int32_t conv_kernel[MV_HFENC_MAX_LAYERS];   /* {10,3,3,3,3,2,2}; layer 0: <= 16 */
+    int32_t conv_stride[MV_HFENC_MAX_LAYERS];   /* {5,2,2,2,2,2,2}; layer 0: <= 8 */
+    int32_t feat_extract_norm;                  /* MV_HF_NORM_GROUP | MV_HF_NORM_LAYER */
+    int32_t conv_bias;                          /* 0 | 1: conv_layers.i.conv.bias */
+    int32_t do_normalize;                       /* the processor's z-score of every waveform row */
+    int32_t activation;                         /* MV_ACT_GELU; anything else is refused */
+    float layer_norm_eps;                       /* of feature_projection.layer_norm (config.layer_norm_eps, 1e-5); the encoder's own norms use 1e-5 */
+    int32_t subtract_time_mean;                 /* 1: featurizer.py:79 */
+} MvHfEncoderCfg;
+
+typedef struct MvHfEncoder MvHfEncoder;
+
+void mv_hfenc_default_cfg(MvHfEncoderCfg* cfg);   /* the wav2vec2-base geometry */
+/* tensors: the fp32 state_dict of the Wav2Vec2Model / WavLMModel under its own key names (device pointers); read are
+ *   feature_extractor.conv_layers.{i}.conv.weight [conv_dim[i], conv_dim[i-1] (1 for i = 0), conv_kernel[i]], .conv.bias (conv_bias),
+ *   feature_extractor.conv_layers.{i}.layer_norm.weight / .bias (i = 0 in "group" mode, every i in "layer" mode),
+ *   feature_projection.layer_norm.weight / .bias.
+ * A missing one: MV_ERR_MISSING_TENSOR; a mis-shaped one: MV_ERR_INVALID_ARGUMENT; both name the tensor.  The handle owns the packed
+ * weights and no mutable state: forwards on different streams with different workspaces may run concurrently. */
+struct MvTensorRef;   /* declared with the backbones below */
+int mv_hfenc_create(const MvHfEncoderCfg* cfg, const struct MvTensorRef* tensors, int32_t num_tensors, MvHfEncoder** out);
+int mv_hfenc_destroy(MvHfEncoder* h);
+/* T' after every layer's n -> floor((n - k) / s) + 1; <= 0 when the waveform is shorter than the receptive field (400 samples) */
+int mv_hfenc_num_frames(const MvHfEncoder* h, int64_t num_samples, int64_t* num_frames);
+int mv_hfenc_workspace_bytes(const MvHfEncoder* h, int32_t B, int64_t L, size_t* bytes);
+/* wav [B, L] fp32 rows wav_stride apart; lens_ratio [B] fp32 or NULL (frames t >= round_half_even(ratio * T') are zeroed);
+ * out [B, T', conv_dim[last]] fp32 contiguous, 16-byte aligned; workspace: mv_hfenc_workspace_bytes(h, B, L) bytes, 16-byte aligned, untouched until the
+ * forward has run on `stream`.  A waveform shorter than the receptive field is refused (the reference's Conv1d raises there).  A row's
+ * bits depend on the row alone: not on B, the other rows or the stream. */
+int mv_hfenc_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
+                     float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+/* The same forward with HIP events between its stages (tools/bench_hf_frontend.py; a measurement hook like mv_profile_*: not thread-safe, WAITS for
+ * the forward, ONE DEVICE per process -- its events are created at the first call, on the device current then, and kept).  stage_ms_host: HOST array of num_stages = num_layers + 1 floats = milliseconds of layer 0 (with the z-score), of every further layer
+ * (conv + its GELU / LayerNorm pass) and of the tail (feature_projection.layer_norm + time mean + mask). */
+int mv_hfenc_forward_timed(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
+                           float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream, float* stage_ms_host, int32_t num_stages);
+
+/* ------------------------------------------------------------------------------------------------
  * Backbones.  A model handle is built from the reference-layout fp32 ``state_dict`` (same key names
  * and shapes as the reference modules, so ``model.pth`` loads unchanged: mvector/utils/checkpoint.py:
  * 11-51).  create() folds eval-mode BatchNorm into per-channel scale/shift, packs conv weights to the

@@ -48,6 +48,17 @@ class MvMfccCfg(ctypes.Structure):
                 ('subtract_time_mean', c_i32)]
 
 
+MV_HFENC_MAX_LAYERS = 8
+MV_HF_NORM_GROUP, MV_HF_NORM_LAYER = 0, 1
+MV_ACT_GELU = 4
+
+
+class MvHfEncoderCfg(ctypes.Structure):
+    _fields_ = [('num_layers', c_i32), ('conv_dim', c_i32 * MV_HFENC_MAX_LAYERS), ('conv_kernel', c_i32 * MV_HFENC_MAX_LAYERS),
+                ('conv_stride', c_i32 * MV_HFENC_MAX_LAYERS), ('feat_extract_norm', c_i32), ('conv_bias', c_i32), ('do_normalize', c_i32),
+                ('activation', c_i32), ('layer_norm_eps', c_f32), ('subtract_time_mean', c_i32)]
+
+
 class MvTensorRef(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char_p), ('data', c_vp), ('numel', c_i64)]
 
@@ -187,6 +198,13 @@ _SIGNATURES = {
     'mv_mfcc_workspace_bytes': (c_sz, [c_vp, c_i32, c_i64]),
     'mv_mfcc_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_mfcc_forward_varlen': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_hfenc_default_cfg': (None, [ctypes.POINTER(MvHfEncoderCfg)]),
+    'mv_hfenc_create': (c_i32, [ctypes.POINTER(MvHfEncoderCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
+    'mv_hfenc_destroy': (c_i32, [c_vp]),
+    'mv_hfenc_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
+    'mv_hfenc_workspace_bytes': (c_i32, [c_vp, c_i32, c_i64, ctypes.POINTER(c_sz)]),
+    'mv_hfenc_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_hfenc_forward_timed': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp, ctypes.POINTER(c_f32), c_i32]),
     'mv_fcm_conv3x3_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'mv_fcm_block_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
     'mv_fcm_block_c1_f16': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
@@ -597,6 +615,103 @@ class Mfcc(_FrontEnd):
         check(self._cdll.mv_mfcc_info(self._h, ctypes.byref(k), ctypes.byref(d)), self._cdll)
         return {'mel_kernel': {0: 'stft_power_kernel (dense DFT)', 1: 'melspec_tile_kernel', 2: 'melspec_pow2_kernel'}[k.value],
                 'dct_lds': bool(d.value)}
+
+
+def _tensor_refs(state_dict, device=None):
+    """(MvTensorRef array, the fp32 tensors it points to -- to be kept alive until create has read them) of a state_dict's floating-point entries"""
+    names, tensors = [], []
+    for k, v in state_dict.items():
+        if not torch.is_floating_point(v):
+            continue
+        t = v.detach().to(device=device if device is not None else v.device, dtype=torch.float32).contiguous()
+        names.append(k.encode())
+        tensors.append(t)
+    refs = (MvTensorRef * max(len(tensors), 1))()
+    for i, (n, t) in enumerate(zip(names, tensors)):
+        refs[i].name = n
+        refs[i].data = t.data_ptr()
+        refs[i].numel = t.numel()
+    return refs, tensors, names
+
+
+class HfEncoder:
+    """Handle of the HuggingFace (Wav2Vec2 / WavLM) front-end (mv_hfenc_*): the processor's z-score, the convolutional feature encoder and
+    feature_projection.layer_norm -- `extract_features` --, then AudioFeaturizer's time mean and mask.  Output [B, T', conv_dim[-1]].
+
+    ``cfg``: the model's config as a dict (``model.config.to_dict()``; read are conv_dim, conv_kernel, conv_stride, feat_extract_norm,
+    feat_extract_activation, conv_bias, layer_norm_eps) plus ``do_normalize`` (the processor's); ``state_dict``: the Wav2Vec2Model / WavLMModel's,
+    under its own key names, on the device the handle is to run on.  Needs no `transformers`."""
+
+    NORMS = {'group': MV_HF_NORM_GROUP, 'layer': MV_HF_NORM_LAYER}
+
+    def __init__(self, cfg, state_dict, subtract_time_mean=True, cdll=None, device=None):
+        self._cdll = cdll or lib()
+        c = MvHfEncoderCfg()
+        dims, kernels, strides = list(cfg['conv_dim']), list(cfg['conv_kernel']), list(cfg['conv_stride'])
+        if not (len(dims) == len(kernels) == len(strides)):
+            raise ValueError('conv_dim, conv_kernel and conv_stride must have one entry per layer')
+        if not 1 <= len(dims) <= MV_HFENC_MAX_LAYERS:
+            raise NotImplementedError(f'a feature encoder of {len(dims)} layers is not implemented by the HIP kernels (1 .. {MV_HFENC_MAX_LAYERS})')
+        act = cfg.get('feat_extract_activation', 'gelu')
+        if act != 'gelu':
+            raise NotImplementedError(f"feat_extract_activation {act!r} is not implemented by the HIP kernels (only 'gelu')")
+        norm = cfg.get('feat_extract_norm', 'group')
+        if norm not in self.NORMS:
+            raise ValueError(f"feat_extract_norm {norm!r} is not one of ['group', 'layer']")   # (the HF config's own check)
+        c.num_layers = len(dims)
+        for i, (d, k, s) in enumerate(zip(dims, kernels, strides)):
+            c.conv_dim[i], c.conv_kernel[i], c.conv_stride[i] = int(d), int(k), int(s)
+        c.feat_extract_norm = self.NORMS[norm]
+        c.conv_bias = 1 if cfg.get('conv_bias', False) else 0
+        c.do_normalize = 1 if cfg.get('do_normalize', True) else 0
+        c.activation = MV_ACT_GELU
+        c.layer_norm_eps = float(cfg.get('layer_norm_eps', 1e-5))
+        c.subtract_time_mean = 1 if subtract_time_mean else 0
+        self.dim = int(dims[-1])
+        self.num_layers = len(dims)
+        refs, tensors, _ = _tensor_refs(state_dict, device)
+        if tensors and tensors[0].is_cuda:
+            torch.cuda.current_stream(tensors[0].device).synchronize()
+        self._h = c_vp()
+        check(self._cdll.mv_hfenc_create(ctypes.byref(c), refs, len(tensors), ctypes.byref(self._h)), self._cdll)
+
+    def num_frames(self, num_samples):
+        t = c_i64()
+        check(self._cdll.mv_hfenc_num_frames(self._h, num_samples, ctypes.byref(t)), self._cdll)
+        return t.value
+
+    def __call__(self, wav, lens_ratio=None, stage_ms=None):
+        """wav [B, L] fp32 -> [B, T', dim] fp32 on the same device, the caller's stream, a workspace per call.  ``stage_ms``: a list that receives
+        the milliseconds of every layer and of the tail (mv_hfenc_forward_timed: waits for the forward; tools only)"""
+        assert wav.dim() == 2 and wav.dtype == torch.float32
+        if wav.stride(1) != 1:
+            wav = wav.contiguous()
+        B, L = wav.shape
+        T = self.num_frames(L)
+        if B == 0:
+            return torch.empty((0, max(T, 0), self.dim), dtype=torch.float32, device=wav.device)
+        need = c_sz()
+        check(self._cdll.mv_hfenc_workspace_bytes(self._h, B, L, ctypes.byref(need)), self._cdll)
+        ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=wav.device)
+        out = torch.empty((B, max(T, 1), self.dim), dtype=torch.float32, device=wav.device)   # (T <= 0: the forward refuses, with its message)
+        if lens_ratio is not None:
+            lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
+        if stage_ms is not None:
+            ms = (c_f32 * (self.num_layers + 1))()
+            check(self._cdll.mv_hfenc_forward_timed(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(), ws.data_ptr(),
+                                                    need.value, current_stream(wav), ms, self.num_layers + 1), self._cdll)
+            stage_ms[:] = list(ms)
+            return out
+        check(self._cdll.mv_hfenc_forward(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(), ws.data_ptr(), need.value,
+                                          current_stream(wav)), self._cdll)
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, '_h', None):
+                self._cdll.mv_hfenc_destroy(self._h)
+        except Exception:
+            pass
 
 
 class Model:

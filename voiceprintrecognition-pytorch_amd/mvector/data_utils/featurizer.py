@@ -3,6 +3,11 @@
 
 Device rule
 -----------
+* ``use_hf_model=True`` (``feature_method`` = a local folder or cached name of a HuggingFace Wav2Vec2 / WavLM model): the reference keeps
+  ``outputs.extract_features`` alone -- the processor's z-score, the convolutional feature encoder and ``feature_projection.layer_norm``.  CUDA
+  tensors run them in ``mv_hfenc_forward`` and stay on the device (the reference calls ``.numpy()`` and cannot take them at all); CPU tensors run
+  the HF module's own ``feature_extractor`` + ``feature_projection.layer_norm`` in torch.  The transformer behind them, whose output the reference
+  throws away, is never evaluated.
 * CUDA (ROCm) tensors: ``mv_fbank_forward`` / ``mv_melspec_forward`` / ``mv_spectrogram_forward`` / ``mv_mfcc_forward`` --
   waveform batch in HBM -> STFT (+ mel + log / dB + DCT) + time-mean subtraction + length mask, output on the same device.
   MFCC with ``log_mels=False`` floors the dB at (loudest value of the whole call) - 80, as torchaudio does on a batch: a row's
@@ -26,8 +31,9 @@ from mvector.utils.logger import logger
 class AudioFeaturizer(nn.Module):
     """音频特征器
 
-    :param feature_method: 所使用的预处理方法 (``Fbank`` / ``MelSpectrogram`` / ``Spectrogram`` / ``MFCC``)
-    :param use_hf_model: HuggingFace feature models are outside the accelerated path
+    :param feature_method: 所使用的预处理方法 (``Fbank`` / ``MelSpectrogram`` / ``Spectrogram`` / ``MFCC``), or with ``use_hf_model`` the
+        local folder / cached name of a HuggingFace ``wav2vec2`` or ``wavlm`` model
+    :param use_hf_model: 是否使用HF上的Wav2Vec2类似模型提取音频特征
     :param method_args: 预处理方法的参数
     """
 
@@ -36,14 +42,61 @@ class AudioFeaturizer(nn.Module):
         self._method_args = dict(method_args or {})
         self._feature_method = feature_method
         self.use_hf_model = use_hf_model
+        self._native = {}  # device index -> native handle (built lazily; never pickled)
         if use_hf_model:
-            raise NotImplementedError('use_hf_model=True (Wav2Vec2-style HuggingFace front-ends) is outside the '
-                                      'MI355X embedding path; use Fbank or MelSpectrogram')
+            self._load_hf_model(feature_method)
+            logger.info(f'使用模型【{feature_method}】提取特征')
+            return
         if feature_method not in ('Fbank', 'MelSpectrogram', 'Spectrogram', 'MFCC'):
             raise Exception(f'预处理方法 {self._feature_method} 不存在!')
         _cpu_frontend.validate_args(feature_method, self._method_args)
-        self._native = {}  # device index -> native handle (built lazily; never pickled)
         logger.info(f'使用【{feature_method}】提取特征')
+
+    HF_MODEL_TYPES = ('wav2vec2', 'wavlm')
+
+    def _load_hf_model(self, name):
+        """AutoModel / AutoFeatureExtractor as the reference loads them (featurizer.py:26-32); kept are the config, the processor's
+        do_normalize and the two modules behind ``extract_features`` -- the transformer is dropped"""
+        from transformers import AutoFeatureExtractor, AutoModel
+        processor = AutoFeatureExtractor.from_pretrained(name)
+        model = AutoModel.from_pretrained(name).eval()
+        cfg = model.config.to_dict()
+        if cfg.get('model_type') not in self.HF_MODEL_TYPES:
+            raise NotImplementedError(f"HuggingFace model_type {cfg.get('model_type')!r} is not implemented; the front-end is built for "
+                                      f'{list(self.HF_MODEL_TYPES)}')
+        if cfg.get('feat_extract_activation', 'gelu') != 'gelu':
+            raise NotImplementedError(f"feat_extract_activation {cfg.get('feat_extract_activation')!r} is not implemented (only 'gelu')")
+        keys = ('model_type', 'conv_dim', 'conv_kernel', 'conv_stride', 'feat_extract_norm', 'feat_extract_activation', 'conv_bias', 'layer_norm_eps')
+        self._hf_cfg = {k: cfg[k] for k in keys if k in cfg}
+        self._hf_cfg['do_normalize'] = bool(getattr(processor, 'do_normalize', True))
+        for p in model.parameters():
+            p.requires_grad_(False)
+        # (a tuple: not registered as sub-modules -- the featurizer has no parameters of its own, and .to(device) must not move what only CPU tensors use)
+        self._hf_modules = (model.feature_extractor, model.feature_projection.layer_norm)
+        self._hf_sd = {k: v.detach().float().cpu() for k, v in model.state_dict().items()
+                       if k.startswith('feature_extractor.') or k.startswith('feature_projection.layer_norm.')}
+
+    def _hf_min_samples(self):
+        """the encoder's receptive field: the shortest waveform that gives a frame (400 samples on the base geometry)"""
+        n = 1
+        for k, st in zip(reversed(self._hf_cfg['conv_kernel']), reversed(self._hf_cfg['conv_stride'])):
+            n = (n - 1) * st + k
+        return n
+
+    def _hf_cpu(self, waveforms, input_lens_ratio):
+        x = waveforms
+        if self._hf_cfg['do_normalize']:   # Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm over the whole (padded) row
+            x = (x - x.mean(1, keepdim=True)) / torch.sqrt(x.var(1, unbiased=False, keepdim=True) + 1e-7)
+        fe, ln = self._hf_modules
+        with torch.no_grad():
+            feature = ln(fe(x).transpose(1, 2))
+        feature = feature - feature.mean(1, keepdim=True)
+        if input_lens_ratio is not None:
+            T = feature.shape[1]
+            mask_lens = torch.round(input_lens_ratio.to(torch.float32) * T).long().unsqueeze(1)
+            mask = (torch.arange(T).repeat(feature.shape[0], 1) < mask_lens).unsqueeze(-1)
+            feature = torch.where(mask, feature, torch.zeros_like(feature))
+        return feature
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -56,7 +109,9 @@ class AudioFeaturizer(nn.Module):
         if h is None:
             from mvector import _hip
             with torch.cuda.device(key):
-                if self._feature_method == 'Fbank':
+                if self.use_hf_model:
+                    h = _hip.HfEncoder(self._hf_cfg, self._hf_sd, device=torch.device('cuda', key))
+                elif self._feature_method == 'Fbank':
                     h = _hip.Fbank(self._method_args)
                 elif self._feature_method == 'Spectrogram':
                     h = _hip.Spectrogram(self._method_args)
@@ -76,6 +131,8 @@ class AudioFeaturizer(nn.Module):
         if waveforms.is_cuda:
             with torch.cuda.device(waveforms.device):
                 return self._handle(waveforms.device)(waveforms, input_lens_ratio)
+        if self.use_hf_model:
+            return self._hf_cpu(waveforms, input_lens_ratio)
         return _cpu_frontend.featurize(waveforms, input_lens_ratio, self._feature_method, self._method_args)
 
     def forward_varlen(self, waveforms, num_samples):
@@ -83,22 +140,30 @@ class AudioFeaturizer(nn.Module):
         own length (own frame count, own padding, own time mean, own MFCC dB floor) and rows beyond it are zero -- what the
         reference's evaluation path gets from per-utterance featurisation + ``collate_fn`` padding.  CUDA tensors: one native
         call per batch for every method (``mv_*_forward_varlen``), no per-row loop and no host synchronisation; a row too short
-        for the transform is all zero.  CPU tensors: the per-row loop."""
+        for the transform is all zero.  CPU tensors: the per-row loop.  The HuggingFace front-end is the exception on CUDA: it has no
+        batched variable-length form, so its rows go through the device forward one by one (the lengths are read back to the host
+        once); a row below the encoder's receptive field (400 samples) is all zero there and on the CPU."""
         if waveforms.dtype != torch.float32:
             waveforms = waveforms.float()
-        if waveforms.is_cuda:
+        if waveforms.is_cuda and not self.use_hf_model:   # (the HF front-end has no batched variable-length form: the per-row loop, on the device)
             with torch.cuda.device(waveforms.device):
                 return self._handle(waveforms.device)(waveforms, None, num_samples)
         T = self.forward(waveforms[:1]).size(1)
         out = torch.zeros((waveforms.size(0), T, self.feature_dim), dtype=torch.float32, device=waveforms.device)
+        lens = [int(n) for n in torch.as_tensor(num_samples).tolist()]   # (one read-back for the whole batch)
+        min_len = self._hf_min_samples() if self.use_hf_model else 0
         for i in range(waveforms.size(0)):
-            n = int(num_samples[i])
+            n = min(max(lens[i], 0), waveforms.size(1))
+            if n < min_len:
+                continue   # no frame fits: an all-zero row, as the other front-ends leave it
             f = self.forward(waveforms[i, :n])
             out[i, :f.size(1)] = f[0]
         return out
 
     @property
     def feature_dim(self):
+        if self.use_hf_model:
+            return self._hf_cfg['conv_dim'][-1]   # what the reference's 1 s probe returns (featurizer.py:35-39): extract_features.shape[2]
         if self._feature_method == 'MelSpectrogram':
             return self._method_args.get('n_mels', 128)
         elif self._feature_method == 'Spectrogram':
