@@ -758,6 +758,35 @@ int mv_fcm_block_c1_f16(const float* feats, int32_t F, const void* c1a, const fl
 /* host -> host: w fp32 [32 maps][3 mel taps][3 time taps] (BatchNorm scale folded) -> out fp16 [2][64][8], the MFMA operand order of the kernel */
 int mv_fcm_c1_pack(const float* w, void* out);
 
+/* The dense layers of one CAM++ block (CAMDenseTDNNLayer, mvector/models/campplus.py:114-181), in place on a channel-last fp16 concat buffer
+ * x [B, T2, ldx]: layer l = 0 .. nlayers - 1 reads channels [0, c_in + 32 l) and writes channels [c_in + 32 l, c_in + 32 (l + 1)); growth 32,
+ * bottleneck 128.  Per layer
+ *   h = ReLU(BN2(W1 . ReLU(BN1(x)))),  ctx = mean_T(h) + mean over the frame's seg_len-frame segment (the last one over its true length),
+ *   y = conv_k3,dil(h, zero padding) * sigmoid(Wb . ReLU(Wa . ctx + ba) + bb).
+ * Parameters: host arrays of nlayers device pointers -- w1 = mv_conv1d_pack_weight of linear1.weight [128, cin, 1], wl the same of
+ * cam_layer.linear_local.weight [32, 128, 3]; bn1_s / bn1_t fp32 [cin], bn2_s / bn2_t fp32 [128] (eval BatchNorm folded to scale / shift);
+ * wa fp32 [64][128], ba [64], wb [32][64], bb [32].
+ * form: which of the library's launch forms runs.  MV_CAM_FORM_AUTO = the choice the CAM++ handle's forward makes (the same code): the block
+ * kernel for the whole block where it takes the geometry, else per layer the one-launch kernel, else the two-launch long form.  A pinned form
+ * that does not take the geometry returns MV_ERR_UNSUPPORTED with a message naming the form -- it never runs another one:
+ *   MV_CAM_FORM_BLOCK  all layers in one launch: T2 <= 160, c_in >= 128, nlayers <= 24, c_in + 32 nlayers <= 1056, dil 1..2, at most 2 segments
+ *   MV_CAM_FORM_LAYER  one launch per layer: T2 <= 160, cin <= 1984, dil 1..2, at most 2 segments
+ *   MV_CAM_FORM_LONG   two launches per layer over chunks of up to 160 frames: T2 > 160, cin <= 1984, dil 1..2, seg_len >= 80
+ * forms_used (optional, host, nlayers entries): the form each layer ran.  ldx % 8 == 0, ldx >= c_in + 32 nlayers; columns beyond that are not
+ * touched.  workspace: mv_cam_dense_block_workspace_bytes(B, T2, nlayers) bytes of device memory, 16-byte aligned (the long form's bottleneck rows
+ * and partial sums, the device copy of the layer table); the call allocates nothing.  The layer table is copied SYNCHRONOUSLY after a wait for
+ * `stream`: a layer-level entry point of the parity tests, not a hot-path call. */
+#define MV_CAM_FORM_AUTO 0
+#define MV_CAM_FORM_BLOCK 1
+#define MV_CAM_FORM_LAYER 2
+#define MV_CAM_FORM_LONG 3
+int mv_cam_dense_block_workspace_bytes(int32_t B, int32_t T2, int32_t nlayers, size_t* bytes);
+int mv_cam_dense_block_f16(void* x, int64_t ldx, int32_t B, int32_t T2, int32_t c_in, int32_t nlayers, const void* const* w1,
+                           const float* const* bn1_s, const float* const* bn1_t, const float* const* bn2_s, const float* const* bn2_t,
+                           const void* const* wl, const float* const* wa, const float* const* ba, const float* const* wb, const float* const* bb,
+                           int32_t dil, int32_t seg_len, int32_t form, int32_t* forms_used, void* workspace, size_t workspace_bytes,
+                           mv_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -1110,3 +1110,95 @@ def res2_chain_case(cdll, device, B=2, T=45, width=64, groups=8, k=3, dil=3, see
                                                  groups, k, dil, _stream(xd)), cdll)
             assert torch.equal(y1[0].cpu(), y[b].cpu()), (b, (y1[0].cpu().float() - y[b].cpu().float()).abs().max().item())
     return err
+
+
+# ---- CAM++ dense layers (mv_cam_dense_block_f16): cases and bars in tests/cam_cases.py, reference in tests/cam_ref.py ----
+CAM_SENTINEL = 7.0
+
+
+def cam_dense_params(cdll, device, layers):
+    """the per-layer tensors of a cam_cases.build() on the device, w1 / wl packed as the kernels read them"""
+    out = []
+    for p in layers:
+        d = {k: v.to(device).contiguous() for k, v in p.items()}
+        d['w1'] = pack_weight(cdll, p['w1'].unsqueeze(2).to(device))
+        d['wl'] = pack_weight(cdll, p['wl'].to(device))
+        out.append(d)
+    return out
+
+
+def cam_dense_launch(cdll, device, x0, params, c_in, nlayers, dil, seg_len, form, pad):
+    """one launch on a fresh buffer: inputs | NaN where the layers write | sentinel in the pitch columns -> (buffer on the CPU, forms used)"""
+    B, T2, _ = x0.shape
+    c_out = c_in + 32 * nlayers
+    buf = torch.full((B, T2, c_out + pad), CAM_SENTINEL, dtype=torch.float16)
+    buf[..., :c_in] = x0
+    buf[..., c_in:c_out] = float('nan')
+    xd = buf.to(device)
+    used = _hip.cam_dense_block(xd, c_in, params, dil, seg_len, form, cdll=cdll)
+    if device != 'cpu':
+        torch.cuda.synchronize()
+    return xd.cpu(), used
+
+
+def cam_dense_case(cdll, device, name, log=print):
+    """One case of tests/cam_cases.py: every layer of the launch against the fp64 layer on the device's OWN input channels, max-abs and mean-abs over
+    all layers' new channels within the case's bars; inputs bit-unchanged, pitch columns untouched, every output finite (the output region is NaN
+    before the launch: a layer that read a predecessor's channels before they landed shows up).  Returns (buffer, max-abs, mean-abs)."""
+    import cam_cases as cc
+    import cam_ref
+    c = cc.CASES[name]
+    x0, layers = cc.build(name)
+    params = cam_dense_params(cdll, device, layers)
+    got, used = cam_dense_launch(cdll, device, x0, params, c['c_in'], c['nlayers'], c['dil'], c['seg_len'], c['form'], c['pad'])
+    c_out = c['c_in'] + 32 * c['nlayers']
+    assert used == [cc.run_form(c)] * c['nlayers'], f'{name}: forms {used}'
+    assert torch.equal(got[..., :c['c_in']].view(torch.int16), x0.view(torch.int16)), f'{name}: the input channels changed'
+    assert bool((got[..., c_out:] == CAM_SENTINEL).all()), f'{name}: the launch wrote into the pitch columns'
+    new = cc.new_channels(got, c)
+    assert bool(torch.isfinite(new.float()).all()), f'{name}: {int((~torch.isfinite(new.float())).sum())} outputs are not finite (NaN: never written, or computed from channels that had not landed)'
+    ref, gates = cam_ref.teacher_forced(got, c['c_in'], layers, c['dil'], c['seg_len'], return_gates=True)
+    cc.check_gate_spread(gates, name)
+    mx, mean = cc.distances(new, ref)
+    bmx, bmean = cc.bars(name)
+    per_layer = (new.double() - ref).abs().reshape(-1, c['nlayers'], 32).amax((0, 2))
+    log(f'cam_dense {name}: form {cc.run_form(c)} max-abs {mx:.3e} (bar {bmx:.3e}, {mx / bmx:.2f}) mean-abs {mean:.3e} (bar {bmean:.3e}, {mean / bmean:.2f}) '
+        f'worst layer {int(per_layer.argmax())}')
+    assert mx <= bmx and mean <= bmean, f'{name}: max-abs {mx:.3e} (bar {bmx:.3e}), mean-abs {mean:.3e} (bar {bmean:.3e}), per layer {per_layer.tolist()}'
+    return got, mx, mean
+
+
+def cam_dense_batch_rows_case(cdll, device, form, T2, c_in, nlayers, dil, seg_len=100, B=5):
+    """row b of a B = 5 launch carries the same bits as the B = 1 launch on that row (one workgroup, or one column of workgroups, per utterance;
+    no summation crosses utterances)"""
+    import cam_cases as cc
+    name = f'rows_form{form}'
+    cc.CASES[name] = cc._case(form, T2, c_in, nlayers, dil, seg_len, B=B)
+    try:
+        x0, layers = cc.build(name)
+    finally:
+        del cc.CASES[name]
+    params = cam_dense_params(cdll, device, layers)
+    full, _ = cam_dense_launch(cdll, device, x0, params, c_in, nlayers, dil, seg_len, form, 8)
+    assert bool(torch.isfinite(full.float()).all())
+    for b in range(B):
+        one, _ = cam_dense_launch(cdll, device, x0[b:b + 1], params, c_in, nlayers, dil, seg_len, form, 8)
+        assert torch.equal(one[0].view(torch.int16), full[b].view(torch.int16)), (form, b, (one[0].float() - full[b].float()).abs().max().item())
+
+
+def cam_dense_refusal_case(cdll, device, form, T2, c_in, nlayers, dil, seg_len):
+    """a pinned form outside its predicate: MV_ERR_UNSUPPORTED with a message naming the form, the buffer untouched"""
+    import cam_cases as cc
+    name = 'refusal'
+    cc.CASES[name] = cc._case(form, T2, c_in, nlayers, dil, seg_len, B=1)
+    try:
+        x0, layers = cc.build(name)
+    finally:
+        del cc.CASES[name]
+    params = cam_dense_params(cdll, device, layers)
+    try:
+        got, _ = cam_dense_launch(cdll, device, x0, params, c_in, nlayers, dil, seg_len, form, 0)
+    except RuntimeError as e:
+        assert f'form {form}' in str(e) and f'(code {_hip.MV_ERR_UNSUPPORTED})' in str(e), str(e)
+        return str(e)
+    raise AssertionError(f'form {form} accepted T2 {T2}, c_in {c_in}, seg_len {seg_len}: {torch.isfinite(got.float()).all()}')

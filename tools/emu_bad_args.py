@@ -1,5 +1,6 @@
 """Bad arguments at the C ABI (no GPU): every field of MvConv1dDesc / MvConv2dsDesc of a VALID layer call -- and every pointer / integer
-argument of the positional entry points (linear, time statistics, ASP pooling, Res2Net chain, BN + ReLU rows, TSTP, wave preparation, cosine) -- is replaced, one at a
+argument of the positional entry points (linear, time statistics, ASP pooling, Res2Net chain, BN + ReLU rows, TSTP, wave preparation, cosine, the CAM++ dense
+block) -- is replaced, one at a
 time, by values a caller can get wrong -- a null pointer, 0, -1, a huge size, an enum out of range, a leading dimension smaller than the row --
 and the entry point is called on the emulator build.  The contract (include/mvector_hip.h): a call the library cannot run returns an error code
 and a message; it never crashes and never touches memory outside the caller's buffers.
@@ -106,12 +107,87 @@ class Tamper:
         return call
 
 
-def worker():
+def cam_dense_block_calls(cdll, log):
+    """mv_cam_dense_block_f16 / mv_cam_dense_block_workspace_bytes: one valid two-layer call (block kernel geometry), then one argument at a time made
+    wrong -- null pointers (the buffer, a parameter array, one layer's pointer inside an array, the workspace), nlayers 0 and 25, T2 0, a row pitch that
+    is no multiple of 8 or shorter than the block's channels, a form that does not exist, each pinned form outside its geometry, a short workspace"""
+    import torch
+    import layer_checks as lc
+    from mvector import _hip
+    # (the inputs are drawn here: the tool needs nothing of the tests beyond the weight packing that every entry point above uses)
+    n, c_in, T2, dil, seg_len = 2, 128, 17, 1, 100
+    c_out = c_in + 32 * n
+    g = torch.Generator().manual_seed(17)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    x0 = rn(1, T2, c_in).half()
+    params = []
+    for l in range(n):
+        cin = c_in + 32 * l
+        params.append(dict(w1=lc.pack_weight(cdll, rn(128, cin, 1) * (2.0 / cin) ** 0.5), bn1_s=1.0 + 0.1 * rn(cin), bn1_t=0.3 * rn(cin),
+                           bn2_s=1.0 + 0.1 * rn(128), bn2_t=0.3 * rn(128), wl=lc.pack_weight(cdll, rn(32, 128, 3) * (2.0 / 384) ** 0.5),
+                           wa=rn(64, 128) * 0.1, ba=0.2 * rn(64), wb=rn(32, 64) * 0.04, bb=0.3 * rn(32)))
+    nbytes = ctypes.c_size_t(0)
+    fn_ws = 'mv_cam_dense_block_workspace_bytes'
+    for label, args in (('bytes = NULL', (1, T2, n, None)), ('B = 0', (0, T2, n, ctypes.byref(nbytes))), ('T2 = 0', (1, 0, n, ctypes.byref(nbytes))),
+                        ('nlayers = 0', (1, T2, 0, ctypes.byref(nbytes))), ('nlayers = 25', (1, T2, 25, ctypes.byref(nbytes)))):
+        print(f'CALL {fn_ws} {label}', flush=True)
+        rc = getattr(cdll, fn_ws)(*args)
+        msg = cdll.mv_last_error().decode() if rc != 0 else ''
+        log.append((fn_ws, label, None, rc, msg))
+        print(f'  -> {"accepted" if rc == 0 else "rejected: " + msg[:120]}', flush=True)
+    _hip.check(cdll.mv_cam_dense_block_workspace_bytes(1, T2, n, ctypes.byref(nbytes)), cdll)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8)
+    arrays = {f: (ctypes.c_void_p * n)(*[L[f].data_ptr() for L in params]) for f in _hip.CAM_LAYER_FIELDS}
+
+    def call(label, **bad):
+        buf = torch.zeros(1, T2, c_out + 8, dtype=torch.float16)
+        buf[..., :c_in] = x0
+        a = dict(x=buf.data_ptr(), ldx=c_out + 8, B=1, T2=T2, c_in=c_in, nlayers=n, dil=dil, seg_len=seg_len, form=1, used=None,
+                 ws=ws.data_ptr(), ws_bytes=nbytes.value, **arrays)
+        a.update(bad)
+        print(f'CALL mv_cam_dense_block_f16 {label}', flush=True)
+        rc = cdll.mv_cam_dense_block_f16(a['x'], a['ldx'], a['B'], a['T2'], a['c_in'], a['nlayers'], *[a[f] for f in _hip.CAM_LAYER_FIELDS], a['dil'],
+                                         a['seg_len'], a['form'], a['used'], a['ws'], a['ws_bytes'], None)
+        msg = cdll.mv_last_error().decode() if rc != 0 else ''
+        if label != 'valid':
+            log.append(('mv_cam_dense_block_f16', label, None, rc, msg))
+        print(f'  -> {"accepted" if rc == 0 else "rejected: " + msg[:120]}', flush=True)
+        return rc
+
+    assert call('valid') == 0
+    call('x = NULL', x=None)
+    call('workspace = NULL', ws=None)
+    call('workspace one byte short', ws_bytes=nbytes.value - 1)
+    for f in _hip.CAM_LAYER_FIELDS:
+        call(f'{f} = NULL', **{f: None})
+        holed = (ctypes.c_void_p * n)(*[L[f].data_ptr() for L in params])
+        holed[n - 1] = None
+        call(f'{f}[{n - 1}] = NULL', **{f: holed})
+    for k, vals in (('nlayers', (0, 25, -1)), ('T2', (0, -1)), ('B', (0, -1)), ('ldx', (c_out + 4, c_out - 8, 0, -8)), ('c_in', (0, 100, -32)), ('dil', (0, -1)),
+                    ('seg_len', (0, -1)), ('form', (-1, 4))):
+        for v in vals:
+            call(f'{k} = {v}', **{k: v})
+    # each pinned form outside its geometry (the valid call is T2 = 17, c_in = 128, dil 1, seg_len 100)
+    call('form 1, dil = 3', form=1, dil=3)
+    call('form 1, seg_len = 5 (four segments)', form=1, seg_len=5)
+    call('form 2, dil = 3', form=2, dil=3)
+    call('form 3, T2 = 17', form=3)
+    call('form 0, dil = 3 (no fused form)', form=0, dil=3)
+
+
+def worker(only=''):
     import layer_checks as lc
     from mvector import _hip
     from emu_lib import emu_cdll
     cdll = emu_cdll()
     log = []
+    if only in ('', 'cam'):
+        cam_dense_block_calls(cdll, log)
+    if only == 'cam':
+        rej = sum(1 for e in log if e[3] != 0)
+        print(f'SUMMARY {len(log)} tampered calls: {rej} rejected, {len(log) - rej} accepted, 0 crashed', flush=True)
+        print('ACCEPTED ' + '; '.join(f'{e[0]}.{e[1]}' for e in log if e[3] == 0), flush=True)
+        return
     # one valid layer per entry point, small enough that an "accepted" variant costs little
     lc.conv1d_case(Tamper(cdll, 'mv_conv1d_forward', _hip.MvConv1dDesc, log), 'cpu', B=2, T=21, cin=24, cout=40, k=3, dil=2, with_x2=True, row_bias=True)
     lc.conv1d_case(Tamper(cdll, 'mv_conv1d_forward', _hip.MvConv1dDesc, log), 'cpu', B=5, T=90, cin=128, cout=256, k=1, dil=1, tile=256, stats=2)
@@ -137,20 +213,23 @@ def worker():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mode', default='plain', choices=['plain', 'asan', 'ubsan'])
+    ap.add_argument('--only', default='', choices=['', 'cam'], help='cam: the CAM++ dense-block entry points alone (what tests/test_cam_dense.py runs)')
     ap.add_argument('--worker', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.worker:
-        worker()
+        worker(args.only)
         return
     import emu_fuzz
     env = emu_fuzz.mode_env(args.mode)
     subprocess.check_call([sys.executable, os.path.join(ROOT, 'tests', 'emu', 'build_emu.py')], env={**env, 'LD_PRELOAD': ''}, stdout=subprocess.DEVNULL)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--worker'], env=env, cwd=ROOT, capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), '--worker', '--only', args.only], env=env, cwd=ROOT, capture_output=True, text=True)
     lines = r.stdout.splitlines()
     if r.returncode != 0 or not any(l.startswith('SUMMARY') for l in lines):
         calls = [l for l in lines if l.startswith('CALL')]
         print(f'{args.mode}: the process died (rc {r.returncode}) in: {calls[-1] if calls else "?"}')
         print('\n'.join(l for l in (r.stdout + r.stderr).splitlines() if 'ERROR' in l or ' #0 ' in l or ' #1 ' in l or 'located' in l or 'SUMMARY' in l))
+        if 'Traceback' in r.stderr:              # the worker itself raised: say where
+            print(r.stderr[-1500:])
         sys.exit(1)
     for l in lines:
         if l.startswith(('SUMMARY', 'ACCEPTED')):

@@ -51,6 +51,8 @@
 // (5) row sums as explicit v_add_f32_dpp chains (the SLP vectoriser had paired the additions into v_pk_add_f32, which has no DPP form).
 // Measured and NOT kept: the next layer's W1 stages requested at the start of the tail (-0.3 %), its context parameters behind the k = 3 phase
 // (requested behind the k = 3 phase instead: -2 %, 23 requests in one burst); the LDS form of the column sums (equal; removed).
+#include <functional>
+
 #include "kernels.h"
 
 namespace mv {
@@ -627,4 +629,122 @@ int cam_dense_block_launch(half_t* x, int64_t ldx, int B, int T2, const MvCamLay
     return check_launch("cam_dense_block_kernel");
 }
 
+// ---- one dense block with the launch form chosen or pinned: what CamppModel::forward runs (form 0) and what mv_cam_dense_block_f16 exposes ----
+// form 0 takes the forward's choice: the block kernel for the whole block where cam_dense_block_supported holds; otherwise, layer by layer, the
+// per-layer kernel, then the two-launch long form, then `fallback(layer)` (the model's five unfused launches; without one the geometry is refused).
+// A pinned form (1 block kernel, 2 per-layer kernel, 3 long form) whose predicate refuses the geometry is an error, never another form.
+// forms_used (optional, nlayers ints): the form each layer ran, 0 for the fallback.
+int cam_dense_block_run(half_t* x, int64_t ldx, int B, int T2, int c_in, const MvCamLayerDesc* layers_host, const MvCamLayerDesc* layers_dev, int nlayers,
+                        int bottleneck, int growth, int dil, int seg_len, int form, half_t* hws, float* hpart, int* forms_used,
+                        const std::function<int(int)>* fallback, hipStream_t stream) {
+    const int c_out = c_in + nlayers * growth;
+    const bool block_ok = cam_dense_block_supported(T2, c_in, c_out, bottleneck, growth, dil, seg_len);
+    if (form == MV_CAM_FORM_BLOCK && !block_ok)
+        return fail(MV_ERR_UNSUPPORTED, "cam_dense_block: form 1 (block kernel) does not take this geometry (T2 <= 160, c_in >= 128, <= 24 layers, c_out <= 1056, dil 1..2, <= 2 segments)");
+    if (form == MV_CAM_FORM_BLOCK || (form == MV_CAM_FORM_AUTO && block_ok)) {
+        const int rc = cam_dense_block_launch(x, ldx, B, T2, layers_dev, nlayers, dil, seg_len, stream);
+        if (rc != MV_OK) return rc;
+        for (int l = 0; forms_used != nullptr && l < nlayers; ++l) forms_used[l] = MV_CAM_FORM_BLOCK;
+        return MV_OK;
+    }
+    for (int l = 0; l < nlayers; ++l) {
+        const MvCamLayerDesc& L = layers_host[l];
+        const bool layer_ok = cam_dense_layer_supported(T2, L.cin, bottleneck, growth, dil, seg_len);
+        const bool long_ok = cam_dense_long_supported(T2, L.cin, bottleneck, growth, dil, seg_len);
+        if (form == MV_CAM_FORM_LAYER && !layer_ok)
+            return fail(MV_ERR_UNSUPPORTED, "cam_dense_block: form 2 (per-layer kernel) does not take this geometry (T2 <= 160, cin a multiple of 32 up to 1984, dil 1..2, <= 2 segments)");
+        if (form == MV_CAM_FORM_LONG && !long_ok)
+            return fail(MV_ERR_UNSUPPORTED, "cam_dense_block: form 3 (two-launch long form) does not take this geometry (T2 > 160, cin a multiple of 32 up to 1984, dil 1..2, seg_len >= 80)");
+        int rc, used;
+        // utterances of up to 160 strided frames (3.2 s): the whole layer is one launch with the bottleneck kept in LDS
+        if (form == MV_CAM_FORM_LAYER || (form == MV_CAM_FORM_AUTO && layer_ok)) {
+            rc = cam_dense_layer_launch(x, ldx, B, T2, L.cin, L.w1, L.bn1_s, L.bn1_t, L.bn2_s, L.bn2_t, L.wl, L.wa, L.ba, L.wb, L.bb, dil, seg_len, stream);
+            used = MV_CAM_FORM_LAYER;
+        } else if (form == MV_CAM_FORM_LONG || (form == MV_CAM_FORM_AUTO && long_ok)) {
+            // longer utterances: two launches per layer over chunks of 160 strided frames (camdense.hip, "long utterances")
+            rc = cam_dense_long_launch(x, ldx, B, T2, L.cin, L.w1, L.bn1_s, L.bn1_t, L.bn2_s, L.bn2_t, L.wl, L.wa, L.ba, L.wb, L.bb, dil, seg_len, hws, hpart, stream);
+            used = MV_CAM_FORM_LONG;
+        } else if (fallback != nullptr) {
+            rc = (*fallback)(l);   // every other geometry (bottleneck / growth widths the fused kernels are not built for)
+            used = MV_CAM_FORM_AUTO;
+        } else {
+            return fail(MV_ERR_UNSUPPORTED, "cam_dense_block: no fused form takes this geometry");
+        }
+        if (rc != MV_OK) return rc;
+        if (forms_used != nullptr) forms_used[l] = used;
+    }
+    return MV_OK;
+}
+
+namespace {
+struct CamBlockWs {
+    MvCamLayerDesc* descs;
+    half_t* hws;
+    float* hpart;
+    size_t bytes;
+};
+CamBlockWs cam_block_carve(void* base, int B, int T2) {
+    char* p = static_cast<char*>(base);
+    size_t off = 0;
+    auto take = [&](size_t n) {
+        off = (off + 255) & ~size_t(255);
+        char* q = p != nullptr ? p + off : nullptr;
+        off += n;
+        return q;
+    };
+    CamBlockWs w;
+    w.descs = reinterpret_cast<MvCamLayerDesc*>(take(CB_MAX_LAYERS * sizeof(MvCamLayerDesc)));
+    w.hws = reinterpret_cast<half_t*>(take((size_t)B * T2 * CB_BN * sizeof(half_t)));
+    w.hpart = reinterpret_cast<float*>(take((size_t)cam_dense_long_part_floats(B, T2) * sizeof(float)));
+    w.bytes = (off + 255) & ~size_t(255);
+    return w;
+}
+}  // namespace
+
 }  // namespace mv
+
+extern "C" {
+
+int mv_cam_dense_block_workspace_bytes(int32_t B, int32_t T2, int32_t nlayers, size_t* bytes) {
+    MV_REQUIRE(bytes != nullptr, "mv_cam_dense_block_workspace_bytes: null argument");
+    MV_REQUIRE(B > 0 && T2 > 0 && nlayers > 0 && nlayers <= mv::CB_MAX_LAYERS, "mv_cam_dense_block_workspace_bytes: bad geometry");
+    *bytes = mv::cam_block_carve(nullptr, B, T2).bytes;
+    return MV_OK;
+}
+
+int mv_cam_dense_block_f16(void* x, int64_t ldx, int32_t B, int32_t T2, int32_t c_in, int32_t nlayers, const void* const* w1,
+                           const float* const* bn1_s, const float* const* bn1_t, const float* const* bn2_s, const float* const* bn2_t,
+                           const void* const* wl, const float* const* wa, const float* const* ba, const float* const* wb, const float* const* bb,
+                           int32_t dil, int32_t seg_len, int32_t form, int32_t* forms_used, void* workspace, size_t workspace_bytes,
+                           mv_stream_t stream) {
+    using namespace mv;
+    MV_REQUIRE(x != nullptr && w1 != nullptr && bn1_s != nullptr && bn1_t != nullptr && bn2_s != nullptr && bn2_t != nullptr && wl != nullptr &&
+                   wa != nullptr && ba != nullptr && wb != nullptr && bb != nullptr && workspace != nullptr,
+               "mv_cam_dense_block_f16: null argument");
+    MV_REQUIRE(nlayers >= 1 && nlayers <= CB_MAX_LAYERS, "mv_cam_dense_block_f16: 1 to 24 layers");
+    MV_REQUIRE(B > 0 && T2 > 0 && c_in >= CB_G && c_in % CB_G == 0 && dil >= 1 && seg_len > 0, "mv_cam_dense_block_f16: bad geometry");
+    MV_REQUIRE(form >= MV_CAM_FORM_AUTO && form <= MV_CAM_FORM_LONG, "mv_cam_dense_block_f16: form is 0 (the model's choice), 1, 2 or 3");
+    const int64_t c_out = (int64_t)c_in + (int64_t)nlayers * CB_G;
+    MV_REQUIRE(ldx % 8 == 0 && ldx >= c_out, "mv_cam_dense_block_f16: a row holds c_in + 32 * nlayers channels in 16-byte aligned chunks");
+    MV_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "mv_cam_dense_block_f16: 16-byte aligned buffers");
+    const CamBlockWs ws = cam_block_carve(workspace, B, T2);
+    if (ws.bytes > workspace_bytes) return fail(MV_ERR_WORKSPACE, "mv_cam_dense_block_f16: workspace too small (mv_cam_dense_block_workspace_bytes)");
+    MvCamLayerDesc hd[CB_MAX_LAYERS];
+    for (int l = 0; l < nlayers; ++l) {
+        MV_REQUIRE(w1[l] != nullptr && bn1_s[l] != nullptr && bn1_t[l] != nullptr && bn2_s[l] != nullptr && bn2_t[l] != nullptr && wl[l] != nullptr &&
+                       wa[l] != nullptr && ba[l] != nullptr && wb[l] != nullptr && bb[l] != nullptr,
+                   "mv_cam_dense_block_f16: null layer parameter");
+        const int cin = c_in + l * CB_G;
+        hd[l] = MvCamLayerDesc{reinterpret_cast<const half_t*>(w1[l]), bn1_s[l], bn1_t[l], bn2_s[l], bn2_t[l], reinterpret_cast<const half_t*>(wl[l]),
+                               wa[l], ba[l], wb[l], bb[l], cin, conv1d_cin_pad(cin)};
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // the descriptor array travels with a SYNCHRONOUS copy behind a wait for the stream (an earlier call may still read the same workspace): this is a
+    // layer-level entry point of the tests, not a hot-path call
+    MV_HIP_OK(hipStreamSynchronize(st));
+    MV_HIP_OK(hipMemcpy(ws.descs, hd, (size_t)nlayers * sizeof(MvCamLayerDesc), hipMemcpyHostToDevice));
+    return cam_dense_block_run(reinterpret_cast<half_t*>(x), ldx, B, T2, c_in, hd, ws.descs, nlayers, CB_BN, CB_G, dil, seg_len, form, ws.hws, ws.hpart,
+                               forms_used, nullptr, st);
+}
+
+}  // extern "C"

@@ -29,6 +29,7 @@
 // MvCamppCfg.head_precision pins the head (measurements, tests, one numerics on every rank); mv_model_info reports the choice and the figures.
 #include <array>
 #include <cfloat>
+#include <functional>
 #include <memory>
 
 #include "kernels.h"
@@ -77,6 +78,7 @@ struct CamppModel : MvModelBase {
         float *tr_s, *tr_t;  // transit BN
         ConvLayer transit;
         MvCamLayerDesc* descs = nullptr;  // device array for cam_dense_block_kernel
+        std::vector<MvCamLayerDesc> hdescs;  // the same on the host: what the per-layer forms are launched from
     };
     Block blocks[3];
     float *out_s = nullptr, *out_t = nullptr;
@@ -229,7 +231,8 @@ struct CamppModel : MvModelBase {
                 L.bb = upload(t);
             }
             {   // the block's layers as one device array (camblock.hip)
-                std::vector<MvCamLayerDesc> hd(B.layers.size());
+                std::vector<MvCamLayerDesc>& hd = B.hdescs;
+                hd.resize(B.layers.size());
                 for (size_t li = 0; li < B.layers.size(); ++li) {
                     const DenseLayer& L = B.layers[li];
                     hd[li] = MvCamLayerDesc{L.lin1.w, L.bn1_s, L.bn1_t, L.bn2_s, L.bn2_t, L.local.w, L.wa, L.ba, L.wb, L.bb, L.cin, conv1d_cin_pad(L.cin)};
@@ -807,28 +810,12 @@ struct CamppModel : MvModelBase {
             half_t* X = s.xb[bi];
             const int64_t ld = Bk.c_out;
             // all layers of the block in one launch, the next layer's first operands requested under the current layer's tail (camblock.hip);
-            // geometries it does not take fall through to one launch per layer, long utterances to two, anything else to five
-            const bool block_kernel = cam_dense_block_supported(T2, Bk.c_in, Bk.c_out, bn_ch, G, Bk.dil, 100);
-            if (block_kernel) {
-                if ((rc = cam_dense_block_launch(X, ld, B, T2, Bk.descs, (int)Bk.layers.size(), Bk.dil, 100, st))) return rc;
-            }
-            for (const DenseLayer& L : Bk.layers) {
-                if (block_kernel) break;
-                // utterances of up to 160 strided frames (3.2 s): the whole layer is one launch with the bottleneck kept in LDS
-                if (cam_dense_layer_supported(T2, L.cin, bn_ch, G, Bk.dil, 100)) {
-                    if ((rc = cam_dense_layer_launch(X, ld, B, T2, L.cin, L.lin1.w, L.bn1_s, L.bn1_t, L.bn2_s, L.bn2_t, L.local.w, L.wa, L.ba,
-                                                     L.wb, L.bb, Bk.dil, 100, st)))
-                        return rc;
-                    continue;
-                }
-                // longer utterances: two launches per layer over chunks of 160 strided frames (camdense.hip, "long utterances")
-                if (cam_dense_long_supported(T2, L.cin, bn_ch, G, Bk.dil, 100)) {
-                    if ((rc = cam_dense_long_launch(X, ld, B, T2, L.cin, L.lin1.w, L.bn1_s, L.bn1_t, L.bn2_s, L.bn2_t, L.local.w, L.wa, L.ba, L.wb, L.bb,
-                                                    Bk.dil, 100, s.h, s.hpart, st)))
-                        return rc;
-                    continue;
-                }
-                // every other geometry (bottleneck / growth widths the fused kernels are not built for): five launches
+            // geometries it does not take fall through to one launch per layer, long utterances to two (cam_dense_block_run: the choice
+            // mv_cam_dense_block_f16 exposes as form 0), anything else to the five launches below
+            const std::function<int(int)> five_launches = [&](int li) -> int {
+                // every other geometry (bottleneck / growth widths the fused kernels are not built for)
+                const DenseLayer& L = Bk.layers[li];
+                int rc;
                 MvConv1dDesc d = conv_desc(L.lin1, X, ld, s.h, bn_ch, B, T2, T2);
                 d.in_scale = L.bn1_s;
                 d.in_shift = L.bn1_t;
@@ -849,8 +836,11 @@ struct CamppModel : MvModelBase {
                 d.dilation = Bk.dil;
                 d.pad = Bk.dil;
                 d.pad_mode = MV_PAD_ZERO;
-                if ((rc = conv1d_launch(d, st))) return rc;
-            }
+                return conv1d_launch(d, st);
+            };
+            if ((rc = cam_dense_block_run(X, ld, B, T2, Bk.c_in, Bk.hdescs.data(), Bk.descs, (int)Bk.layers.size(), bn_ch, G, Bk.dil, 100,
+                                          MV_CAM_FORM_AUTO, s.h, s.hpart, nullptr, &five_launches, st)))
+                return rc;
             // transit: BN + ReLU, then a 1x1 conv that halves the channels into the next block's buffer.  The pre-activation is written out once
             // (bn_relu_rows_kernel) and the conv runs on the direct global -> LDS path (ring kernel, 256 x 256 tiles) instead of transforming on
             // load through registers: 124 -> 83 us for the two 1024-channel blocks, 60 -> ~35 for the 512-channel one (r10d, r10i).

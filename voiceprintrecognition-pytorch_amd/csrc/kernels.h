@@ -1,5 +1,7 @@
 // Internal launch functions shared between the layer-level C ABI and the model forwards.
 #pragma once
+#include <functional>
+
 #include "common.h"
 
 namespace mv {
@@ -83,6 +85,11 @@ struct MvCamLayerDesc {
 bool cam_dense_block_supported(int T2, int c_in, int c_out, int bottleneck, int growth, int dil, int seg_len);
 int cam_dense_block_launch(half_t* x, int64_t ldx, int B, int T2, const MvCamLayerDesc* layers_dev, int nlayers, int dil, int seg_len,
                            hipStream_t stream);
+// one dense block with the launch form chosen (MV_CAM_FORM_AUTO: what the model's forward runs) or pinned; fallback(layer): the caller's unfused
+// launches for a layer no fused form takes (camblock.hip)
+int cam_dense_block_run(half_t* x, int64_t ldx, int B, int T2, int c_in, const MvCamLayerDesc* layers_host, const MvCamLayerDesc* layers_dev, int nlayers,
+                        int bottleneck, int growth, int dil, int seg_len, int form, half_t* hws, float* hpart, int* forms_used,
+                        const std::function<int(int)>* fallback, hipStream_t stream);
 int seg_mean_launch(const half_t* x, int64_t ld, int B, int T, int C, int seg_len, float* ctx, hipStream_t stream);
 int se_gate_residual_launch(const half_t* y, int64_t ldy, const float* gate, const half_t* res, int64_t ldr, half_t* out,
                             int64_t ldo, int B, int T, int C, hipStream_t stream);

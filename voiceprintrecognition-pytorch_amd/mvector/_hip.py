@@ -211,6 +211,9 @@ _SIGNATURES = {
     'mv_fcm_c1_pack': (c_i32, [c_vp, c_vp]),
     'mv_time_stats_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_f32, c_vp]),
     'mv_bn_relu_rows_f16': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp]),
+    'mv_cam_dense_block_workspace_bytes': (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
+    'mv_cam_dense_block_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32] + [ctypes.POINTER(c_vp)] * 10 +
+                               [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_vp, c_sz, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -847,3 +850,24 @@ def cosine(a, b, cdll=None):
         check(cdll.mv_cosine_f32(a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], out.data_ptr(),
                                  current_stream(a)), cdll)
     return out
+
+
+MV_ERR_UNSUPPORTED = -3
+CAM_FORM_AUTO, CAM_FORM_BLOCK, CAM_FORM_LAYER, CAM_FORM_LONG = 0, 1, 2, 3
+CAM_LAYER_FIELDS = ('w1', 'bn1_s', 'bn1_t', 'bn2_s', 'bn2_t', 'wl', 'wa', 'ba', 'wb', 'bb')
+
+
+def cam_dense_block(x, c_in, layers, dil, seg_len=100, form=CAM_FORM_AUTO, cdll=None):
+    """The dense layers of one CAM++ block in place on the fp16 concat buffer x [B, T2, ldx] (mv_cam_dense_block_f16).  layers: one dict per
+    layer with the tensors of CAM_LAYER_FIELDS (w1 / wl packed by mv_conv1d_pack_weight).  Returns the form each layer ran."""
+    cdll = cdll or lib()
+    B, T2, ldx = x.shape
+    n = len(layers)
+    nbytes = c_sz(0)
+    check(cdll.mv_cam_dense_block_workspace_bytes(B, T2, n, ctypes.byref(nbytes)), cdll)
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=x.device)
+    arrays = [(c_vp * n)(*[L[f].data_ptr() for L in layers]) for f in CAM_LAYER_FIELDS]
+    used = (c_i32 * n)()
+    check(cdll.mv_cam_dense_block_f16(x.data_ptr(), ldx, B, T2, c_in, n, *arrays, dil, seg_len, form, used, ws.data_ptr(), nbytes.value,
+                                      current_stream(x)), cdll)
+    return list(used)
