@@ -690,6 +690,35 @@ int mv_time_stats_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C
 int mv_bn_relu_rows_f16(const void* x, int64_t ldx, const float* scale, const float* shift, void* y, int64_t ldy, int64_t n_rows,
                         int32_t C, mv_stream_t stream);
 
+/* The time reductions and element-wise row passes between the GEMMs of the backbones, one entry point per launcher of the model forwards (added
+ * within ABI 5: layer-level entry points of the parity tests).  fp16 rows are channel-last and 16-byte aligned (pointer and pitch) unless noted; a call
+ * a launcher cannot run returns MV_ERR_INVALID_ARGUMENT and launches nothing.  A NaN input gives a NaN output in every one of them; values beyond
+ * the fp16 range saturate at +-65504.
+ *   mv_time_stats_ex_f16     mv_time_stats_f16 with every argument of the launcher: the output pitch ld_out >= C (CAM++ StatsPool writes mean | std into
+ *                            one [B, 2C] row: std = mean + C, ld_out = 2C) and the optional pre-activation v = relu(x * in_scale[c] + in_shift[c])
+ *                            (both NULL: none).  x needs ld % 8 == 0 only; a C that is no multiple of 8 takes scalar loads in its last lane.
+ *   mv_seg_mean_f16          ctx[b, s, c] = mean_t x[b, t, c] + mean over segment s of seg_len frames (the last one over its true length), fp32
+ *                            [B, ceil(T / seg_len), C]; C % 8 == 0.
+ *   mv_se_gate_residual_f16  out[n, c] = fp16(gate[b(n), c] * y[n, c] + res[n, c]) over n = b * T + t; gate fp32 [B, C]; out and res may be column
+ *                            slices of one buffer as long as they do not overlap; C % 8 == 0.
+ *   mv_asp_hidden_act_f16    zh[b, t, a] = fp16(tanh(relu(zh[b, t, a] + row_bias[b, a]) * scale[a] + shift[a])) in place on [B * T, A], A % 8 == 0.
+ *   mv_cast_pad_f16          dst[b, t', 0:F] = fp16(src[b, reflect(t' - pad), 0:F]) for t' in [0, T + 2 pad), columns F..ldd-1 zero; src fp32
+ *                            [B, T, F] (16-byte aligned when ldd == F, which needs F % 8 == 0; any F and 4-byte alignment when ldd = round_up(F, 8)).
+ *   mv_cast_rows_f16         dst[n, 0:C] = fp16(src[n, 0:C]), columns C..ldd-1 zero; src fp32 at pitch lds >= C, no alignment beyond the element's.
+ *   mv_copy_slice_f16        dst[n, 0:C] = src[n, 0:C] between fp16 rows of different pitch; C % 8 == 0.
+ *   mv_pad_rows_f32          dst[n, 0:F] = src[n, 0:F] (fp32 rows of width F, exact copy), columns F..ldd-1 zero; ldd % 4 == 0, dst 16-byte aligned. */
+int mv_time_stats_ex_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C, float* mean, float* std, int64_t ld_out, int32_t unbiased,
+                         float clamp_eps, const float* in_scale, const float* in_shift, mv_stream_t stream);
+int mv_seg_mean_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C, int32_t seg_len, float* ctx, mv_stream_t stream);
+int mv_se_gate_residual_f16(const void* y, int64_t ldy, const float* gate, const void* res, int64_t ldr, void* out, int64_t ldo, int32_t B,
+                            int32_t T, int32_t C, mv_stream_t stream);
+int mv_asp_hidden_act_f16(void* zh, const float* row_bias, const float* scale, const float* shift, int32_t B, int32_t T, int32_t A,
+                          mv_stream_t stream);
+int mv_cast_pad_f16(const float* src, void* dst, int32_t B, int32_t T, int32_t F, int64_t ldd, int32_t pad, mv_stream_t stream);
+int mv_cast_rows_f16(const float* src, int64_t lds, void* dst, int64_t ldd, int64_t n_rows, int32_t C, mv_stream_t stream);
+int mv_copy_slice_f16(const void* src, int64_t lds, void* dst, int64_t ldd, int32_t C, int64_t n_rows, mv_stream_t stream);
+int mv_pad_rows_f32(const float* src, int32_t F, float* dst, int64_t ldd, int64_t n_rows, mv_stream_t stream);
+
 /* Per-kernel-class timing with HIP events recorded on the launch stream (used by bench.py for its roofline legs; off by
  * default, not thread-safe).  work = algorithmic FLOPs (MV_PROF_CONV1D: 2*B*T_out*cin*cout*k per launch) or algorithmic
  * bytes (MV_PROF_FBANK: B*(4*L + 4*T*num_mel_bins) per launch).  mv_profile_read waits for the recorded launches. */

@@ -1202,3 +1202,549 @@ def cam_dense_refusal_case(cdll, device, form, T2, c_in, nlayers, dil, seg_len):
         assert f'form {form}' in str(e) and f'(code {_hip.MV_ERR_UNSUPPORTED})' in str(e), str(e)
         return str(e)
     raise AssertionError(f'form {form} accepted T2 {T2}, c_in {c_in}, seg_len {seg_len}: {torch.isfinite(got.float()).all()}')
+
+
+# ------------------------------------------------------------------------------------------------ csrc/pool.hip: reductions and row passes, per kernel
+# One case function per launcher, the same for the emulator (tests/test_pool_rows.py) and the device (tests/test_gpu_pool_rows.py).  Every case:
+# an fp64 reference from the fp16-rounded operands the kernel sees; pitch columns (and a guard behind contiguous buffers) filled with a sentinel that
+# must come back bit-unchanged; inputs bit-unchanged; the output region NaN before the call, so an element nobody wrote shows up.
+
+POOL_SENTINEL = 7.0
+U32 = 2.0 ** -24        # unit roundoff of fp32 (round to nearest)
+
+
+def _gamma(m):
+    """the standard bound of m consecutive fp32 roundings"""
+    return m * U32 / (1.0 - m * U32)
+
+
+def _bits(t):
+    t = t.detach().cpu().contiguous()
+    return t.view({2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def _same_bits(a, b):
+    return torch.equal(_bits(a), _bits(b))
+
+
+def _dev_copy(t, device):
+    """a device copy whose storage is the test's own (on the CPU `.to` would alias the original and hide a kernel that writes its input)"""
+    return t.clone().to(device)
+
+
+def _raises(fn, cdll):
+    """the message of a refused call (the launcher returned an error code)"""
+    rc = fn()
+    assert rc != 0, 'the call was accepted'
+    return cdll.mv_last_error().decode(errors='replace')
+
+
+def time_stats_data(B, T, C, ld, seed=0):
+    """fp16 rows [B, T, ld], drawn utterance by utterance (row b is the same whatever B is); channel 3 constant, sentinel in the pitch columns"""
+    x = torch.empty(B, T, ld, dtype=torch.float16)
+    for b in range(B):
+        x[b] = (torch.randn(T, ld, generator=torch.Generator().manual_seed(1000 + 7919 * seed + b)) * 2 + 0.5).half()
+    x[:, :, 3] = 1.25
+    x[..., C:] = POOL_SENTINEL
+    return x
+
+
+def time_stats_launch(cdll, device, x, C, want_std=True, unbiased=0, eps=1e-12, pre=None, out_pad=0, joint=False):
+    """mv_time_stats_ex_f16 on x (fp16 [B, T, ld], CPU).  joint: mean | std in ONE row of pitch 2C + out_pad, std = mean + C (CAM++ StatsPool);
+    else two buffers of pitch C + out_pad.  Checks inputs, pitch columns and that every output was written; returns (mean, std) [B, C] on the CPU."""
+    B, T, ld = x.shape
+    xd = _dev_copy(x, device)
+    sc = sh = None
+    if pre is not None:
+        sc, sh = _dev_copy(pre[0], device), _dev_copy(pre[1], device)
+    if joint:
+        ld_out = 2 * C + out_pad
+        out = torch.full((B, ld_out), float('nan'), device=device)
+        out[:, 2 * C:] = POOL_SENTINEL
+        mean_ptr, std_ptr = out.data_ptr(), out.data_ptr() + 4 * C
+        assert want_std
+    else:
+        ld_out = C + out_pad
+        out = torch.full((2, B, ld_out), float('nan'), device=device)
+        out[:, :, C:] = POOL_SENTINEL
+        mean_ptr, std_ptr = out[0].data_ptr(), (out[1].data_ptr() if want_std else None)
+    _hip.check(cdll.mv_time_stats_ex_f16(xd.data_ptr(), ld, B, T, C, mean_ptr, std_ptr, ld_out, unbiased, eps, sc.data_ptr() if pre else None,
+                                         sh.data_ptr() if pre else None, _stream(xd)), cdll)
+    o = out.cpu()
+    assert _same_bits(xd, x), 'time_stats wrote its input'
+    if pre is not None:
+        assert _same_bits(sc, pre[0]) and _same_bits(sh, pre[1])
+    if joint:
+        assert bool((o[:, 2 * C:] == POOL_SENTINEL).all()), 'time_stats wrote behind mean | std'
+        return o[:, :C], o[:, C:2 * C]
+    assert bool((o[:, :, C:] == POOL_SENTINEL).all()), 'time_stats wrote the pitch columns of its output'
+    if not want_std:
+        assert bool(torch.isnan(o[1, :, :C]).all()), 'std = NULL, and the buffer beside the mean was written'
+        return o[0, :, :C], None
+    return o[0, :, :C], o[1, :, :C]
+
+
+def time_stats_check(x, C, mean, std, unbiased=0, eps=1e-12, pre=None, log=print, tag=''):
+    """mean / std of time_stats_kernel against fp64, per element, under bars derived from the kernel's own summation order.
+
+    The kernel takes the moments about k = v[b, 0, c]:  z1 = sum_t (v_t - k),  z2 = sum_t (v_t - k)^2,  mean = k + z1 / T,
+    var = max(z2 - z1^2 / T, 0) / (T or T - 1), clamped from below, std = sqrt(var).  A lane adds its rows t_first, t_first + 16, ... in one chain of
+    n = ceil(T / 16) fp32 additions; two shuffles add the four row groups of a wave, three additions the four LDS partials of the waves: a term passes
+    through at most n + 5 additions, after the one rounding of d = v_t - k itself (two fp16 values do not always differ by an fp32 number).  With
+    u = 2^-24 and gamma_m = m u / (1 - m u), S1 = sum |v_t - k| and S2 = sum (v_t - k)^2 taken from the fp64 data:
+        |z1 - Z1| <= gamma_(n+6) S1 =: e1         |z2 - Z2| <= gamma_(n+7) S2 =: e2      (the square of a rounded d, then its chain)
+        mean:  the division z1 / T rounds once more (gamma_(n+7) S1 / T in all), the final addition rounds the result: u |mean|
+        m2 = z2 - z1^2 / T:  e2 + (2 |Z1| e1 + e1^2) / T + 2 u Z1^2 / T (product, division) + u S2 (the subtraction: |m2| <= S2)
+        var:   that / denom, + 4 u var for the division, the clamp's operands and the square root (std^2 is compared: sqrt amplifies near zero)
+    The pre-activation v = relu(x * scale + shift) is an fp32 value itself: eps_t = u (|x scale| + |x scale + shift|) (product and sum; fused, less)
+    enters e1 as sum eps_t and e2 as sum 2 |v_t - k| eps_t; k is recomputed by the same operations, so its own error cancels.
+    Bars = 2 x these bounds (the factor tests/cam_cases.py gives its bars).  max(., 0) and the clamp are contractions: they need no term.
+    A channel with a NaN frame must come out NaN (mean and std), and no other may."""
+    B, T, ld = x.shape
+    xd = x.double()[..., :C]
+    nanch = torch.isnan(xd).any(1)
+    xd = torch.nan_to_num(xd, nan=0.0)
+    if pre is not None:
+        s64, t64 = pre[0].double(), pre[1].double()
+        v = torch.relu(xd * s64 + t64)
+        ev = U32 * ((xd * s64).abs() + (xd * s64 + t64).abs())
+    else:
+        v, ev = xd, torch.zeros_like(xd)
+    d = v - v[:, :1]
+    S1, Z1, S2 = d.abs().sum(1), d.sum(1), (d * d).sum(1)
+    n = (T + 15) // 16
+    mean_ref = v.mean(1)
+    bar_mean = 2 * (_gamma(n + 7) * S1 / T + ev.sum(1) / T + U32 * mean_ref.abs())
+    assert torch.equal(torch.isnan(mean), nanch), f'time_stats {tag}: the NaN means are not those of the channels with a NaN frame'
+    err = (mean.double() - mean_ref).abs()
+    ok = (err <= bar_mean) | nanch
+    ratio = (err / bar_mean.clamp_min(1e-300))[~nanch].max().item()
+    assert bool(ok.all()), f'time_stats {tag}: mean misses its bar: err {err[~ok].max().item():.3e}, ratio {ratio:.3f} at {torch.nonzero(~ok)[0].tolist()}'
+    r2 = float('nan')
+    if std is not None:
+        denom = T - 1 if unbiased else T
+        var_ref = ((v - mean_ref.unsqueeze(1)) ** 2).sum(1) / denom
+        eps32 = float(np.float32(eps))
+        if eps > 0:
+            var_ref = var_ref.clamp_min(eps32)
+        e1 = _gamma(n + 6) * S1 + ev.sum(1)
+        e2 = _gamma(n + 7) * S2 + (2 * d.abs() * ev).sum(1)
+        em2 = e2 + (2 * Z1.abs() * e1 + e1 * e1) / T + 2 * U32 * Z1 * Z1 / T + U32 * S2
+        bar_var = 2 * (em2 / denom + 4 * U32 * var_ref)
+        assert torch.equal(torch.isnan(std), nanch), f'time_stats {tag}: the NaN stds are not those of the channels with a NaN frame'
+        errv = (std.double() ** 2 - var_ref).abs()
+        okv = (errv <= bar_var) | nanch
+        r2 = (errv / bar_var.clamp_min(1e-300))[~nanch].max().item()
+        assert bool(okv.all()), f'time_stats {tag}: std^2 misses its bar: err {errv[~okv].max().item():.3e}, ratio {r2:.3f} at {torch.nonzero(~okv)[0].tolist()}'
+        # a constant channel: d = 0 in every frame, the variance is exactly zero -> exactly the clamp
+        const = (d == 0).all(1) & ~nanch
+        want = float(np.sqrt(np.float32(eps))) if eps > 0 else 0.0
+        assert bool((std[const] == want).all()), f'time_stats {tag}: a constant channel does not give exactly sqrt(clamp_eps)'
+    if pre is None:
+        assert bool(((mean[:, 3] == 1.25) | nanch[:, 3]).all())
+    log(f'time_stats {tag}: B={B} T={T} C={C} mean err/bar {ratio:.3f}, std^2 err/bar {r2:.3f}')
+    return ratio, r2
+
+
+def time_stats_ex_case(cdll, device, B=2, T=49, C=264, ld=272, want_std=True, unbiased=0, eps=1e-12, seed=0, log=print):
+    """one call (B small: the <PIPE> form) at a (T, C) edge"""
+    x = time_stats_data(B, T, C, ld, seed)
+    mean, std = time_stats_launch(cdll, device, x, C, want_std, unbiased, eps)
+    return time_stats_check(x, C, mean, std, unbiased, eps, log=log, tag=f'T{T}_C{C}')
+
+
+def time_stats_forms_case(cdll, device, T=33, C=136, ld=144, B_big=1025, log=print):
+    """The three instantiations on the same rows: the general form (ceil(C / 128) * B_big > 1024 workgroups, std requested), <LEAN> (the same call with
+    std = NULL) and <PIPE> (the first two utterances alone), each against fp64 -- and the mean of a row bit-identical across the three, as pool.hip
+    promises ("same additions in the same order: the same mean").  Three channels of the large calls hold a NaN frame (utterances the <PIPE> call
+    does not see): they come out NaN in both large-grid forms, every other channel meets its fp64 bar."""
+    assert (C + 127) // 128 * B_big > 1024
+    x = time_stats_data(B_big, T, C, ld, seed=7)
+    x[7, 0, 9] = x[B_big // 2, T // 2, 3] = x[B_big - 1, T - 1, C - 1] = float('nan')
+    m_gen, s_gen = time_stats_launch(cdll, device, x, C, True)
+    m_lean, _ = time_stats_launch(cdll, device, x, C, False)
+    m_pipe, s_pipe = time_stats_launch(cdll, device, x[:2].clone(), C, True)
+    time_stats_check(x, C, m_gen, s_gen, log=log, tag='general')
+    time_stats_check(x, C, m_lean, None, log=log, tag='lean')
+    time_stats_check(x[:2], C, m_pipe, s_pipe, log=log, tag='pipe')
+    assert _same_bits(m_gen, m_lean), 'the LEAN mean differs from the general form\'s'
+    assert _same_bits(m_gen[:2], m_pipe), 'the PIPE mean differs from the general form\'s on the same rows'
+
+
+def time_stats_preact_case(cdll, device, B=2, T=49, C=264, ld=272, out_pad=0, log=print):
+    """the CAM++ StatsPool call: pre-activation relu(x * scale + shift) with scales of both signs, unbiased std without a clamp, mean | std in one row
+    of pitch 2C (+ out_pad columns that keep their sentinel).  Channel 5 is zeroed by the ReLU in every frame: mean and variance exactly 0."""
+    x = time_stats_data(B, T, C, ld, seed=3)
+    g = torch.Generator().manual_seed(11)
+    sc = torch.randn(C, generator=g) * 1.5
+    sc[::2] = sc[::2].abs() + 0.1
+    sc[1::2] = -sc[1::2].abs() - 0.1
+    sh = torch.randn(C, generator=g)
+    sc[5], sh[5] = 1.0, -1000.0
+    mean, std = time_stats_launch(cdll, device, x, C, True, 1, 0.0, pre=(sc, sh), out_pad=out_pad, joint=True)
+    assert bool((mean[:, 5] == 0).all()) and bool((std[:, 5] == 0).all()), 'a channel the ReLU zeroes in every frame must have mean and variance exactly 0'
+    return time_stats_check(x, C, mean, std, 1, 0.0, pre=(sc, sh), log=log, tag=f'preact_pad{out_pad}')
+
+
+def time_stats_nan_case(cdll, device, B=2, T=49, C=264, ld=272, pre=False, B_big=0):
+    """a NaN frame makes that channel's mean and std NaN; every other output has the bits it has without the NaN.  B_big: the general and LEAN forms"""
+    B = B_big or B
+    x = time_stats_data(B, T, C, ld, seed=5)
+    p = None
+    if pre:
+        g = torch.Generator().manual_seed(12)
+        p = (torch.randn(C, generator=g), torch.randn(C, generator=g))
+    xn = x.clone()
+    hits = [(0, 0, 9), (B - 1, T - 1, C - 1), (B - 1, T // 2, 3)]      # the first frame (k itself), the last frame of the last (scalar-path) channel, the constant channel
+    for b, t, c in hits:
+        xn[b, t, c] = float('nan')
+    for want_std in ((True, False) if B_big else (True,)):
+        kw = dict(want_std=want_std, unbiased=1 if pre else 0, eps=0.0 if pre else 1e-12, pre=p)
+        m0, s0 = time_stats_launch(cdll, device, x, C, **kw)
+        m1, s1 = time_stats_launch(cdll, device, xn, C, **kw)
+        mask = torch.zeros(B, C, dtype=torch.bool)
+        for b, _, c in hits:
+            mask[b, c] = True
+        for a0, a1, what in ((m0, m1, 'mean'), (s0, s1, 'std')):
+            if a1 is None:
+                continue
+            assert bool(torch.isnan(a1[mask]).all()), f'time_stats: a NaN frame left a finite {what}: {a1[mask].tolist()}'
+            assert _same_bits(a0[~mask], a1[~mask]), f'time_stats: a NaN frame changed the {what} of another channel'
+
+
+def time_stats_batch_rows_case(cdll, device, T=49, C=264, ld=272):
+    x = time_stats_data(5, T, C, ld, seed=0)
+    m5, s5 = time_stats_launch(cdll, device, x, C)
+    m1, s1 = time_stats_launch(cdll, device, x[:1].clone(), C)
+    assert _same_bits(m5[:1], m1) and _same_bits(s5[:1], s1)
+
+
+def time_stats_refusal_case(cdll, device):
+    """unbiased with T = 1, ld_out < C, a misaligned x: refused with a message, nothing launched"""
+    x = _dev_copy(time_stats_data(2, 3, 16, 24), device)
+    out = torch.full((2, 2, 16), float('nan'), device=device)
+    f = cdll.mv_time_stats_ex_f16
+    msgs = [_raises(lambda: f(x.data_ptr(), 24, 6, 1, 16, out[0].data_ptr(), out[1].data_ptr(), 16, 1, 0.0, None, None, _stream(x)), cdll),
+            _raises(lambda: f(x.data_ptr(), 24, 2, 3, 16, out[0].data_ptr(), out[1].data_ptr(), 15, 0, 0.0, None, None, _stream(x)), cdll),
+            _raises(lambda: f(x.data_ptr() + 2, 24, 1, 3, 16, out[0].data_ptr(), out[1].data_ptr(), 16, 0, 0.0, None, None, _stream(x)), cdll)]
+    assert bool(torch.isnan(out.cpu()).all()), 'a refused call wrote its output'
+    return msgs
+
+
+# ---- seg_mean
+
+def seg_mean_data(B, T, C, seed=0):
+    ld = C + 8
+    x = torch.empty(B, T, ld, dtype=torch.float16)
+    for b in range(B):   # utterance by utterance: row 0 of a B = 5 call is row 0 of a B = 1 call
+        x[b] = (torch.randn(T, ld, generator=torch.Generator().manual_seed(3000 + 17 * seed + b)) * 1.5 + 0.7).half()
+    x[..., C:] = POOL_SENTINEL
+    return x
+
+
+def seg_mean_launch(cdll, device, x, C, seg_len):
+    B, T, ld = x.shape
+    nseg = (T + seg_len - 1) // seg_len
+    xd = _dev_copy(x, device)
+    ctx = torch.full((B * nseg * C + 8,), float('nan'), device=device)
+    ctx[-8:] = POOL_SENTINEL
+    _hip.check(cdll.mv_seg_mean_f16(xd.data_ptr(), ld, B, T, C, seg_len, ctx.data_ptr(), _stream(xd)), cdll)
+    o = ctx.cpu()
+    assert _same_bits(xd, x), 'seg_mean wrote its input'
+    assert bool((o[-8:] == POOL_SENTINEL).all()), 'seg_mean wrote behind its output'
+    return o[:-8].view(B, nseg, C)
+
+
+def seg_mean_case(cdll, device, T=101, seg_len=100, C=136, B=3, log=print):
+    """ctx[b, s, c] = mean over T + mean over segment s, the last segment divided by its own length, against fp64.
+
+    Bar, from seg_mean_kernel's order: a segment of L frames is summed by 16 row phases, each a chain of ceil(L / 16) fp32 additions, then the 16 LDS
+    partials in one chain of 15 more, then one division: gamma_(ceil(L/16)+16) sum_seg |x| / L.  The utterance total adds the nseg segment sums (nseg
+    more) and is divided by T: gamma_(ceil(seg_len/16)+16+nseg) sum |x| / T.  Their sum rounds once: u |ctx|.  Bar = 2 x the bound."""
+    x = seg_mean_data(B, T, C)
+    ctx = seg_mean_launch(cdll, device, x, C, seg_len)
+    xd = x.double()[..., :C]
+    nseg = ctx.shape[1]
+    gm = xd.mean(1)
+    n_all = (min(seg_len, T) + 15) // 16 + 16 + nseg
+    bar_gm = _gamma(n_all) * xd.abs().sum(1) / T
+    ratio = 0.0
+    for s in range(nseg):
+        seg = xd[:, s * seg_len:min((s + 1) * seg_len, T)]
+        L = seg.shape[1]
+        ref = gm + seg.mean(1)
+        bar = 2 * (bar_gm + _gamma((L + 15) // 16 + 16) * seg.abs().sum(1) / L + U32 * ref.abs())
+        err = (ctx[:, s].double() - ref).abs()
+        ratio = max(ratio, (err / bar).max().item())
+        assert bool((err <= bar).all()), f'seg_mean T={T} seg_len={seg_len} C={C}: segment {s} misses its bar, err {err.max().item():.3e}, err/bar {(err / bar).max().item():.3f}'
+    log(f'seg_mean T={T} seg_len={seg_len} C={C}: err/bar {ratio:.3f}')
+    return ratio
+
+
+def seg_mean_nan_case(cdll, device, T=30, seg_len=7, C=136, B=3):
+    x = seg_mean_data(B, T, C, seed=1)
+    xn = x.clone()
+    xn[1, T - 1, C - 1] = float('nan')     # the last frame of the ragged last segment
+    xn[0, 0, 0] = float('nan')
+    c0, c1 = seg_mean_launch(cdll, device, x, C, seg_len), seg_mean_launch(cdll, device, xn, C, seg_len)
+    mask = torch.zeros_like(c0, dtype=torch.bool)
+    mask[1, :, C - 1] = True               # every segment: the utterance mean is part of each
+    mask[0, :, 0] = True
+    assert bool(torch.isnan(c1[mask]).all()), 'seg_mean: a NaN frame left a finite context'
+    assert _same_bits(c0[~mask], c1[~mask]), 'seg_mean: a NaN frame changed another channel'
+
+
+def seg_mean_batch_rows_case(cdll, device, T=101, seg_len=100, C=136):
+    x = seg_mean_data(5, T, C)
+    assert _same_bits(seg_mean_launch(cdll, device, x, C, seg_len)[:1], seg_mean_launch(cdll, device, x[:1].clone(), C, seg_len))
+
+
+# ---- se_gate_residual
+
+def se_gate_launch(cdll, device, y, gate, cat, res_col, out_col, res_own, T, C):
+    """out = gate * y + res.  cat: the buffer `out` is a column slice of (at out_col); res: the slice at res_col of the same buffer, or res_own."""
+    n, ldy = y.shape
+    B = n // T
+    yd, gd, cd = _dev_copy(y, device), _dev_copy(gate, device), _dev_copy(cat, device)
+    rd = _dev_copy(res_own, device) if res_own is not None else None
+    res_ptr, ldr = (rd.data_ptr(), rd.shape[1]) if rd is not None else (cd.data_ptr() + 2 * res_col, cd.shape[1])
+    _hip.check(cdll.mv_se_gate_residual_f16(yd.data_ptr(), ldy, gd.data_ptr(), res_ptr, ldr, cd.data_ptr() + 2 * out_col, cd.shape[1], B, T, C, _stream(yd)), cdll)
+    o = cd.cpu()
+    assert _same_bits(yd, y) and _same_bits(gd, gate), 'se_gate_residual wrote an input'
+    if rd is not None:
+        assert _same_bits(rd, res_own), 'se_gate_residual wrote its residual'
+    keep = torch.ones(cat.shape[1], dtype=torch.bool)
+    keep[out_col:out_col + C] = False
+    assert _same_bits(o[:, keep], cat[:, keep]), 'se_gate_residual wrote outside its output slice'
+    return o[:, out_col:out_col + C]
+
+
+def se_gate_data(B, T, C, ldy, own, seed=0):
+    n = B * T
+    rows = lambda b, w, s: torch.cat([torch.randn(T, w, generator=torch.Generator().manual_seed(4000 + 31 * seed + 7 * bb + s)) for bb in range(b)])
+    y = (rows(B, ldy, 0) * 2).half()
+    y[:, C:] = POOL_SENTINEL
+    gate = torch.cat([torch.rand(1, C, generator=torch.Generator().manual_seed(4500 + 31 * seed + b)) for b in range(B)])   # sigmoid outputs, each utterance its own
+    res = (rows(B, C, 1) * 2).half()
+    if T * C >= 3:      # planted in utterance 0, row 0: beyond +65504 and below -65504 (stored saturated), and g * y cancelling r to the last bits
+        y[0, 0], gate[0, 0], res[0, 0] = 30000.0, 2.0, 30000.0
+        y[0, 1], gate[0, 1], res[0, 1] = -30000.0, 2.0, -30000.0
+        y[0, 2], gate[0, 2], res[0, 2] = 3.0, 1.0 / 3.0, -1.0
+    if own:     # the residual in a buffer of its own (pitch C + 16), out at column 8 of a buffer of pitch C + 16
+        res_own = torch.full((n, C + 16), POOL_SENTINEL, dtype=torch.float16)
+        res_own[:, :C] = res
+        cat = torch.full((n, C + 16), POOL_SENTINEL, dtype=torch.float16)
+        res_col, out_col = None, 8
+    else:       # res and out: disjoint column slices of one buffer (pitch 2C + 16: res at column 8, out at column C + 8), as in the model's concat buffer
+        res_own = None
+        cat = torch.full((n, 2 * C + 16), POOL_SENTINEL, dtype=torch.float16)
+        res_col, out_col = 8, C + 8
+        cat[:, 8:8 + C] = res
+    cat[:, out_col:out_col + C] = float('nan')
+    return y, gate, res, cat, res_col, out_col, res_own
+
+
+def se_gate_residual_case(cdll, device, B=3, T=7, C=72, ldy=80, own=False, log=print):
+    """Bar per element, as bn_relu_rows_case: half an fp16 ulp of the exact value (x 1.001, which also covers the fp32 rounding of the sum; subnormals
+    2^-25) + one fp32 rounding of the product g * y (the device fuses the multiply-add, the host build of the emulator need not: visible where g * y
+    and r cancel)."""
+    y, gate, res, cat, res_col, out_col, res_own = se_gate_data(B, T, C, ldy, own)
+    out = se_gate_launch(cdll, device, y, gate, cat, res_col, out_col, res_own, T, C)
+    g = gate.double().repeat_interleave(T, 0)
+    prod = g * y.double()[:, :C]
+    ref = (prod + res.double()).clamp(-65504.0, 65504.0)
+    err = (out.double() - ref).abs()
+    tol = ref.abs() * 2.0 ** -11 * 1.001 + 2.0 ** -25 + prod.abs() * U32
+    assert not bool(torch.isnan(out).any()), 'se_gate_residual left an element unwritten'
+    ratio = (err / tol).max().item()
+    assert bool((err <= tol).all()), f'se_gate_residual: err/bar {ratio:.3f}'
+    assert out[0, 0] == 65504.0 and out[0, 1] == -65504.0
+    log(f'se_gate_residual B={B} T={T} C={C} {"own" if own else "slices"}: err/bar {ratio:.3f}')
+    return ratio
+
+
+def se_gate_nan_case(cdll, device, where, B=3, T=7, C=72, ldy=80):
+    y, gate, res, cat, res_col, out_col, res_own = se_gate_data(B, T, C, ldy, False, seed=1)
+    out0 = se_gate_launch(cdll, device, y, gate, cat, res_col, out_col, res_own, T, C)
+    mask = torch.zeros(B * T, C, dtype=torch.bool)
+    r, c = T + 2, C - 3                     # utterance 1
+    if where == 'y':
+        y = y.clone(); y[r, c] = float('nan'); mask[r, c] = True
+    elif where == 'res':
+        cat = cat.clone(); cat[r, res_col + c] = float('nan'); mask[r, c] = True
+    else:
+        gate = gate.clone(); gate[1, c] = float('nan'); mask[T:2 * T, c] = True
+    out1 = se_gate_launch(cdll, device, y, gate, cat, res_col, out_col, res_own, T, C)
+    assert bool(torch.isnan(out1[mask]).all()), f'se_gate_residual: a NaN in {where} came out finite: {out1[mask].tolist()}'
+    assert _same_bits(out0[~mask], out1[~mask])
+
+
+def se_gate_batch_rows_case(cdll, device, T=7, C=72, ldy=80):
+    y, gate, res, cat, res_col, out_col, _ = se_gate_data(5, T, C, ldy, False)
+    o5 = se_gate_launch(cdll, device, y, gate, cat, res_col, out_col, None, T, C)
+    o1 = se_gate_launch(cdll, device, y[:T].clone(), gate[:1].clone(), cat[:T].clone(), res_col, out_col, None, T, C)
+    assert _same_bits(o5[:T], o1)
+
+
+# ---- asp_hidden_act
+
+def asp_hidden_data(B, T, A, seed=0):
+    g = torch.Generator().manual_seed(5000 + seed)
+    z = (torch.randn(B * T, A, generator=g) * 1.5).half()
+    z[0, 0], z[1, 1], z[2, 2], z[3, 3] = 30.0, -30.0, 100.0, 45.0       # tanhf where the value has saturated to +-1 (scale[0 .. 3] = +-1 below)
+    rb = torch.randn(B, A, generator=g) + torch.arange(B).float().unsqueeze(1) * 1.5 - 1.0     # the utterances' biases 1.5 apart: a wrong b is far outside the bar
+    sc = torch.randn(A, generator=g) * 1.5
+    sh = torch.randn(A, generator=g) * 0.5
+    sc[0], sc[1], sc[2], sc[3] = 1.0, 1.0, -1.0, 0.8
+    return z, rb, sc, sh
+
+
+def asp_hidden_launch(cdll, device, z, rb, sc, sh, B, T, A):
+    buf = torch.full((B * T * A + 8,), POOL_SENTINEL, dtype=torch.float16)
+    buf[:-8] = z.reshape(-1)
+    bd, rd, sd, td = _dev_copy(buf, device), _dev_copy(rb, device), _dev_copy(sc, device), _dev_copy(sh, device)
+    _hip.check(cdll.mv_asp_hidden_act_f16(bd.data_ptr(), rd.data_ptr(), sd.data_ptr(), td.data_ptr(), B, T, A, _stream(bd)), cdll)
+    o = bd.cpu()
+    assert _same_bits(rd, rb) and _same_bits(sd, sc) and _same_bits(td, sh), 'asp_hidden_act wrote a parameter'
+    assert bool((o[-8:] == POOL_SENTINEL).all()), 'asp_hidden_act wrote behind its rows'
+    return o[:-8].view(B * T, A)
+
+
+def asp_hidden_act_case(cdll, device, B=3, T=5, A=136, log=print):
+    """h = tanh(relu(z + rb[b]) * scale + shift) in place, against fp64.  Bar per element: half an fp16 ulp of the exact value x 1.001 (subnormals 2^-25;
+    the 0.001 covers tanhf's own ulp or two of fp32 and the rounding of the last addition, whose effect on h is at most u |a| tanh'(a) <= u |h|) + the
+    fp32 term of p = relu(z + rb) * scale: the sum z + rb and the product round once each, 2 u |p|, and reach h multiplied by tanh' <= 1."""
+    z, rb, sc, sh = asp_hidden_data(B, T, A)
+    out = asp_hidden_launch(cdll, device, z, rb, sc, sh, B, T, A)
+    p = torch.relu(z.double() + rb.double().repeat_interleave(T, 0)) * sc.double()
+    ref = torch.tanh(p + sh.double())
+    err = (out.double() - ref).abs()
+    tol = ref.abs() * 2.0 ** -11 * 1.001 + 2.0 ** -25 + 2 * U32 * p.abs()
+    ratio = (err / tol).max().item()
+    assert bool((err <= tol).all()), f'asp_hidden_act A={A}: err/bar {ratio:.3f} at {torch.nonzero(err > tol)[0].tolist()}'
+    assert (ref.abs() > 0.9999).sum() >= 3          # the saturated plants are there
+    log(f'asp_hidden_act B={B} T={T} A={A}: err/bar {ratio:.3f}')
+    return ratio
+
+
+def asp_hidden_nan_case(cdll, device, B=3, T=5, A=136):
+    z, rb, sc, sh = asp_hidden_data(B, T, A, seed=1)
+    out0 = asp_hidden_launch(cdll, device, z, rb, sc, sh, B, T, A)
+    zn = z.clone()
+    zn[T + 1, A - 1] = float('nan')
+    rbn = rb.clone()
+    rbn[2, 4] = float('nan')
+    out1 = asp_hidden_launch(cdll, device, zn, rbn, sc, sh, B, T, A)
+    mask = torch.zeros(B * T, A, dtype=torch.bool)
+    mask[T + 1, A - 1] = True
+    mask[2 * T:3 * T, 4] = True
+    assert bool(torch.isnan(out1[mask]).all()), f'asp_hidden_act: a NaN came out finite: {out1[mask].tolist()}'
+    assert _same_bits(out0[~mask], out1[~mask])
+
+
+# ---- the casts and copies: bitwise against numpy
+
+def pool_features(B, T, F, seed):
+    """as _features of tests/test_feature_dims.py: values beyond the fp16 range on either side, and 65519 (rounds to inf in fp16 without the clamp)"""
+    x = torch.randn(B, T, F, generator=torch.Generator().manual_seed(seed)) * 3
+    x[0, 0, 0], x[-1, -1, -1] = 1.0e6, -7.0e4
+    if F > 2:
+        x[0, 1, 2] = 65519.0
+    return x
+
+
+def _equal_f16(got, want):
+    """bitwise, a NaN matching any NaN"""
+    gn, wn = np.isnan(got), np.isnan(want)
+    return np.array_equal(gn, wn) and np.array_equal(got.view(np.uint16)[~gn], want.view(np.uint16)[~wn])
+
+
+def cast_pad_case(cdll, device, F=13, pad=2, B=2, T=9, nan=False):
+    """mv_cast_pad_f16 (the choice EcapaModel::forward makes: the 16-byte kernel for ldd == F, the ragged one otherwise) against np.pad(mode='reflect'),
+    clip(+-65504), astype(float16); columns F .. ldd-1 are +0"""
+    ldd = (F + 7) // 8 * 8
+    x = pool_features(B, T, F, F + pad)
+    if nan:
+        x[0, 0, 1 % F], x[1, T - 1, F - 1], x[1, T // 2, 0] = float('nan'), float('nan'), float('nan')   # the first and last frames are mirrored into the padding
+    Tp = T + 2 * pad
+    xd = _dev_copy(x, device)
+    out = torch.full((B * Tp * ldd + 8,), float('nan'), dtype=torch.float16, device=device)
+    out[-8:] = POOL_SENTINEL
+    _hip.check(cdll.mv_cast_pad_f16(xd.data_ptr(), out.data_ptr(), B, T, F, ldd, pad, _stream(xd)), cdll)
+    o = out.cpu()
+    assert _same_bits(xd, x) and bool((o[-8:] == POOL_SENTINEL).all())
+    want = np.zeros((B, Tp, ldd), np.float16)
+    xp = np.pad(x.numpy(), ((0, 0), (pad, pad), (0, 0)), mode='reflect')
+    want[:, :, :F] = np.clip(xp, -65504.0, 65504.0).astype(np.float16)
+    got = o[:-8].view(B, Tp, ldd).numpy()
+    if nan:
+        assert np.isnan(want).sum() >= 3
+    assert _equal_f16(got, want), np.argwhere(got.view(np.uint16) != want.view(np.uint16))[:4]
+
+
+def cast_rows_case(cdll, device, C=13, ldd=16, n=37, nan=False):
+    lds = C + 3
+    x = torch.full((n, lds), POOL_SENTINEL)
+    x[:, :C] = pool_features(1, n, C, C)[0]
+    if nan:
+        x[0, 0], x[n - 1, C - 1] = float('nan'), float('nan')
+    xd = _dev_copy(x, device)
+    out = torch.full((n * ldd + 8,), float('nan'), dtype=torch.float16, device=device)
+    out[-8:] = POOL_SENTINEL
+    _hip.check(cdll.mv_cast_rows_f16(xd.data_ptr(), lds, out.data_ptr(), ldd, n, C, _stream(xd)), cdll)
+    o = out.cpu()
+    assert _same_bits(xd, x) and bool((o[-8:] == POOL_SENTINEL).all())
+    want = np.zeros((n, ldd), np.float16)      # columns C .. ldd-1: +0
+    want[:, :C] = np.clip(x.numpy()[:, :C], -65504.0, 65504.0).astype(np.float16)
+    assert _equal_f16(o[:-8].view(n, ldd).numpy(), want)
+
+
+def copy_slice_case(cdll, device, C=64, lds=512, ldd=520, n=37, src_col=128, dst_col=8):
+    g = torch.Generator().manual_seed(6000)
+    src = (torch.randn(n, lds, generator=g) * 3).half()
+    src[0, src_col], src[1, src_col + 1], src[2, src_col + C - 1] = float('inf'), float('nan'), 6.0e-8    # a copy keeps everything: inf, NaN, subnormals
+    dst = torch.full((n, ldd), POOL_SENTINEL, dtype=torch.float16)
+    dst[:, dst_col:dst_col + C] = float('nan')
+    dst[:, dst_col:dst_col + C].view(torch.int16).fill_(0x7e55)          # (a NaN with a payload of its own: the copied NaN must not be taken for it)
+    sd, dd = _dev_copy(src, device), _dev_copy(dst, device)
+    _hip.check(cdll.mv_copy_slice_f16(sd.data_ptr() + 2 * src_col, lds, dd.data_ptr() + 2 * dst_col, ldd, C, n, _stream(sd)), cdll)
+    o = dd.cpu()
+    want = dst.clone()
+    want[:, dst_col:dst_col + C] = src[:, src_col:src_col + C]
+    assert _same_bits(sd, src) and _same_bits(o, want)
+
+
+def pad_rows_f32_case(cdll, device, F=13, ldd=16, n=37):
+    x = pool_features(1, n, F, F)[0].contiguous()
+    x[3, 0] = float('inf')
+    xd = _dev_copy(x, device)
+    out = torch.full((n * ldd + 4,), float('nan'), device=device)
+    out[-4:] = POOL_SENTINEL
+    _hip.check(cdll.mv_pad_rows_f32(xd.data_ptr(), F, out.data_ptr(), ldd, n, _stream(xd)), cdll)
+    o = out.cpu()
+    want = torch.zeros(n, ldd)
+    want[:, :F] = x                                       # an exact copy: no clamp, the first conv converts to fp16 itself
+    assert _same_bits(xd, x) and bool((o[-4:] == POOL_SENTINEL).all())
+    assert _same_bits(o[:-4].view(n, ldd), want)
+
+
+def bn_relu_rows_nan_case(cdll, device, rows=9, C=72, ldx=80, ldy=88):
+    """relu(NaN * scale + shift) is NaN (torch.relu keeps it); every other element keeps its bits"""
+    g = torch.Generator().manual_seed(21)
+    x = (torch.randn(rows, ldx, generator=g) * 3).half()
+    sc, sh = torch.randn(C, generator=g) * 2, torch.randn(C, generator=g)
+    xn = x.clone()
+    xn[4, C - 1] = float('nan')
+    scn = sc.clone()
+    scn[7] = float('nan')
+    outs = []
+    for xx, ss in ((x, sc), (xn, scn)):
+        xd, sd, td = _dev_copy(xx, device), _dev_copy(ss, device), _dev_copy(sh, device)
+        y = torch.full((rows, ldy), -7.0, dtype=torch.half, device=device)
+        _hip.check(cdll.mv_bn_relu_rows_f16(xd.data_ptr(), ldx, sd.data_ptr(), td.data_ptr(), y.data_ptr(), ldy, rows, C, _stream(xd)), cdll)
+        outs.append(y.cpu())
+    mask = torch.zeros(rows, ldy, dtype=torch.bool)
+    mask[4, C - 1] = True
+    mask[:, 7] = True
+    assert bool(torch.isnan(outs[1][mask]).all()), f'bn_relu_rows: a NaN came out finite: {outs[1][mask].tolist()}'
+    assert _same_bits(outs[0][~mask], outs[1][~mask])

@@ -2,7 +2,6 @@
 zero-padding kernels against a numpy statement, EcapaTdnn (window and per-tap first conv), TDNN and CAM++ against the host package's torch
 forward, and the padding contract -- a model at F = 201 gives the bits of the same model at F = 208 with zero-padded features and first-layer
 weights."""
-import ctypes
 import os
 
 import numpy as np
@@ -13,25 +12,16 @@ from emu_lib import emu_cdll
 from helpers import cos_dist
 from mvector import _hip
 
-# the launchers of csrc/pool.hip are internal (not in the C ABI); the emulator build exports every symbol, so the tests reach them by name
-_PAD_F16 = '_ZN2mv30cast_reflect_pad_ragged_launchEPKfPDF16_iiiiiPv'   # mv::cast_reflect_pad_ragged_launch
-_PAD_F32 = '_ZN2mv19pad_rows_f32_launchEPKfiPfllPv'                    # mv::pad_rows_f32_launch
-
-
-def _fn(name, argtypes):
-    f = getattr(emu_cdll(), name)
-    f.argtypes, f.restype = argtypes, ctypes.c_int
-    return f
+# the zero-padding launchers of csrc/pool.hip through their layer-level entry points (mv_cast_pad_f16 makes the choice EcapaModel::forward makes: the
+# ragged kernel whenever ldd != F)
 
 
 def _pad_f16(src, dst, B, T, F, ldd, pad):
-    f = _fn(_PAD_F16, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p])
-    return f(src, dst, B, T, F, ldd, pad, None)
+    return emu_cdll().mv_cast_pad_f16(src, dst, B, T, F, ldd, pad, None)
 
 
 def _pad_f32(src, F, dst, ldd, n_rows):
-    f = _fn(_PAD_F32, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p])
-    return f(src, F, dst, ldd, n_rows, None)
+    return emu_cdll().mv_pad_rows_f32(src, F, dst, ldd, n_rows, None)
 
 
 def _round8(n):

@@ -1,6 +1,6 @@
 """Bad arguments at the C ABI (no GPU): every field of MvConv1dDesc / MvConv2dsDesc of a VALID layer call -- and every pointer / integer
 argument of the positional entry points (linear, time statistics, ASP pooling, Res2Net chain, BN + ReLU rows, TSTP, wave preparation, cosine, the CAM++ dense
-block) -- is replaced, one at a
+block, the reductions and row passes of pool.hip) -- is replaced, one at a
 time, by values a caller can get wrong -- a null pointer, 0, -1, a huge size, an enum out of range, a leading dimension smaller than the row --
 and the entry point is called on the emulator build.  The contract (include/mvector_hip.h): a call the library cannot run returns an error code
 and a message; it never crashes and never touches memory outside the caller's buffers.
@@ -175,6 +175,39 @@ def cam_dense_block_calls(cdll, log):
     call('form 0, dil = 3 (no fused form)', form=0, dil=3)
 
 
+def pool_rows_calls(cdll, log):
+    """the layer-level entry points of csrc/pool.hip's reductions and row passes: one small valid call each, every pointer null and every integer 0
+    and -1 in turn (the inputs are drawn here: the tool needs nothing of the tests)"""
+    import torch
+    from mvector import _hip
+    g = torch.Generator().manual_seed(23)
+    h16 = lambda *s: torch.randn(*s, generator=g).half()
+    f32 = lambda *s: torch.randn(*s, generator=g)
+    t = lambda name: getattr(TamperArgs(cdll, name, log), name)
+    B, T, C, ld = 2, 9, 72, 80
+    x = h16(B, T, ld)
+    out = torch.zeros(B, 2 * C + 8)
+    sc, sh = f32(C), f32(C)
+    _hip.check(t('mv_time_stats_ex_f16')(x.data_ptr(), ld, B, T, C, out.data_ptr(), out.data_ptr() + 4 * C, 2 * C + 8, 1, 0.0, sc.data_ptr(), sh.data_ptr(), None), cdll)
+    ctx = torch.zeros(B, 3, C)
+    _hip.check(t('mv_seg_mean_f16')(x.data_ptr(), ld, B, T, C, 4, ctx.data_ptr(), None), cdll)
+    y, gate, cat = h16(B * T, ld), torch.rand(B, C, generator=g), h16(B * T, 2 * C + 16)
+    _hip.check(t('mv_se_gate_residual_f16')(y.data_ptr(), ld, gate.data_ptr(), cat.data_ptr() + 16, 2 * C + 16, cat.data_ptr() + 2 * (C + 8), 2 * C + 16, B, T, C,
+                                            None), cdll)
+    z, rb = h16(B * T, C), f32(B, C)
+    _hip.check(t('mv_asp_hidden_act_f16')(z.data_ptr(), rb.data_ptr(), sc.data_ptr(), sh.data_ptr(), B, T, C, None), cdll)
+    for F in (16, 13):      # the 16-byte kernel, the ragged kernel
+        ldd, pad = (F + 7) // 8 * 8, 2
+        feats, dst = f32(B, T, F), torch.zeros(B * (T + 2 * pad) * ldd, dtype=torch.float16)
+        _hip.check(t('mv_cast_pad_f16')(feats.data_ptr(), dst.data_ptr(), B, T, F, ldd, pad, None), cdll)
+    src, dst = f32(5, 16), torch.zeros(5, 16, dtype=torch.float16)
+    _hip.check(t('mv_cast_rows_f16')(src.data_ptr(), 16, dst.data_ptr(), 16, 5, 13, None), cdll)
+    s16, d16 = h16(5, 32), torch.zeros(5, 40, dtype=torch.float16)
+    _hip.check(t('mv_copy_slice_f16')(s16.data_ptr() + 16, 32, d16.data_ptr() + 16, 40, 16, 5, None), cdll)
+    s32, d32 = f32(5, 13), torch.zeros(5, 16)
+    _hip.check(t('mv_pad_rows_f32')(s32.data_ptr(), 13, d32.data_ptr(), 16, 5, None), cdll)
+
+
 def worker(only=''):
     import layer_checks as lc
     from mvector import _hip
@@ -183,6 +216,14 @@ def worker(only=''):
     log = []
     if only in ('', 'cam'):
         cam_dense_block_calls(cdll, log)
+    if only == '':
+        pool_rows_calls(cdll, log)
+    if only == 'pool':
+        pool_rows_calls(cdll, log)
+        rej = sum(1 for e in log if e[3] != 0)
+        print(f'SUMMARY {len(log)} tampered calls: {rej} rejected, {len(log) - rej} accepted, 0 crashed', flush=True)
+        print('ACCEPTED ' + '; '.join(f'{e[0]}.{e[1]}={e[2]!r}' for e in log if e[3] == 0), flush=True)
+        return
     if only == 'cam':
         rej = sum(1 for e in log if e[3] != 0)
         print(f'SUMMARY {len(log)} tampered calls: {rej} rejected, {len(log) - rej} accepted, 0 crashed', flush=True)
@@ -213,7 +254,8 @@ def worker(only=''):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--mode', default='plain', choices=['plain', 'asan', 'ubsan'])
-    ap.add_argument('--only', default='', choices=['', 'cam'], help='cam: the CAM++ dense-block entry points alone (what tests/test_cam_dense.py runs)')
+    ap.add_argument('--only', default='', choices=['', 'cam', 'pool'],
+                    help='cam: the CAM++ dense-block entry points alone (what tests/test_cam_dense.py runs); pool: the row passes of pool.hip (tests/test_pool_rows.py)')
     ap.add_argument('--worker', action='store_true', help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.worker:

@@ -96,6 +96,8 @@ int se_gate_residual_launch(const half_t* y, int64_t ldy, const float* gate, con
 int cast_reflect_pad_launch(const float* src, half_t* dst, int B, int T, int C, int pad, hipStream_t stream);
 // ragged feature width F: destination pitch ldd = round_up(F, 8), columns F..ldd-1 zero (any F; the model takes it for F % 8 != 0)
 int cast_reflect_pad_ragged_launch(const float* src, half_t* dst, int B, int T, int F, int ldd, int pad, hipStream_t stream);
+// the choice between the two (ldd == F: the 16-byte form): what EcapaModel::forward and mv_cast_pad_f16 call
+int cast_pad_launch(const float* src, half_t* dst, int B, int T, int F, int64_t ldd, int pad, hipStream_t stream);
 // fp32 rows of width F copied to pitch ldd (a multiple of 4), columns F..ldd-1 zero
 int pad_rows_f32_launch(const float* src, int F, float* dst, int64_t ldd, int64_t n_rows, hipStream_t stream);
 int cast_rows_f32_f16_launch(const float* src, int64_t lds_, half_t* dst, int64_t ldd, int64_t n_rows, int C, hipStream_t stream);

@@ -602,11 +602,7 @@ struct EcapaModel : MvModelBase {
         const int64_t ldf = round_up(F, 8);
         const int pad0 = cfg.dilations[0] * (cfg.kernel_sizes[0] - 1) / 2;
         if (block0_window) {
-            if (ldf == F) {
-                if ((rc = cast_reflect_pad_launch(feats, s.x16, B, T, F, pad0, st))) return rc;
-            } else {
-                if ((rc = cast_reflect_pad_ragged_launch(feats, s.x16, B, T, F, (int)ldf, pad0, st))) return rc;
-            }
+            if ((rc = cast_pad_launch(feats, s.x16, B, T, F, ldf, pad0, st))) return rc;
             d = conv_desc(block0w, s.x16, ldf, s.a0, cfg.channels[0], B, T + 2 * pad0, T);   // (the window form: a 1x1 conv over the padded rows)
             d.pad_mode = MV_PAD_ZERO;
             d.pre_act = MV_ACT_RELU;

@@ -22,6 +22,14 @@ static inline int ew_grid(int64_t groups) {
     return (int)(g < 1 ? 1 : (g < EW_MAX_GRID ? g : EW_MAX_GRID));
 }
 
+// Saturation to a range in front of the fp16 rounding that KEEPS a NaN (fminf / fmaxf return their other operand: the plain form turns a NaN input
+// into a finite bound, and the model returns a plausible embedding where the reference returns NaN -- the s16_clamp of the conv2ds kernels, s16map.h).
+// Every non-NaN value takes the same two operations as before: the same bits.
+__device__ __forceinline__ float sat_keep_nan(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+__device__ __forceinline__ float f16_sat(float v) { return sat_keep_nan(v, -65504.0f, 65504.0f); }
+// ReLU as torch has it: relu(NaN) = NaN (fmaxf(NaN, 0) is 0)
+__device__ __forceinline__ float relu_keep_nan(float v) { return v != v ? v : fmaxf(v, 0.0f); }
+
 
 // ------------------------------------------------------------------------------------------------
 // mean / std over time.  Workgroup = (utterance, 128-channel group): lane (c16 = lane & 15) owns 8 channels, the four
@@ -59,7 +67,7 @@ __global__ __launch_bounds__(256) void time_stats_kernel(const half_t* x, int64_
     }
     auto val = [&](half_t h, int e) {
         const float v = (float)h;
-        return pre ? fmaxf(v * isc[e] + ish[e], 0.0f) : v;
+        return pre ? relu_keep_nan(v * isc[e] + ish[e]) : v;
     };
     if (active) {
         if (nvalid == 8) {
@@ -127,14 +135,16 @@ __global__ __launch_bounds__(256) void time_stats_kernel(const half_t* x, int64_
     if (tid < 128 && cg0 + tid < C) {
         // k of channel tid: recomputed by its owner thread (one 2-byte load)
         float kc = (float)x[(int64_t)b * T * ld + cg0 + tid];
-        if (pre) kc = fmaxf(kc * in_scale[cg0 + tid] + in_shift[cg0 + tid], 0.0f);
+        if (pre) kc = relu_keep_nan(kc * in_scale[cg0 + tid] + in_shift[cg0 + tid]);
         const float z1 = red[0][0][tid] + red[0][1][tid] + red[0][2][tid] + red[0][3][tid];
         const float z2 = LEAN ? 0.0f : red[1][0][tid] + red[1][1][tid] + red[1][2][tid] + red[1][3][tid];
         mean[(int64_t)b * ld_out + cg0 + tid] = kc + z1 / (float)T;
         if (!LEAN && stdv != nullptr) {
             const float denom = unbiased ? (float)(T - 1) : (float)T;
-            float var = fmaxf(z2 - z1 * z1 / (float)T, 0.0f) / denom;
-            if (clamp_eps > 0.0f) var = fmaxf(var, clamp_eps);
+            // (comparisons, not fmaxf: a NaN frame leaves the channel's std NaN like its mean, where fmaxf would return the clamp)
+            const float m2 = z2 - z1 * z1 / (float)T;
+            float var = (m2 < 0.0f ? 0.0f : m2) / denom;
+            if (clamp_eps > 0.0f) var = var < clamp_eps ? clamp_eps : var;
             stdv[(int64_t)b * ld_out + cg0 + tid] = sqrtf(var);
         }
     }
@@ -146,6 +156,7 @@ int time_stats_launch(const half_t* x, int64_t ld, int B, int T, int C, float* m
     MV_REQUIRE(ld > 0 && ld % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "time_stats: rows must be 16-byte aligned");
     MV_REQUIRE(ld_out >= C, "time_stats: output leading dimension");
     if (unbiased) MV_REQUIRE(T > 1, "time_stats: unbiased std needs T > 1");
+    MV_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "time_stats: the pre-activation needs both in_scale and in_shift");
     const bool lean = stdv == nullptr && in_scale == nullptr;
     if (ceil_div(C, 128) * (int64_t)B <= 1024) {
         MV_LAUNCH(time_stats_kernel<true>, ((unsigned)ceil_div(C, 128), (unsigned)B, 1), (256, 1, 1), 0, stream, x, ld, T, C, mean, stdv,
@@ -209,7 +220,7 @@ __global__ __launch_bounds__(256) void seg_mean_kernel(const half_t* x, int64_t 
 
 int seg_mean_launch(const half_t* x, int64_t ld, int B, int T, int C, int seg_len, float* ctx, hipStream_t stream) {
     MV_REQUIRE(x != nullptr && ctx != nullptr && B > 0 && T > 0 && C > 0 && seg_len > 0, "seg_mean: bad argument");
-    MV_REQUIRE(C % 8 == 0 && ld % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "seg_mean: rows must be 16-byte aligned");
+    MV_REQUIRE(C % 8 == 0 && ld % 8 == 0 && ld >= C && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "seg_mean: rows must be 16-byte aligned, ld >= C");
     const int nseg = (int)ceil_div(T, seg_len);
     MV_LAUNCH(seg_mean_kernel, ((unsigned)ceil_div(C, 128), (unsigned)B, 1), (256, 1, 1), 0, stream, x, ld, T, C, seg_len, nseg,
               ctx);
@@ -235,9 +246,8 @@ __global__ __launch_bounds__(256) void se_gate_residual_kernel(const half_t* y, 
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float g = e < 4 ? g0[e] : g1[e - 4];
-            float v = g * (float)yv[e] + (float)rv[e];
-            v = fminf(fmaxf(v, -65504.0f), 65504.0f);
-            ov[e] = (half_t)v;
+            const float v = g * (float)yv[e] + (float)rv[e];
+            ov[e] = (half_t)f16_sat(v);
         }
         *reinterpret_cast<half8v*>(out + n * ldo + c) = ov;
     }
@@ -246,7 +256,12 @@ __global__ __launch_bounds__(256) void se_gate_residual_kernel(const half_t* y, 
 int se_gate_residual_launch(const half_t* y, int64_t ldy, const float* gate, const half_t* res, int64_t ldr, half_t* out,
                             int64_t ldo, int B, int T, int C, hipStream_t stream) {
     MV_REQUIRE(y != nullptr && gate != nullptr && res != nullptr && out != nullptr, "se_gate_residual: null tensor");
+    MV_REQUIRE(B > 0 && T > 0 && C > 0, "se_gate_residual: bad geometry");
     MV_REQUIRE(C % 8 == 0 && ldy % 8 == 0 && ldr % 8 == 0 && ldo % 8 == 0, "se_gate_residual: channels must be a multiple of 8");
+    MV_REQUIRE(ldy >= C && ldr >= C && ldo >= C, "se_gate_residual: a leading dimension is shorter than the row");
+    MV_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(gate) & 15) == 0 && (reinterpret_cast<uintptr_t>(res) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+               "se_gate_residual: rows and gates must be 16-byte aligned");
     const int64_t n_rows = (int64_t)B * T;
     const int64_t total = n_rows * (C / 8);
     const int grid = ew_grid(total);
@@ -275,15 +290,15 @@ __global__ __launch_bounds__(256) void cast_rows_f32_f16_kernel(const float* src
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t n = i / ldd;
         const int c = (int)(i - n * ldd);
-        float v = c < C ? src[n * lds_ + c] : 0.0f;
-        v = fminf(fmaxf(v, -65504.0f), 65504.0f);
-        dst[i] = (half_t)v;
+        const float v = c < C ? src[n * lds_ + c] : 0.0f;
+        dst[i] = (half_t)f16_sat(v);
     }
 }
 
 int cast_rows_f32_f16_launch(const float* src, int64_t lds_, half_t* dst, int64_t ldd, int64_t n_rows, int C,
                              hipStream_t stream) {
     MV_REQUIRE(src != nullptr && dst != nullptr && ldd >= C, "cast_rows: bad argument");
+    MV_REQUIRE(n_rows > 0 && C > 0 && lds_ >= C, "cast_rows: bad shape (rows and channels must be positive, the source pitch at least C)");
     const int64_t total = n_rows * ldd;
     const int grid = ew_grid(total);
     MV_LAUNCH(cast_rows_f32_f16_kernel, (grid, 1, 1), (256, 1, 1), 0, stream, src, lds_, dst, ldd, n_rows, C);
@@ -306,13 +321,14 @@ __global__ __launch_bounds__(256) void cast_reflect_pad_kernel(const float* src,
         const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         half8v o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j] = (half_t)fminf(fmaxf(v[j], -65504.0f), 65504.0f);
+        for (int j = 0; j < 8; ++j) o[j] = (half_t)f16_sat(v[j]);
         *reinterpret_cast<half8v*>(dst + (int64_t)i * 8) = o;
     }
 }
 
 int cast_reflect_pad_launch(const float* src, half_t* dst, int B, int T, int C, int pad, hipStream_t stream) {
     MV_REQUIRE(src != nullptr && dst != nullptr && pad >= 0 && pad < T && C % 8 == 0, "cast_reflect_pad: bad argument");
+    MV_REQUIRE(B > 0 && T > 0 && C > 0, "cast_reflect_pad: bad shape");
     const int64_t total = (int64_t)B * (T + 2 * pad) * (C / 8);
     MV_REQUIRE(total < (int64_t)1 << 31, "cast_reflect_pad: batch too large");
     const int grid = ew_grid(total);
@@ -337,7 +353,7 @@ __global__ __launch_bounds__(256) void cast_reflect_pad_ragged_kernel(const floa
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float v = c0 + j < F ? s[c0 + j] : 0.0f;
-            o[j] = (half_t)fminf(fmaxf(v, -65504.0f), 65504.0f);
+            o[j] = (half_t)f16_sat(v);
         }
         *reinterpret_cast<half8v*>(dst + (int64_t)i * 8) = o;
     }
@@ -352,6 +368,14 @@ int cast_reflect_pad_ragged_launch(const float* src, half_t* dst, int B, int T, 
     const int grid = ew_grid(total);
     MV_LAUNCH(cast_reflect_pad_ragged_kernel, (grid, 1, 1), (256, 1, 1), 0, stream, src, dst, B, T, F, ldd, pad);
     return check_launch("cast_reflect_pad_ragged_kernel");
+}
+
+// The features of EcapaTdnn's window form at the destination pitch ldd: the 16-byte form when the rows need no padding (ldd == F, F % 8 == 0), the
+// ragged form otherwise.  ONE choice for the model's forward and the layer-level entry point (mv_cast_pad_f16).
+int cast_pad_launch(const float* src, half_t* dst, int B, int T, int F, int64_t ldd, int pad, hipStream_t stream) {
+    if (ldd == F) return cast_reflect_pad_launch(src, dst, B, T, F, pad, stream);
+    MV_REQUIRE(ldd > 0 && ldd < ((int64_t)1 << 31), "cast_pad: bad destination pitch");
+    return cast_reflect_pad_ragged_launch(src, dst, B, T, F, (int)ldd, pad, stream);
 }
 
 // dst[n, 0:F] = src[n, 0:F], dst[n, F:ldd] = 0 in fp32: features of a ragged width F at a pitch the conv loader accepts (TDNN td_layer1, which
@@ -380,7 +404,11 @@ int pad_rows_f32_launch(const float* src, int F, float* dst, int64_t ldd, int64_
 }
 
 int copy_slice_launch(const half_t* src, int64_t lds_, half_t* dst, int64_t ldd, int C, int64_t n_rows, hipStream_t stream) {
+    MV_REQUIRE(src != nullptr && dst != nullptr, "copy_slice: null tensor");
+    MV_REQUIRE(C > 0 && n_rows > 0, "copy_slice: bad geometry");
     MV_REQUIRE(C % 8 == 0 && lds_ % 8 == 0 && ldd % 8 == 0, "copy_slice: channels must be a multiple of 8");
+    MV_REQUIRE(lds_ >= C && ldd >= C, "copy_slice: a leading dimension is shorter than the row");
+    MV_REQUIRE((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0, "copy_slice: rows must be 16-byte aligned");
     const int64_t total = n_rows * (C / 8);
     const int grid = ew_grid(total);
     MV_LAUNCH(copy_slice_kernel, (grid, 1, 1), (256, 1, 1), 0, stream, src, lds_, dst, ldd, C, n_rows);
@@ -409,7 +437,7 @@ __global__ __launch_bounds__(256) void asp_hidden_act_kernel(half_t* zh, const f
             const float4v r4 = *reinterpret_cast<const float4v*>(rb + 4 * q);
             const float4v sc = *reinterpret_cast<const float4v*>(scale + a8 * 8 + 4 * q), sh = *reinterpret_cast<const float4v*>(shift + a8 * 8 + 4 * q);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[4 * q + e] = (half_t)tanhf(fmaxf((float)v[4 * q + e] + r4[e], 0.0f) * sc[e] + sh[e]);
+            for (int e = 0; e < 4; ++e) o[4 * q + e] = (half_t)tanhf(relu_keep_nan((float)v[4 * q + e] + r4[e]) * sc[e] + sh[e]);
         }
         *reinterpret_cast<half8v*>(zh + i * 8) = o;
     }
@@ -430,7 +458,7 @@ __global__ __launch_bounds__(256) void bn_relu_rows_kernel(const half_t* x, int6
         for (int q = 0; q < 2; ++q) {
             const float4v sc = *reinterpret_cast<const float4v*>(scale + c + 4 * q), sh = *reinterpret_cast<const float4v*>(shift + c + 4 * q);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) o[4 * q + e] = (half_t)fminf(fmaxf((float)v[4 * q + e] * sc[e] + sh[e], 0.0f), 65504.0f);
+            for (int e = 0; e < 4; ++e) o[4 * q + e] = (half_t)sat_keep_nan((float)v[4 * q + e] * sc[e] + sh[e], 0.0f, 65504.0f);
         }
         *reinterpret_cast<half8v*>(y + n * ldy + c) = o;
     }
@@ -451,6 +479,9 @@ int bn_relu_rows_launch(const half_t* x, int64_t ldx, const float* scale, const 
 int asp_hidden_act_launch(half_t* zh, const float* row_bias, const float* scale, const float* shift, int B, int T, int A, hipStream_t stream) {
     MV_REQUIRE(zh != nullptr && row_bias != nullptr && scale != nullptr && shift != nullptr, "asp_hidden_act: null tensor");
     MV_REQUIRE(B > 0 && T > 0 && A > 0 && A % 8 == 0, "asp_hidden_act: bad geometry");
+    MV_REQUIRE((reinterpret_cast<uintptr_t>(zh) & 15) == 0 && (reinterpret_cast<uintptr_t>(row_bias) & 15) == 0 && (reinterpret_cast<uintptr_t>(scale) & 15) == 0 &&
+                   (reinterpret_cast<uintptr_t>(shift) & 15) == 0,
+               "asp_hidden_act: rows and parameters must be 16-byte aligned");
     const int64_t total8 = (int64_t)B * T * (A / 8);
     const int grid = ew_grid(total8);
     MV_LAUNCH(asp_hidden_act_kernel, (grid, 1, 1), (256, 1, 1), 0, stream, zh, row_bias, scale, shift, total8, T, A / 8);
@@ -1099,6 +1130,44 @@ int mv_time_stats_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C
                       int32_t unbiased, float clamp_eps, mv_stream_t stream) {
     return mv::time_stats_launch(reinterpret_cast<const half_t*>(x), ld, B, T, C, mean, std, C, unbiased, clamp_eps,
                                  static_cast<hipStream_t>(stream), nullptr, nullptr);
+}
+
+int mv_time_stats_ex_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C, float* mean, float* std, int64_t ld_out, int32_t unbiased,
+                         float clamp_eps, const float* in_scale, const float* in_shift, mv_stream_t stream) {
+    return mv::time_stats_launch(reinterpret_cast<const half_t*>(x), ld, B, T, C, mean, std, ld_out, unbiased, clamp_eps,
+                                 static_cast<hipStream_t>(stream), in_scale, in_shift);
+}
+
+int mv_seg_mean_f16(const void* x, int64_t ld, int32_t B, int32_t T, int32_t C, int32_t seg_len, float* ctx, mv_stream_t stream) {
+    return mv::seg_mean_launch(reinterpret_cast<const half_t*>(x), ld, B, T, C, seg_len, ctx, static_cast<hipStream_t>(stream));
+}
+
+int mv_se_gate_residual_f16(const void* y, int64_t ldy, const float* gate, const void* res, int64_t ldr, void* out, int64_t ldo, int32_t B,
+                            int32_t T, int32_t C, mv_stream_t stream) {
+    return mv::se_gate_residual_launch(reinterpret_cast<const half_t*>(y), ldy, gate, reinterpret_cast<const half_t*>(res), ldr,
+                                       reinterpret_cast<half_t*>(out), ldo, B, T, C, static_cast<hipStream_t>(stream));
+}
+
+int mv_asp_hidden_act_f16(void* zh, const float* row_bias, const float* scale, const float* shift, int32_t B, int32_t T, int32_t A,
+                          mv_stream_t stream) {
+    return mv::asp_hidden_act_launch(reinterpret_cast<half_t*>(zh), row_bias, scale, shift, B, T, A, static_cast<hipStream_t>(stream));
+}
+
+int mv_cast_pad_f16(const float* src, void* dst, int32_t B, int32_t T, int32_t F, int64_t ldd, int32_t pad, mv_stream_t stream) {
+    return mv::cast_pad_launch(src, reinterpret_cast<half_t*>(dst), B, T, F, ldd, pad, static_cast<hipStream_t>(stream));
+}
+
+int mv_cast_rows_f16(const float* src, int64_t lds, void* dst, int64_t ldd, int64_t n_rows, int32_t C, mv_stream_t stream) {
+    return mv::cast_rows_f32_f16_launch(src, lds, reinterpret_cast<half_t*>(dst), ldd, n_rows, C, static_cast<hipStream_t>(stream));
+}
+
+int mv_copy_slice_f16(const void* src, int64_t lds, void* dst, int64_t ldd, int32_t C, int64_t n_rows, mv_stream_t stream) {
+    return mv::copy_slice_launch(reinterpret_cast<const half_t*>(src), lds, reinterpret_cast<half_t*>(dst), ldd, C, n_rows,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int mv_pad_rows_f32(const float* src, int32_t F, float* dst, int64_t ldd, int64_t n_rows, mv_stream_t stream) {
+    return mv::pad_rows_f32_launch(src, F, dst, ldd, n_rows, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -211,6 +211,14 @@ _SIGNATURES = {
     'mv_fcm_c1_pack': (c_i32, [c_vp, c_vp]),
     'mv_time_stats_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_f32, c_vp]),
     'mv_bn_relu_rows_f16': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp]),
+    'mv_time_stats_ex_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    'mv_seg_mean_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'mv_se_gate_residual_f16': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp]),
+    'mv_asp_hidden_act_f16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    'mv_cast_pad_f16': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i64, c_i32, c_vp]),
+    'mv_cast_rows_f16': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_vp]),
+    'mv_copy_slice_f16': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i64, c_vp]),
+    'mv_pad_rows_f32': (c_i32, [c_vp, c_i32, c_vp, c_i64, c_i64, c_vp]),
     'mv_cam_dense_block_workspace_bytes': (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     'mv_cam_dense_block_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32] + [ctypes.POINTER(c_vp)] * 10 +
                                [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_vp, c_sz, c_vp]),
