@@ -272,7 +272,7 @@ int mv_mfcc_forward_varlen(const MvMfcc* h, const float* wav, int32_t B, int64_t
  * Front-end 5: a HuggingFace Wav2Vec2 / WavLM model's `extract_features` + time-mean subtraction + mask.  Replaces
  * AudioFeaturizer(use_hf_model=True) (featurizer.py:20-39: AutoModel + AutoFeatureExtractor; forward :60-76 keeps
  * outputs.extract_features alone) and featurizer.py:77-90.  What is evaluated: the processor's per-row z-score
- * (x - mean) / sqrt(var + 1e-7) over the whole padded row (do_normalize), the convolutional feature encoder
+ * (x - mean) / sqrt(var + 1e-7) over the whole padded row (do_normalize; over the row's own samples in mv_hfenc_forward_varlen), the convolutional feature encoder
  * (feature_extractor.conv_layers.*: unpadded strided Conv1d -> GroupNorm on layer 0 ("group") or LayerNorm on every layer
  * ("layer") -> exact GELU) and feature_projection.layer_norm; the transformer behind them, whose output the reference
  * discards, is not.  Layer 0 runs in exact fp32; the other layers are fp16-operand convolutions on channel-last fp16
@@ -316,6 +316,19 @@ int mv_hfenc_workspace_bytes(const MvHfEncoder* h, int32_t B, int64_t L, size_t*
  * bits depend on the row alone: not on B, the other rows or the stream. */
 int mv_hfenc_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
                      float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+/* Variable-length batch (additive since ABI 5; the contract of mv_melspec_forward_varlen): row b holds n_b = clamp(num_samples[b], 0, L) valid
+ * samples (device array, int64, B entries, read on the device only; NULL is refused).  Frames 0 .. T'(n_b) - 1 of row b are what mv_hfenc_forward
+ * of the same handle gives for that row alone as a [1, n_b] batch without a ratio, and BIT FOR BIT so ("group" and "layer" mode, with and without
+ * do_normalize, conv_bias and subtract_time_mean); the output keeps the shape [B, T'(L), conv_dim[last]] and its frames t >= T'(n_b) are zero:
+ *   - the z-score, layer 0's GroupNorm statistics and the time mean run over the row's own n_b samples / T_0(n_b) / T'(n_b) frames, summed in
+ *     orders that depend on these counts alone (not on L, B, the other rows or the stream);
+ *   - the samples behind n_b are never read into a result (NaN included): layer 0 loads them as zeros and stores zeros behind the row's own
+ *     frames; the further layers run over all T_i(L) frames and hold finite filler behind a row's own count, which no valid frame reads;
+ *   - a row below the receptive field (n_b = 0 included) is all zero and no error, whatever subtract_time_mean says.
+ * The call is refused when T'(L) <= 0, as mv_hfenc_forward refuses it; the other checks are those of the forward on (B, L), the workspace is
+ * the one mv_hfenc_workspace_bytes(h, B, L) reports. */
+int mv_hfenc_forward_varlen(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples,
+                            float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream);
 /* The same forward with HIP events between its stages (tools/bench_hf_frontend.py; a measurement hook like mv_profile_*: not thread-safe, WAITS for
  * the forward, ONE DEVICE per process -- its events are created at the first call, on the device current then, and kept).  stage_ms_host: HOST array of num_stages = num_layers + 1 floats = milliseconds of layer 0 (with the z-score), of every further layer
  * (conv + its GELU / LayerNorm pass) and of the tail (feature_projection.layer_norm + time mean + mask). */

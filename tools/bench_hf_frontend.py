@@ -5,6 +5,13 @@ same run, one dense 1x1 layer of the FLOPs of encoder layer 1 (K = 3 * 512, N = 
 on this box for that much work.  Reported, not promised: no threshold.
 
     python tools/bench_hf_frontend.py [--batch 256] [--seconds 3] [--iters 10] [--norm group|layer]
+
+--varlen: the variable-length form instead.  64 rows and 256 rows of seeded uniform 1-3 s lengths, width 512, both norms: one
+mv_hfenc_forward_varlen call on the padded batch against the per-row loop it replaced in AudioFeaturizer.forward_varlen (the lengths read back
+once, then h(wav[b:b+1, :n_b]) row by row into a zeroed output), timed the same way; beside them the stages of the fixed-length forward on the
+padded batch (what the one call computes: every row at the padded length).  Reported, not promised.
+
+    python tools/bench_hf_frontend.py --varlen [--iters 10]
 """
 import argparse
 import ctypes
@@ -31,13 +38,65 @@ def timed(fn, iters, warmup=3):
     return ms[len(ms) // 2], ms[0]
 
 
+def per_row_loop(h, wav, num_samples, min_len):
+    """AudioFeaturizer.forward_varlen's device path before mv_hfenc_forward_varlen: one read-back, then every row alone"""
+    T = h(wav[:1]).size(1)
+    out = torch.zeros((wav.size(0), T, h.dim), dtype=torch.float32, device=wav.device)
+    lens = [int(n) for n in num_samples.tolist()]
+    for i in range(wav.size(0)):
+        n = min(max(lens[i], 0), wav.size(1))
+        if n < min_len:
+            continue
+        f = h(wav[i:i + 1, :n])
+        out[i, :f.size(1)] = f[0]
+    return out
+
+
+def varlen(iters):
+    import hf_cases as hc
+    import hf_ref
+    from mvector import _hip
+    from oracle import frontend
+    dev = torch.device('cuda:0')
+    print(f'# {torch.cuda.get_device_name(0)}; wav2vec2-base geometry, width 512, seeded uniform lengths of 1-3 s; medians (best) of {iters} runs, HIP events')
+    for norm in ('group', 'layer'):
+        cfg, sd = hc.seeded_model(norm)
+        h = _hip.HfEncoder(cfg, {k: v.to(dev) for k, v in sd.items()})
+        min_len = hf_ref.receptive_field(cfg)
+        for B in (64, 256):
+            g = torch.Generator().manual_seed(B)
+            lens = torch.randint(16000, 48001, (B,), generator=g)
+            L = int(lens.max())
+            wav = frontend.synth_waveforms(B, L, seed=2)
+            for b in range(B):
+                wav[b, int(lens[b]):] = 0.0
+            wav, n = wav.to(dev), lens.to(dev)
+            one = h(wav, None, n)
+            assert torch.equal(one, per_row_loop(h, wav, n, min_len)), 'the one call and the per-row loop differ'
+            one_med, one_best = timed(lambda: h(wav, None, n), iters)
+            loop_med, loop_best = timed(lambda: per_row_loop(h, wav, n, min_len), iters)
+            stages = []
+            for _ in range(iters + 3):
+                ms = []
+                h(wav, stage_ms=ms)
+                stages.append(ms)
+            stages = stages[3:]
+            med = [sorted(r[i] for r in stages)[len(stages) // 2] for i in range(len(stages[0]))]
+            print(f'{norm:5s} B = {B:3d}, L = {L} (mean length {float(lens.float().mean()):.0f}, padding {1 - float(lens.sum()) / (B * L):.1%} of the batch): '
+                  f'one call {one_med:8.3f} ms ({one_best:.3f}), per-row loop {loop_med:8.3f} ms ({loop_best:.3f}), loop / one call = {loop_med / one_med:.2f}; same bits')
+            print(f'      fixed-length forward on the padded batch, per stage (layers 0-6, tail): ' + ' '.join(f'{m:.3f}' for m in med) + f' = {sum(med):.3f} ms')
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--varlen', action='store_true')
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--seconds', type=float, default=3.0)
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--norm', default='group', choices=['group', 'layer'])
     a = ap.parse_args()
+    if a.varlen:
+        return varlen(a.iters)
     import hf_cases as hc
     from mvector import _hip
     from oracle import frontend

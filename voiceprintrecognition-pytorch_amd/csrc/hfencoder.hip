@@ -2,7 +2,7 @@
 // `outputs.extract_features` alone -- the convolutional feature encoder followed by feature_projection.layer_norm (the transformer behind it is never
 // evaluated here).  Activations are channel-last fp16 [B, T, C]; statistics and normalisations are fp32 (sums that can cancel: fp64).
 //
-//   processor   per-row z-score of the waveform, (x - mean) / sqrt(var + 1e-7) over the whole padded row   hf_wave_stats_kernel + on load in layer 0
+//   processor   per-row z-score of the waveform, (x - mean) / sqrt(var + 1e-7) over the row's own samples   hf_wave_stats_kernel + on load in layer 0
 //   layer 0     1 -> C0, k0 taps, stride s0, exact fp32 on the vector unit (33 MFLOP per second of audio)
 //     "group"   GroupNorm(C0, C0): per (utterance, channel) over all frames.  The conv runs TWICE: hf_l0_kernel<STATS> leaves fp64 sums per
 //               128-frame chunk, hf_l0_finish_kernel adds the chunks in chunk order, hf_l0_kernel<APPLY> evaluates the conv again, normalises,
@@ -16,6 +16,16 @@
 // Every reduction is a function of the row's own length: a wave per frame (LayerNorm), fixed 128-frame chunks added in order (GroupNorm), one
 // workgroup per waveform row (z-score), 4 phases (time mean).  Nothing depends on B, the launch form or the stream; the convs are conv1d_launch's,
 // whose tile families accumulate in one order.
+//
+// The row's own length is an ARGUMENT of the four kernels that reduce over it or mask by it: mv_hfenc_forward passes no length array and every row
+// holds L samples; mv_hfenc_forward_varlen passes num_samples and row b holds n_b = clamp(num_samples[b], 0, L) -- the same code, the same
+// summation orders, so row b comes out bit for bit as the forward gives it alone as a [1, n_b] batch.  The convs are valid (no padding): frame
+// t < T_i(n_b) of layer i reads frames < T_{i-1}(n_b) only, whatever lies behind them.  So
+//   z-score     over the row's n_b samples (mean 0, sd 1 at n_b = 0);
+//   layer 0     T0_b = T_0(n_b) frames: a chunk loads and counts its frames below T0_b only (samples at or behind n_b are never read), the
+//               GroupNorm sums run over ceil(T0_b / 128) chunks and divide by T0_b; frames at or behind T0_b are stored as zeros;
+//   layers 1..  and hf_rows_kernel run over all T_i(L) frames: behind a row's own count they hold finite filler that no valid frame reads;
+//   output      the time mean over T'_b = T'(n_b) frames, zeros (by selection) from T'_b on.  A row below the receptive field is all zero.
 #include <vector>
 
 #include "kernels.h"
@@ -28,6 +38,27 @@ constexpr int HF_L0_FR = 128;     // frames of layer 0 per workgroup: the chunk 
 constexpr int HF_L0_MAX_S = 8;    // largest stride of layer 0
 constexpr int HF_L0_MAX_K = 16;   // largest kernel of layer 0
 constexpr int HF_MAX_C = 1024;    // widest frame a wave holds in registers (16 per lane)
+
+// frames behind one valid (unpadded) strided conv: n -> floor((n - k) / s) + 1, 0 as soon as no whole window fits
+__host__ __device__ __forceinline__ int64_t hf_conv_frames(int64_t n, int k, int s) { return n >= k ? (n - k) / s + 1 : 0; }
+
+// kernels and strides of the layers, by value into the kernels that need a row's frame count behind several layers
+struct HfGeom {
+    int n;
+    int k[MV_HFENC_MAX_LAYERS], s[MV_HFENC_MAX_LAYERS];
+};
+
+__host__ __device__ __forceinline__ int64_t hf_frames_behind(const HfGeom& g, int64_t samples) {
+    for (int i = 0; i < g.n; ++i) samples = hf_conv_frames(samples, g.k[i], g.s[i]);
+    return samples;
+}
+
+// valid samples of row b: all L (no length array: the fixed-length forward) or clamp(num_samples[b], 0, L)
+__device__ __forceinline__ int64_t hf_row_len(const int64_t* num_samples, int b, int64_t L) {
+    if (num_samples == nullptr) return L;
+    const int64_t n = num_samples[b];
+    return n < 0 ? 0 : (n > L ? L : n);
+}
 
 __device__ __forceinline__ float hf_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 
@@ -49,19 +80,29 @@ __device__ __forceinline__ double block_sum_f64(double v, double* red) {
     return red[0];
 }
 
-// mean and sqrt(var + 1e-7) (biased variance) of every waveform row: Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm.  One workgroup per row.
-__global__ __launch_bounds__(HF_THREADS) void hf_wave_stats_kernel(const float* wav, int64_t L, int64_t stride, float* stats) {
+// mean and sqrt(var + 1e-7) (biased variance) of every waveform row over its own n samples: Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm.
+// One workgroup per row.  n = 0: mean 0, sd 1 (nothing is loaded with them).
+__global__ __launch_bounds__(HF_THREADS) void hf_wave_stats_kernel(const float* wav, int64_t L, int64_t stride, const int64_t* num_samples,
+                                                                   float* stats) {
     __shared__ double red[HF_THREADS];
     const float* row = wav + (int64_t)blockIdx.x * stride;
+    const int64_t n = hf_row_len(num_samples, blockIdx.x, L);
+    if (n == 0) {   // (uniform per workgroup)
+        if (threadIdx.x == 0) {
+            stats[2 * blockIdx.x] = 0.0f;
+            stats[2 * blockIdx.x + 1] = 1.0f;
+        }
+        return;
+    }
     double s = 0.0;
-    for (int64_t i = threadIdx.x; i < L; i += HF_THREADS) s += (double)row[i];
-    const double mean = block_sum_f64(s, red) / (double)L;
+    for (int64_t i = threadIdx.x; i < n; i += HF_THREADS) s += (double)row[i];
+    const double mean = block_sum_f64(s, red) / (double)n;
     double q = 0.0;
-    for (int64_t i = threadIdx.x; i < L; i += HF_THREADS) {
+    for (int64_t i = threadIdx.x; i < n; i += HF_THREADS) {
         const double d = (double)row[i] - mean;
         q += d * d;
     }
-    const double var = block_sum_f64(q, red) / (double)L;
+    const double var = block_sum_f64(q, red) / (double)n;
     if (threadIdx.x == 0) {
         stats[2 * blockIdx.x] = (float)mean;
         stats[2 * blockIdx.x + 1] = sqrtf((float)var + 1e-7f);
@@ -71,6 +112,7 @@ __global__ __launch_bounds__(HF_THREADS) void hf_wave_stats_kernel(const float* 
 struct HfL0Args {
     const float* wav;      // [B, L] rows wav_stride apart
     int64_t L, wav_stride;
+    const int64_t* num_samples;   // [B] valid samples of every row (variable-length form) or null: L
     const float* wstats;   // [B][2] mean, std of the row (do_normalize) or null
     const float* w;        // [C][k] fp32
     const float* bias;     // [C] or null
@@ -84,14 +126,25 @@ struct HfL0Args {
 
 // One workgroup = one 128-frame chunk of one utterance, every channel: the chunk's samples (z-scored on load) sit in LDS, a thread keeps its
 // channel's taps in registers and walks the frames.  STATS: fp64 sum / sum of squares of the chunk per channel.  APPLY: GroupNorm + GELU (gamma
-// given) or the bare conv + bias, stored fp16 -- consecutive threads store consecutive channels of a frame.
+// given) or the bare conv + bias, stored fp16 -- consecutive threads store consecutive channels of a frame.  The chunk holds its frames below the
+// row's own T0_b = T_0(n_b): STATS counts those alone (a chunk behind them leaves, its sums are never read), APPLY stores zeros from T0_b on
+// and skips the convolution where the whole chunk lies behind it.  Every branch on T0_b is uniform per workgroup.
 template <bool STATS, int KT>
 __global__ __launch_bounds__(HF_THREADS) void hf_l0_kernel(HfL0Args a) {
     __shared__ float xs[HF_L0_FR * HF_L0_MAX_S + HF_L0_MAX_K];
     const int tid = threadIdx.x, chunk = blockIdx.x, b = blockIdx.y;
     const int t0 = chunk * HF_L0_FR;
-    const int nf = a.T1 - t0 < HF_L0_FR ? a.T1 - t0 : HF_L0_FR;
-    const int ns = (nf - 1) * a.s + a.k;                       // samples of the chunk (inside the row: t0 + nf <= T1)
+    const int nslot = a.T1 - t0 < HF_L0_FR ? a.T1 - t0 : HF_L0_FR;     // frames of the chunk in the padded row
+    const int T0b = (int)hf_conv_frames(hf_row_len(a.num_samples, b, a.L), a.k, a.s);
+    const int nf = T0b - t0 < nslot ? T0b - t0 : nslot;          // ... of which the row's own (<= 0: the chunk lies behind them)
+    if (nf <= 0) {
+        if constexpr (!STATS) {
+            half_t* y = a.y + ((int64_t)b * a.T1 + t0) * a.C;
+            for (int i = tid; i < nslot * a.C; i += HF_THREADS) y[i] = (half_t)0.0f;
+        }
+        return;
+    }
+    const int ns = (nf - 1) * a.s + a.k;                       // samples of the chunk (inside the row's own: t0 + nf <= T0_b)
     const float* row = a.wav + (int64_t)b * a.wav_stride + (int64_t)t0 * a.s;
     float mean = 0.0f, sd = 1.0f;
     if (a.wstats != nullptr) {
@@ -134,17 +187,27 @@ __global__ __launch_bounds__(HF_THREADS) void hf_l0_kernel(HfL0Args a) {
                 if (norm) v = hf_gelu((v - m) * r * g + be);
                 y[(int64_t)f * a.C] = (half_t)v;
             }
+            for (int f = nf; f < nslot; ++f) y[(int64_t)f * a.C] = (half_t)0.0f;
         }
     }
 }
 
-// GroupNorm statistics of layer 0: the chunks' fp64 sums added in chunk order -> mean, 1 / sqrt(biased var + eps) per (utterance, channel)
-__global__ void hf_l0_finish_kernel(const double* partial, int B, int nchunk, int C, int T1, float eps, float* cstats) {
+// GroupNorm statistics of layer 0: the fp64 sums of the row's own ceil(T0_b / 128) chunks added in chunk order -> mean, 1 / sqrt(biased var + eps)
+// per (utterance, channel) over its T0_b frames.  T0_b = 0: mean 0, rstd 1 (no frame is normalised with them).
+__global__ void hf_l0_finish_kernel(const double* partial, int B, int nchunk, int C, const int64_t* num_samples, int64_t L, int k0, int s0, float eps,
+                                    float* cstats) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)B * C) return;
     const int b = (int)(i / C), c = (int)(i - (int64_t)b * C);
+    const int T1 = (int)hf_conv_frames(hf_row_len(num_samples, b, L), k0, s0);
+    if (T1 == 0) {
+        cstats[2 * i] = 0.0f;
+        cstats[2 * i + 1] = 1.0f;
+        return;
+    }
+    const int own = (T1 + HF_L0_FR - 1) / HF_L0_FR;
     double s = 0.0, q = 0.0;
-    for (int ch = 0; ch < nchunk; ++ch) {
+    for (int ch = 0; ch < own; ++ch) {
         const double* p = partial + (((int64_t)b * nchunk + ch) * C + c) * 2;
         s += p[0];
         q += p[1];
@@ -223,20 +286,24 @@ __global__ __launch_bounds__(HF_THREADS) void hf_rows_kernel(const half_t* x, vo
     }
 }
 
-// AudioFeaturizer.forward behind the model (featurizer.py:79-90): minus the mean over ALL T frames, then zeros from round(ratio * T) on -- the
-// semantics and the summation order of the other front-ends' cmn_mask_kernel (4 time phases, then their sum).  Workgroup = (utterance, 64 channels).
-__global__ __launch_bounds__(HF_THREADS) void hf_cmn_mask_kernel(float* out, const float* lens_ratio, int T, int C, int cmn) {
+// AudioFeaturizer.forward behind the model (featurizer.py:79-90): minus the mean over ALL frames of the row, then zeros from round(ratio * T) on
+// -- the semantics and the summation order of the other front-ends' cmn_mask_kernel (4 time phases, then their sum).  The row's frames are all T
+// (no length array) or Tb = T'(n_b) of its own samples: the mean runs over and divides by Tb, frames from Tb on are zeros (selected, never
+// multiplied: what lies there is filler), Tb = 0 is an all-zero row.  Workgroup = (utterance, 64 channels).
+__global__ __launch_bounds__(HF_THREADS) void hf_cmn_mask_kernel(float* out, const float* lens_ratio, const int64_t* num_samples, int64_t L, HfGeom g,
+                                                                 int T, int C, int cmn) {
     __shared__ float part[4][64];
     const int b = blockIdx.x, c = blockIdx.y * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
+    const int Tb = num_samples != nullptr ? (int)hf_frames_behind(g, hf_row_len(num_samples, b, L)) : T;
     float* o = out + (int64_t)b * T * C + c;
     float s = 0.0f;
     if (cmn)
-        for (int t = ph; t < T; t += 4) s += o[(int64_t)t * C];
+        for (int t = ph; t < Tb; t += 4) s += o[(int64_t)t * C];
     part[ph][threadIdx.x & 63] = s;
     __syncthreads();
     const int l = threadIdx.x & 63;
-    const float mean = cmn ? (part[0][l] + part[1][l] + part[2][l] + part[3][l]) / (float)T : 0.0f;
-    int mask_len = T;
+    const float mean = cmn && Tb > 0 ? (part[0][l] + part[1][l] + part[2][l] + part[3][l]) / (float)Tb : 0.0f;
+    int mask_len = Tb;
     if (lens_ratio != nullptr) mask_len = (int)rintf(lens_ratio[b] * (float)T);
     for (int t = ph; t < T; t += 4) o[(int64_t)t * C] = t < mask_len ? o[(int64_t)t * C] - mean : 0.0f;
 }
@@ -273,11 +340,11 @@ namespace {
 
 using namespace mv;
 
-// frames behind every layer: n -> floor((n - k) / s) + 1, <= 0 as soon as a layer has no whole window
+// frames behind every layer (hf_conv_frames, the device's own count), 0 as soon as a layer has no whole window
 void hf_frames(const MvHfEncoderCfg& c, int64_t L, int64_t* T) {
     int64_t n = L;
     for (int i = 0; i < c.num_layers; ++i) {
-        n = n >= c.conv_kernel[i] ? (n - c.conv_kernel[i]) / c.conv_stride[i] + 1 : 0;
+        n = hf_conv_frames(n, c.conv_kernel[i], c.conv_stride[i]);
         T[i] = n;
     }
 }
@@ -439,9 +506,10 @@ int mv_hfenc_workspace_bytes(const MvHfEncoder* h, int32_t B, int64_t L, size_t*
 
 namespace {
 
+// The forward of both forms: lens_ratio (batch form, or neither) or num_samples (variable-length form: a device array the kernels read), never both.
 // ev (optional, num_layers + 2 events): recorded in front of layer 0 (the z-score counts as layer 0's), behind every layer and behind the tail
-int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, float* out,
-               void* workspace, size_t workspace_bytes, mv_stream_t stream_, hipEvent_t* ev) {
+int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, const int64_t* num_samples,
+               float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream_, hipEvent_t* ev) {
     MV_REQUIRE(h != nullptr && wav != nullptr && out != nullptr, "mv_hfenc_forward: null argument");
     MV_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "mv_hfenc_forward: out must be 16-byte aligned");
     MV_REQUIRE(B > 0 && B <= 65535, "mv_hfenc_forward: batch size must be 1 .. 65535");
@@ -463,13 +531,14 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
 
     if (ev != nullptr) MV_HIP_OK(hipEventRecord(ev[0], stream));
     if (c.do_normalize) {
-        MV_LAUNCH(hf_wave_stats_kernel, (B, 1, 1), (HF_THREADS, 1, 1), 0, stream, wav, L, wav_stride, s.wstats);
+        MV_LAUNCH(hf_wave_stats_kernel, (B, 1, 1), (HF_THREADS, 1, 1), 0, stream, wav, L, wav_stride, num_samples, s.wstats);
         if ((rc = check_launch("hf_wave_stats_kernel"))) return rc;
     }
     HfL0Args a = {};
     a.wav = wav;
     a.L = L;
     a.wav_stride = wav_stride;
+    a.num_samples = num_samples;
     a.wstats = c.do_normalize ? s.wstats : nullptr;
     a.w = h->w0;
     a.bias = h->bias[0];
@@ -486,7 +555,7 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
         if ((rc = check_launch("hf_l0_kernel<STATS>"))) return rc;
         const int64_t bc = (int64_t)B * a.C;
         MV_LAUNCH(hf_l0_finish_kernel, ((unsigned)ceil_div(bc, HF_THREADS), 1, 1), (HF_THREADS, 1, 1), 0, stream, (const double*)s.partial, B, a.nchunk,
-                  a.C, a.T1, 1e-5f, s.cstats);
+                  a.C, num_samples, L, a.k, a.s, 1e-5f, s.cstats);
         if ((rc = check_launch("hf_l0_finish_kernel"))) return rc;
         a.gamma = h->ln_w[0];
         a.beta = h->ln_b[0];
@@ -526,7 +595,14 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
     }
     const int CL = c.conv_dim[n - 1], TL = (int)T[n - 1];
     if ((rc = hf_rows_launch<HF_ROWS_LN_F32>(s.buf[(n - 1) & 1], out, h->proj_w, h->proj_b, c.layer_norm_eps, (int64_t)B * TL, CL, stream))) return rc;
-    MV_LAUNCH(hf_cmn_mask_kernel, (B, CL / 64, 1), (HF_THREADS, 1, 1), 0, stream, out, lens_ratio, TL, CL, c.subtract_time_mean ? 1 : 0);
+    HfGeom g = {};
+    g.n = n;
+    for (int i = 0; i < n; ++i) {
+        g.k[i] = c.conv_kernel[i];
+        g.s[i] = c.conv_stride[i];
+    }
+    MV_LAUNCH(hf_cmn_mask_kernel, (B, CL / 64, 1), (HF_THREADS, 1, 1), 0, stream, out, lens_ratio, num_samples, L, g, TL, CL,
+              c.subtract_time_mean ? 1 : 0);
     if ((rc = check_launch("hf_cmn_mask_kernel"))) return rc;
     if (ev != nullptr) MV_HIP_OK(hipEventRecord(ev[n + 1], stream));
     return MV_OK;
@@ -538,7 +614,13 @@ extern "C" {
 
 int mv_hfenc_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, float* out,
                      void* workspace, size_t workspace_bytes, mv_stream_t stream) {
-    return hf_forward(h, wav, B, L, wav_stride, lens_ratio, out, workspace, workspace_bytes, stream, nullptr);
+    return hf_forward(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, workspace, workspace_bytes, stream, nullptr);
+}
+
+int mv_hfenc_forward_varlen(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples, float* out,
+                            void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    MV_REQUIRE(num_samples != nullptr, "mv_hfenc_forward_varlen: null length array");
+    return hf_forward(h, wav, B, L, wav_stride, nullptr, num_samples, out, workspace, workspace_bytes, stream, nullptr);
 }
 
 int mv_hfenc_forward_timed(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, float* out,
@@ -552,7 +634,7 @@ int mv_hfenc_forward_timed(const MvHfEncoder* h, const float* wav, int32_t B, in
         for (hipEvent_t& e : ev) MV_HIP_OK(hipEventCreate(&e));
         have = true;
     }
-    const int rc = hf_forward(h, wav, B, L, wav_stride, lens_ratio, out, workspace, workspace_bytes, stream, ev);
+    const int rc = hf_forward(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, workspace, workspace_bytes, stream, ev);
     if (rc != MV_OK) return rc;
     MV_HIP_OK(hipEventSynchronize(ev[n + 1]));
     for (int i = 0; i <= n; ++i) MV_HIP_OK(hipEventElapsedTime(&stage_ms_host[i], ev[i], ev[i + 1]));

@@ -204,6 +204,7 @@ _SIGNATURES = {
     'mv_hfenc_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
     'mv_hfenc_workspace_bytes': (c_i32, [c_vp, c_i32, c_i64, ctypes.POINTER(c_sz)]),
     'mv_hfenc_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_hfenc_forward_varlen': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_hfenc_forward_timed': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp, ctypes.POINTER(c_f32), c_i32]),
     'mv_fcm_conv3x3_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'mv_fcm_block_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
@@ -691,9 +692,15 @@ class HfEncoder:
         check(self._cdll.mv_hfenc_num_frames(self._h, num_samples, ctypes.byref(t)), self._cdll)
         return t.value
 
-    def __call__(self, wav, lens_ratio=None, stage_ms=None):
-        """wav [B, L] fp32 -> [B, T', dim] fp32 on the same device, the caller's stream, a workspace per call.  ``stage_ms``: a list that receives
-        the milliseconds of every layer and of the tail (mv_hfenc_forward_timed: waits for the forward; tools only)"""
+    def __call__(self, wav, lens_ratio=None, num_samples=None, stage_ms=None):
+        """wav [B, L] fp32 -> [B, T', dim] fp32 on the same device, the caller's stream, a workspace per call.  ``lens_ratio``: the reference's
+        batched semantics (mean over all T' frames, then mask).  ``num_samples`` (int64 [B]): every row featurised on its own length, zero
+        frames beyond it (mv_hfenc_forward_varlen; the lengths go to the device and are never read back).  ``stage_ms``: a list that receives
+        the milliseconds of every layer and of the tail (mv_hfenc_forward_timed: waits for the forward; tools only; not with ``num_samples``)"""
+        if lens_ratio is not None and num_samples is not None:
+            raise ValueError('lens_ratio and num_samples are mutually exclusive')
+        if num_samples is not None and stage_ms is not None:
+            raise ValueError('stage_ms times the fixed-length forward: it cannot be combined with num_samples')
         assert wav.dim() == 2 and wav.dtype == torch.float32
         if wav.stride(1) != 1:
             wav = wav.contiguous()
@@ -705,6 +712,13 @@ class HfEncoder:
         check(self._cdll.mv_hfenc_workspace_bytes(self._h, B, L, ctypes.byref(need)), self._cdll)
         ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=wav.device)
         out = torch.empty((B, max(T, 1), self.dim), dtype=torch.float32, device=wav.device)   # (T <= 0: the forward refuses, with its message)
+        if num_samples is not None:
+            num_samples = torch.as_tensor(num_samples).to(device=wav.device, dtype=torch.int64).contiguous()
+            if num_samples.shape != (B,):
+                raise ValueError(f'num_samples must have shape ({B},), got {tuple(num_samples.shape)}')
+            check(self._cdll.mv_hfenc_forward_varlen(self._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
+                                                     ws.data_ptr(), need.value, current_stream(wav)), self._cdll)
+            return out
         if lens_ratio is not None:
             lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
         if stage_ms is not None:

@@ -5,7 +5,7 @@ Device rule
 -----------
 * ``use_hf_model=True`` (``feature_method`` = a local folder or cached name of a HuggingFace Wav2Vec2 / WavLM model): the reference keeps
   ``outputs.extract_features`` alone -- the processor's z-score, the convolutional feature encoder and ``feature_projection.layer_norm``.  CUDA
-  tensors run them in ``mv_hfenc_forward`` and stay on the device (the reference calls ``.numpy()`` and cannot take them at all); CPU tensors run
+  tensors run them in ``mv_hfenc_forward`` (``forward_varlen``: ``mv_hfenc_forward_varlen``, one call per batch) and stay on the device (the reference calls ``.numpy()`` and cannot take them at all); CPU tensors run
   the HF module's own ``feature_extractor`` + ``feature_projection.layer_norm`` in torch.  The transformer behind them, whose output the reference
   throws away, is never evaluated.
 * CUDA (ROCm) tensors: ``mv_fbank_forward`` / ``mv_melspec_forward`` / ``mv_spectrogram_forward`` / ``mv_mfcc_forward`` --
@@ -139,13 +139,12 @@ class AudioFeaturizer(nn.Module):
         """Zero-padded waveforms [B, L] + true lengths int64 [B] -> [B, T(L), feature_dim]: every row is featurised on its
         own length (own frame count, own padding, own time mean, own MFCC dB floor) and rows beyond it are zero -- what the
         reference's evaluation path gets from per-utterance featurisation + ``collate_fn`` padding.  CUDA tensors: one native
-        call per batch for every method (``mv_*_forward_varlen``), no per-row loop and no host synchronisation; a row too short
-        for the transform is all zero.  CPU tensors: the per-row loop.  The HuggingFace front-end is the exception on CUDA: it has no
-        batched variable-length form, so its rows go through the device forward one by one (the lengths are read back to the host
-        once); a row below the encoder's receptive field (400 samples) is all zero there and on the CPU."""
+        call per batch for every method and for the HuggingFace front-end (``mv_*_forward_varlen``, ``mv_hfenc_forward_varlen``), no per-row
+        loop and no host synchronisation; a row too short for the transform -- below the encoder's receptive field (400 samples) with
+        ``use_hf_model`` -- is all zero.  CPU tensors: the per-row loop, with the same all-zero rows."""
         if waveforms.dtype != torch.float32:
             waveforms = waveforms.float()
-        if waveforms.is_cuda and not self.use_hf_model:   # (the HF front-end has no batched variable-length form: the per-row loop, on the device)
+        if waveforms.is_cuda:
             with torch.cuda.device(waveforms.device):
                 return self._handle(waveforms.device)(waveforms, None, num_samples)
         T = self.forward(waveforms[:1]).size(1)
