@@ -200,7 +200,7 @@ int mv_melspec_forward_varlen(const MvMelSpec* h, const float* wav, int32_t B, i
  * subtraction + mask.  Replaces torchaudio.transforms.Spectrogram(**method_args) (featurizer.py:43-44)
  * and featurizer.py:77-90.  Output [B, T, n_fft / 2 + 1].  The STFT fields mean what they mean in
  * MvMelSpecCfg.  n_fft = 400: one launch (melspec_tile_kernel's FFT); any other n_fft: dense DFT +
- * spec_cmn_mask_kernel.  Additive since ABI 5.
+ * cmn_mask_kernel.  Additive since ABI 5.
  * ------------------------------------------------------------------------------------------------ */
 typedef struct MvSpectrogramCfg {
     int32_t n_fft;       /* 400 */

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import layer_checks as lc
 import spectral_ref as sr
 from helpers import cos_dist, load_case
 from oracle import frontend, models as omodels, weights
@@ -45,6 +46,22 @@ def test_gpu_spectrogram_matches_restatement(args):
     if args:
         wav, ratio = wav[:32], ratio[:32]
     _spec_check(AudioFeaturizer('Spectrogram', method_args=args)(wav.to(DEV), ratio.to(DEV)), wav, ratio, args)
+
+
+@pytest.mark.parametrize('method,args', [('MelSpectrogram', dict(n_fft=600, n_mels=80)), ('Spectrogram', dict(n_fft=600))], ids=str)
+def test_gpu_dense_path_time_mean_and_mask(method, args):
+    """the device twin of test_emu_dense_path_time_mean_and_mask: cmn_mask_kernel in place (80 mel columns) and from the padded bin rows
+    (301 of 304), two rows, the second one masked"""
+    from mvector import _hip
+    wav, ratio = frontend.synth_waveforms(2, 6000, seed=12), torch.tensor([1.0, 0.55])
+    h = {'MelSpectrogram': _hip.MelSpec, 'Spectrogram': _hip.Spectrogram}[method](args)
+    assert h.info()['kernel'] == 'stft_power_kernel (dense DFT)'
+    out = h(wav.to(DEV), ratio.to(DEV))
+    if method == 'Spectrogram':
+        _spec_check(out, wav, ratio, args)
+    else:
+        lc.melspec_case(_hip.lib(), DEV, wav, ratio, args)
+    assert bool((out[1, int(torch.round(ratio[1] * out.shape[1])):] == 0).all()) and bool((out[0] != 0).any())
 
 
 @pytest.mark.parametrize('args', [{}, dict(n_mfcc=13), dict(n_mfcc=80), dict(norm=None), dict(log_mels=True),

@@ -5,6 +5,7 @@ import pytest
 import scipy.fft
 import torch
 
+import layer_checks as lc
 import spectral_ref as sr
 from emu_lib import emu_cdll
 from mvector import _hip
@@ -87,11 +88,15 @@ def test_cpu_mfcc_matches_restatement(args):
     ('Spectrogram', dict(onesided=False), NotImplementedError), ('Spectrogram', dict(normalized='x'), ValueError),
     ('MFCC', dict(dct_type=3), ValueError), ('MFCC', dict(n_mfcc=41, melkwargs=dict(n_mels=40)), ValueError),
     ('MFCC', dict(norm='backward'), AssertionError), ('MFCC', dict(n_mels=40), TypeError),
-    ('MFCC', dict(melkwargs=dict(sample_rate=8000)), TypeError), ('MFCC', dict(melkwargs=dict(window='x')), TypeError)])
+    ('MFCC', dict(melkwargs=dict(sample_rate=8000)), TypeError), ('MFCC', dict(melkwargs=dict(window='x')), TypeError),
+    ('MelSpectrogram', dict(power=None), NotImplementedError), ('MelSpectrogram', dict(onesided=False), NotImplementedError),
+    ('MelSpectrogram', dict(normalized='x'), ValueError), ('MelSpectrogram', dict(pad_mode='x'), NotImplementedError),
+    ('MelSpectrogram', dict(n_mfcc=13), TypeError), ('MelSpectrogram', dict(norm='x'), ValueError),
+    ('MelSpectrogram', dict(mel_scale='x'), ValueError)])
 def test_argument_errors(method, args, exc):
     with pytest.raises(exc):
         AudioFeaturizer(method, method_args=args)
-    cls = {'Spectrogram': _hip.Spectrogram, 'MFCC': _hip.Mfcc}[method]
+    cls = {'Spectrogram': _hip.Spectrogram, 'MFCC': _hip.Mfcc, 'MelSpectrogram': _hip.MelSpec}[method]
     with pytest.raises(exc):
         cls(args, cdll=emu_cdll())
 
@@ -180,11 +185,26 @@ def test_emu_spectrogram_default_geometry():
 
 
 def test_emu_spectrogram_dense_geometries():
-    """power-of-two and other n_fft: stft_power_kernel + spec_cmn_mask_kernel"""
+    """power-of-two and other n_fft: stft_power_kernel + cmn_mask_kernel reading the padded bin rows"""
     wav = _wav(2, 2400, 8)
     for args in (dict(n_fft=512, hop_length=256), dict(n_fft=600), dict(n_fft=256, win_length=200, hop_length=80, center=False)):
         assert _hip.Spectrogram(args, cdll=emu_cdll()).info()['kernel'] == 'stft_power_kernel (dense DFT)'
         _emu_case('Spectrogram', wav, torch.tensor([1.0, 0.55]), args, None)
+
+
+@pytest.mark.parametrize('method,args', [('MelSpectrogram', dict(n_fft=600, n_mels=80)), ('Spectrogram', dict(n_fft=600))], ids=str)
+def test_emu_dense_path_time_mean_and_mask(method, args):
+    """n_fft 600 = the dense DFT, whose time mean and mask are cmn_mask_kernel: in place behind the mel projection (80 columns: one block
+    of 64 and a tail of 16), from stft_power_kernel's padded bin rows for the Spectrogram (301 columns in rows of 304); the second row masked"""
+    wav, ratio = _wav(2, 6000, 12), torch.tensor([1.0, 0.55])
+    if method == 'Spectrogram':
+        _emu_case(method, wav, ratio, args, None)
+        return
+    h = _hip.MelSpec(args, cdll=emu_cdll())
+    assert h.info()['kernel'] == 'stft_power_kernel (dense DFT)'
+    lc.melspec_case(emu_cdll(), 'cpu', wav, ratio, args)
+    out = h(wav, ratio)
+    assert bool((out[1, int(torch.round(ratio[1] * out.shape[1])):] == 0).all()) and bool((out[0] != 0).any())
 
 
 def test_emu_mfcc_default_geometry():

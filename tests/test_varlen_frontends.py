@@ -101,3 +101,24 @@ def test_varlen_entry_points_refuse_bad_arguments(method):
     assert fwd(h._h, padded.data_ptr(), B, vc.L, vc.L, n.data_ptr(), None, ws.data_ptr(), need, None) != 0
     assert 'null buffer' in cd.mv_last_error().decode()
     assert fwd(h._h, padded.data_ptr(), B, vc.L, vc.L, n.data_ptr(), out.data_ptr(), ws.data_ptr(), need, None) == 0
+
+
+@pytest.mark.parametrize('args,min_len,msg', [
+    (dict(n_fft=64), 33, 'reflect padding needs more than n_fft/2 samples'),                 # the transform kernels reflect themselves
+    (dict(n_fft=64, pad=3), 33, 'reflect padding needs more than n_fft/2 samples'),          # the extension pass; the 2 x 3 zeros count
+    (dict(n_fft=64, pad_mode='circular'), 32, 'circular padding needs at least n_fft/2 samples'),
+    (dict(n_fft=64, pad_mode='replicate'), 1, None), (dict(n_fft=64, pad_mode='constant'), 1, None)], ids=str)
+def test_shortest_row_is_the_same_for_the_batch_form_and_the_variable_length_form(args, min_len, msg):
+    """one frame rule on the host and on the device: the batch form refuses a call of min_len - 1 samples (pad counted) under reflect and
+    circular padding and takes min_len; a row of the variable-length form has no frames below min_len and its own frames from there on"""
+    h = _hip.Spectrogram(args, subtract_time_mean=False, cdll=emu_cdll())   # (no mean: the two frames of a wrapped-round row are equal)
+    n = min_len - 2 * args.get('pad', 0)
+    wav = vc.batch()[1][:2, :n + 5].contiguous()
+    if msg is not None:
+        with pytest.raises(RuntimeError, match=msg):
+            h(wav[:, :n - 1])
+    alone = h(wav[1:, :n])
+    assert alone.shape[1] == h.num_frames(n) and bool((alone != 0).any())
+    out = h(wav, None, torch.tensor([n - 1, n]))
+    assert bool((out[0] == 0).all())
+    assert torch.equal(out[1, :alone.shape[1]], alone[0]) and bool((out[1, alone.shape[1]:] == 0).all())

@@ -29,7 +29,7 @@ CASES = [
     ('MelSpectrogram', dict(pad=7, pad_mode='replicate')),        # the extension pass repeating the edge value at n_b
     ('Spectrogram', dict(pad_mode='circular', hop_length=160)),   # the extension pass wrapping round at n_b
     ('Spectrogram', {}),                                          # melspec_tile_kernel<spectrogram>
-    ('Spectrogram', dict(n_fft=512)),                             # dense DFT + spec_cmn_mask_kernel
+    ('Spectrogram', dict(n_fft=512)),                             # dense DFT + cmn_mask_kernel from the padded bin rows
     ('MFCC', {}),                                                 # per-row dB floor
     ('MFCC', dict(log_mels=True)),
     ('MFCC', dict(melkwargs=dict(n_fft=600))),

@@ -110,14 +110,23 @@ constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHL4 = 0x104, DPP_ROW_SHL8 = 0x108;
 // ---- variable-length batches of the STFT front-ends (mv_melspec / mv_spectrogram / mv_mfcc _forward_varlen) ---------------
 // Every kernel of that path takes one of these.  num_samples == nullptr is the batch form: every row has the kernel's own L
 // samples and T frames.  Otherwise row b has clamp(num_samples[b], 0, L) samples and is transformed exactly as a [1, n_b] batch
-// would be: its own frame count (the rule of mv_melspec_num_frames), its own padding at n_b, its own time mean.
+// would be: its own frame count (stft_num_frames), its own padding at n_b, its own time mean.
 struct RowLens {
     const int64_t* num_samples;   // [B] on the device, or nullptr
     int64_t L;                    // the caller's row length (the clamp)
     int64_t extra;                // samples melspec_extend_kernel puts around every row (0: the transform kernels pad themselves)
     int32_t cfg_pad, center, n_fft, hop;
-    int32_t min_len;              // fewest samples, cfg.pad included, that the centre padding accepts (torch.stft raises below it)
+    int32_t min_len;              // centre padding: fewest samples, cfg.pad included, that give a frame -- what torch.stft's reflect / circular padding
+                                  // accepts, one sample otherwise (nothing to pad: F.pad's replicate raises on an empty signal too)
 };
+
+// The frame rule of the STFT front-ends, host and device: the frames of a row of n samples.  cfg_pad zeros on either side count as samples;
+// under centre padding a row below min_len has no frames (mv_melspec_num_frames passes 0: the batch form refuses such a call instead).
+__host__ __device__ inline int64_t stft_num_frames(int64_t n, int cfg_pad, int center, int n_fft, int hop, int64_t min_len) {
+    const int64_t lp = n + 2 * (int64_t)cfg_pad;
+    if (center) return lp < min_len ? 0 : 1 + lp / hop;
+    return lp < n_fft ? 0 : 1 + (lp - n_fft) / hop;
+}
 
 __device__ __forceinline__ int64_t row_samples(const RowLens& v, int b) {
     const int64_t n = v.num_samples[b];
@@ -131,10 +140,9 @@ __device__ __forceinline__ int row_frames(const RowLens& v, int b, int64_t L_all
         *len = L_all;
         return T_all;
     }
-    const int64_t n = row_samples(v, b), lp = n + 2 * (int64_t)v.cfg_pad;
+    const int64_t n = row_samples(v, b);
     *len = n + v.extra;
-    if (v.center) return (lp < v.min_len || lp == 0) ? 0 : (int)(1 + lp / v.hop);   // (nothing to pad: F.pad's replicate raises on an empty signal too)
-    return lp < v.n_fft ? 0 : (int)(1 + (lp - v.n_fft) / v.hop);
+    return (int)stft_num_frames(n, v.cfg_pad, v.center, v.n_fft, v.hop, v.min_len);
 }
 
 // ---- banded mel stage on v_mfma_f32_4x4x1 -------------------------------------------------------------------------------

@@ -13,9 +13,15 @@
 //                       for 8 MFMA chains).
 //   mel projection      exact-fp32 GEMM (linear.hip) against the transposed filterbank.
 //   cmn_mask_kernel     column means over ALL frames (padded ones included, featurizer.py:79), subtract, zero the frames
-//                       t >= round_half_even(ratio * T).
+//                       t >= round_half_even(ratio * T); in place behind the mel projection, or from stft_power_kernel's padded
+//                       bin rows when the handle is a Spectrogram (spectral.hip) and the bins are the features.
+// Host side: melspec_create_mode checks the configuration and builds the tables piece by piece; melspec_forward_rows is checks ->
+// optional melspec_extend_kernel -> one of tile_forward (n_fft 400), pow2_forward (melfft.hip) or dense_forward (the kernels above).
+// The frame count of a row is stft_num_frames (frontend_common.h) on the host and on the device.
 // hipcc-flags: -fno-slp-vectorize -fno-signed-zeros
 //   (see fbank.hip: scalar chains stay scalar instead of being re-packed into v_pk_* ops behind register shuffles)
+#include <memory>
+#include <string>
 #include <vector>
 
 #include "frontend_common.h"
@@ -566,12 +572,15 @@ __global__ __launch_bounds__(MST_WAVES * 64) void melspec_tile_kernel(MelTileArg
     }
 }
 
-// out[b, t, c] -= mean_t out[b, :, c]; frames t >= mask_len zeroed.  One workgroup per utterance.  Variable-length form (rows): the mean is taken
-// over the row's own Tb frames -- four time phases whose members depend on Tb alone -- and the frames behind them are zeroed.
-__global__ __launch_bounds__(256) void cmn_mask_kernel(float* out, int T, int C, const float* lens_ratio, int cmn, RowLens rows) {
-    __shared__ float part[4][256];
-    __shared__ float mean[256];
+// out[b, t, c] = src[b * T + t][c] - mean_t src[b * T + :][c]; frames t >= mask_len zeroed.  One workgroup per utterance.  src rows are ld_src floats
+// apart: the mel path works in place (src = out, ld_src = C -- no __restrict__), the Spectrogram path repacks stft_power_kernel's padded bin rows
+// (ld_src = nbin_pad).  The mean is a sum over four time phases, then their sum, in that order.  Variable-length form (rows): the mean is taken
+// over the row's own Tb frames -- the members of a phase depend on Tb alone -- and the frames behind them are zeroed.
+__global__ __launch_bounds__(256) void cmn_mask_kernel(const float* src, int ld_src, float* out, int T, int C, const float* lens_ratio, int cmn, RowLens rows) {
+    __shared__ float part[4][64];
+    __shared__ float mean[64];
     const int b = blockIdx.x;
+    const float* p = src + (int64_t)b * T * ld_src;
     float* o = out + (int64_t)b * T * C;
     const int tid = threadIdx.x;
     int64_t Lb;
@@ -584,49 +593,14 @@ __global__ __launch_bounds__(256) void cmn_mask_kernel(float* out, int T, int C,
         const int ph = tid >> 6;
         float s = 0.0f;
         if (c < C)
-            for (int t = ph; t < Tb; t += 4) s += o[(int64_t)t * C + c];
+            for (int t = ph; t < Tb; t += 4) s += p[(int64_t)t * ld_src + c];
         part[ph][tid & 63] = s;
         __syncthreads();
         if (tid < 64) mean[tid] = cmn && Tb > 0 ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)Tb : 0.0f;
         __syncthreads();
         if (c < C) {
             const float m = mean[tid & 63];
-            for (int t = ph; t < T; t += 4) {
-                const float v = o[(int64_t)t * C + c] - m;
-                o[(int64_t)t * C + c] = t < mask_len ? v : 0.0f;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// Spectrogram rows: P [b * T + t][ldp] (stft_power_kernel's padded bin rows) -> out [b][t][C] minus the time mean over ALL frames, frames
-// t >= round_half_even(ratio * T) zeroed.  One workgroup per utterance; sums in the fixed order of cmn_mask_kernel.
-// Variable-length form (rows): as cmn_mask_kernel.
-__global__ __launch_bounds__(256) void spec_cmn_mask_kernel(const float* P, int ldp, float* out, int T, int C, const float* lens_ratio, int cmn, RowLens rows) {
-    __shared__ float part[4][64];
-    __shared__ float mean[64];
-    const int b = blockIdx.x;
-    const float* p = P + (int64_t)b * T * ldp;
-    float* o = out + (int64_t)b * T * C;
-    const int tid = threadIdx.x;
-    int64_t Lb;
-    const int Tb = row_frames(rows, b, 0, T, &Lb);
-    int mask_len = Tb;
-    if (lens_ratio != nullptr) mask_len = (int)rintf(lens_ratio[b] * (float)T);
-    for (int c0 = 0; c0 < C; c0 += 64) {
-        const int c = c0 + (tid & 63);
-        const int ph = tid >> 6;
-        float s = 0.0f;
-        if (c < C)
-            for (int t = ph; t < Tb; t += 4) s += p[(int64_t)t * ldp + c];
-        part[ph][tid & 63] = s;
-        __syncthreads();
-        if (tid < 64) mean[tid] = cmn && Tb > 0 ? (part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid]) / (float)Tb : 0.0f;
-        __syncthreads();
-        if (c < C) {
-            const float m = mean[tid & 63];
-            for (int t = ph; t < T; t += 4) o[(int64_t)t * C + c] = t < mask_len ? p[(int64_t)t * ldp + c] - m : 0.0f;
+            for (int t = ph; t < T; t += 4) o[(int64_t)t * C + c] = t < mask_len ? p[(int64_t)t * ld_src + c] - m : 0.0f;
         }
         __syncthreads();
     }
@@ -667,6 +641,134 @@ int upload_vec(const std::vector<T>& v, T** dptr) {
     return MV_OK;
 }
 
+constexpr double PI = 3.14159265358979323846;
+
+// a create call's handle until it is handed to the caller: every early return destroys it
+using MelSpecPtr = std::unique_ptr<MvMelSpec, decltype(&mv_melspec_destroy)>;
+
+// what both create calls refuse, under the caller's name (mv_spectrogram_create fills n_mels, f_min, f_max, mel_scale and norm with defaults)
+int check_cfg(const MvMelSpecCfg* cfg, bool spectrogram, const std::string& who) {
+    MV_REQUIRE(cfg->n_fft >= 4 && cfg->n_fft <= 8192, who + ": n_fft out of range");
+    MV_REQUIRE(cfg->win_length >= 1 && cfg->win_length <= cfg->n_fft, who + ": win_length must be in [1, n_fft]");
+    MV_REQUIRE(cfg->hop_length >= 1, who + ": hop_length must be positive");
+    MV_REQUIRE(cfg->n_mels >= 1 && cfg->n_mels <= 256, who + ": n_mels must be in [1, 256]");
+    MV_REQUIRE(cfg->f_min <= cfg->f_max, who + ": Require f_min <= f_max (torchaudio's MelScale raises the same)");
+    MV_REQUIRE(cfg->power > 0.0f && cfg->power < 64.0f, who + ": power must be a positive exponent (power=None, the complex spectrogram, " +
+                                                            (spectrogram ? "is not implemented)" : "has no mel scale)"));
+    MV_REQUIRE(cfg->mel_scale == MV_MEL_HTK || cfg->mel_scale == MV_MEL_SLANEY, who + ": unknown mel_scale");
+    MV_REQUIRE(cfg->norm == MV_MEL_NORM_NONE || cfg->norm == MV_MEL_NORM_SLANEY, who + ": unknown norm");
+    MV_REQUIRE(cfg->normalized >= MV_STFT_NORM_NONE && cfg->normalized <= MV_STFT_NORM_FRAME_LENGTH, who + ": unknown normalized mode");
+    MV_REQUIRE(cfg->pad >= 0 && cfg->pad < (1 << 24), who + ": pad must be a non-negative sample count");
+    MV_REQUIRE(cfg->pad_mode >= MV_STFT_PAD_REFLECT && cfg->pad_mode <= MV_STFT_PAD_CIRCULAR, who + ": unknown pad_mode");
+    return MV_OK;
+}
+
+// the window (periodic Hann of win_length unless the caller passed window_fn's values), centred in n_fft (torch.stft pads it on both sides)
+int stft_window(const MvMelSpecCfg* cfg, std::vector<float>* window) {
+    window->assign(cfg->n_fft, 0.0f);
+    float* w = window->data() + (cfg->n_fft - cfg->win_length) / 2;
+    for (int i = 0; i < cfg->win_length; ++i) w[i] = cfg->window != nullptr ? cfg->window[i] : (float)(0.5 - 0.5 * cos(2.0 * PI * i / cfg->win_length));
+    // normalized = "window": spec / sqrt(sum window^2); "frame_length": torch.stft(normalized=True) = spec / sqrt(n_fft).  Both scale the complex
+    // spectrum, i.e. the window (torchaudio.functional.spectrogram)
+    if (cfg->normalized != MV_STFT_NORM_NONE) {
+        float ss = 0.0f;   // fp32 like window.pow(2.).sum().sqrt()
+        for (int i = 0; i < cfg->win_length; ++i) ss += w[i] * w[i];
+        const float div = cfg->normalized == MV_STFT_NORM_WINDOW ? sqrtf(ss) : sqrtf((float)cfg->n_fft);
+        MV_REQUIRE(div > 0.0f, "mv_melspec_create: normalized with an all-zero window");
+        for (int i = 0; i < cfg->win_length; ++i) w[i] /= div;
+    }
+    return MV_OK;
+}
+
+// stft_power_kernel's tables [nbin_pad][kpad]: cos and -sin of 2 pi k n / n_fft over the folded half n <= n_fft / 2, zero in the padding
+void dense_dft_tables(const MvMelSpec* h, std::vector<float>* dcos, std::vector<float>* dsin) {
+    const int n_fft = h->cfg.n_fft;
+    dcos->assign((size_t)h->nbin_pad * h->kpad, 0.0f);
+    dsin->assign((size_t)h->nbin_pad * h->kpad, 0.0f);
+    for (int k = 0; k < h->nbin; ++k)
+        for (int n = 0; n <= n_fft / 2; ++n) {
+            const int64_t m = ((int64_t)k * n) % n_fft;  // exact argument reduction
+            const double ang = 2.0 * PI * (double)m / n_fft;
+            (*dcos)[(size_t)k * h->kpad + n] = (float)cos(ang);
+            (*dsin)[(size_t)k * h->kpad + n] = (float)(-sin(ang));
+        }
+}
+
+// mel filterbank [n_mels][nbin_pad], triangles in Hz (torchaudio.functional.melscale_fbanks): HTK or Slaney mel points, optional Slaney area
+// normalisation
+std::vector<float> mel_filterbank(const MvMelSpec* h) {
+    const MvMelSpecCfg* cfg = &h->cfg;
+    std::vector<float> fbT((size_t)cfg->n_mels * h->nbin_pad, 0.0f);
+    const int n_mels = cfg->n_mels;
+    const bool slaney = cfg->mel_scale == MV_MEL_SLANEY;
+    const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
+    auto hz_to_mel = [&](double f) {
+        if (!slaney) return 2595.0 * log10(1.0 + f / 700.0);
+        return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
+    };
+    const double m_min = hz_to_mel(cfg->f_min), m_max = hz_to_mel(cfg->f_max);
+    std::vector<float> f_pts(n_mels + 2);
+    for (int i = 0; i < n_mels + 2; ++i) {
+        // torch.linspace in fp32, then the mel -> Hz map in fp32
+        const float m = (float)(m_min + (m_max - m_min) * i / (n_mels + 1));
+        if (!slaney) f_pts[i] = 700.0f * (powf(10.0f, m / 2595.0f) - 1.0f);
+        else f_pts[i] = m >= (float)min_log_mel ? (float)min_log_hz * expf((float)logstep * (m - (float)min_log_mel)) : (float)f_sp * m;
+    }
+    for (int k = 0; k < h->nbin; ++k) {
+        const float f = (float)((double)(cfg->sample_rate / 2) * k / (h->nbin - 1));
+        for (int j = 0; j < n_mels; ++j) {
+            const float down = (f - f_pts[j]) / (f_pts[j + 1] - f_pts[j]);
+            const float up = (f_pts[j + 2] - f) / (f_pts[j + 2] - f_pts[j + 1]);
+            const float w = fminf(down, up);
+            const float enorm = cfg->norm == MV_MEL_NORM_SLANEY ? 2.0f / (f_pts[j + 2] - f_pts[j]) : 1.0f;
+            fbT[(size_t)j * h->nbin_pad + k] = w > 0.0f ? w * enorm : 0.0f;
+        }
+    }
+    return fbT;
+}
+
+// the filterbank as build_mel_plan reads it: [n_mels][nbin], without the row padding
+std::vector<std::vector<float>> mel_banks(const MvMelSpec* h, const std::vector<float>& fbT) {
+    std::vector<std::vector<float>> banks(h->cfg.n_mels, std::vector<float>(h->nbin, 0.0f));
+    for (int j = 0; j < h->cfg.n_mels; ++j)
+        for (int k = 0; k < h->nbin; ++k) banks[j][k] = fbT[(size_t)j * h->nbin_pad + k];
+    return banks;
+}
+
+// [rows][16][2]: cos, sin of 2 pi r c / period -- the twiddles between the two stages of the FFT kernels (tw400: 13 rows, period 400;
+// tw512: 32 rows, period 512)
+std::vector<float> stage_twiddles(int rows, double period) {
+    std::vector<float> tw((size_t)rows * 16 * 2);
+    for (int r = 0; r < rows; ++r)
+        for (int c = 0; c < 16; ++c) {
+            tw[2 * (r * 16 + c)] = (float)cos(2.0 * PI * (c * r) / period);
+            tw[2 * (r * 16 + c) + 1] = (float)sin(2.0 * PI * (c * r) / period);
+        }
+    return tw;
+}
+
+// melspec_tile_kernel (n_fft = 400): the FFT's twiddles, for the mel instantiation the weights in MFMA order, and the kernel's dynamic LDS
+int setup_tile_kernel(MvMelSpec* h, void (*kernel)(mv::MelTileArgs), const std::vector<float>* melb, const std::string& who) {
+    int rc;
+    if ((rc = upload_vec(stage_twiddles(13, 400.0), &h->d_tw400)) || (melb != nullptr && (rc = upload_vec(*melb, &h->d_melb)))) return rc;
+    h->tile_kernel = true;
+    if (MV_SET_MAX_SMEM(kernel, 160 * 1024) != hipSuccess) return mv::fail(MV_ERR_HIP, who + ": cannot reserve dynamic LDS for melspec_tile_kernel");
+    return MV_OK;
+}
+
+// melspec_pow2_kernel (melfft.hip): the twiddles of its 512-point stage and of the 1024-point split, the weights in MFMA order
+int setup_pow2_kernel(MvMelSpec* h, const std::vector<float>& melb) {
+    std::vector<float> w1(512 * 2);
+    for (int k = 0; k < 512; ++k) {
+        w1[2 * k] = (float)cos(2.0 * PI * k / 1024.0);
+        w1[2 * k + 1] = (float)sin(2.0 * PI * k / 1024.0);
+    }
+    int rc;
+    if ((rc = upload_vec(stage_twiddles(32, 512.0), &h->d_tw512)) || (rc = upload_vec(w1, &h->d_w1024)) || (rc = upload_vec(melb, &h->d_melb))) return rc;
+    h->pow2_kernel = true;
+    return MV_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -695,19 +797,11 @@ int mv_melspec_create(const MvMelSpecCfg* cfg, MvMelSpec** out) { return mv::mel
 }  // extern "C"
 
 int mv::melspec_create_mode(const MvMelSpecCfg* cfg, bool spectrogram, MvMelSpec** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_melspec_create: null argument");
-    MV_REQUIRE(cfg->n_fft >= 4 && cfg->n_fft <= 8192, "mv_melspec_create: n_fft out of range");
-    MV_REQUIRE(cfg->win_length >= 1 && cfg->win_length <= cfg->n_fft, "mv_melspec_create: win_length must be in [1, n_fft]");
-    MV_REQUIRE(cfg->hop_length >= 1, "mv_melspec_create: hop_length must be positive");
-    MV_REQUIRE(cfg->n_mels >= 1 && cfg->n_mels <= 256, "mv_melspec_create: n_mels must be in [1, 256]");
-    MV_REQUIRE(cfg->f_min <= cfg->f_max, "mv_melspec_create: Require f_min <= f_max (torchaudio's MelScale raises the same)");
-    MV_REQUIRE(cfg->power > 0.0f && cfg->power < 64.0f, "mv_melspec_create: power must be a positive exponent (power=None, the complex spectrogram, has no mel scale)");
-    MV_REQUIRE(cfg->mel_scale == MV_MEL_HTK || cfg->mel_scale == MV_MEL_SLANEY, "mv_melspec_create: unknown mel_scale");
-    MV_REQUIRE(cfg->norm == MV_MEL_NORM_NONE || cfg->norm == MV_MEL_NORM_SLANEY, "mv_melspec_create: unknown norm");
-    MV_REQUIRE(cfg->normalized >= MV_STFT_NORM_NONE && cfg->normalized <= MV_STFT_NORM_FRAME_LENGTH, "mv_melspec_create: unknown normalized mode");
-    MV_REQUIRE(cfg->pad >= 0 && cfg->pad < (1 << 24), "mv_melspec_create: pad must be a non-negative sample count");
-    MV_REQUIRE(cfg->pad_mode >= MV_STFT_PAD_REFLECT && cfg->pad_mode <= MV_STFT_PAD_CIRCULAR, "mv_melspec_create: unknown pad_mode");
-    MvMelSpec* h = new MvMelSpec();
+    const std::string who = spectrogram ? "mv_spectrogram_create" : "mv_melspec_create";
+    MV_REQUIRE(cfg != nullptr && out != nullptr, who + ": null argument");
+    int rc = check_cfg(cfg, spectrogram, who);
+    if (rc != MV_OK) return rc;
+    MelSpecPtr h(new MvMelSpec(), mv_melspec_destroy);
     h->cfg = *cfg;
     h->spectrogram = spectrogram;
     h->cfg.window = nullptr;   // (the caller's host array is read below and not kept)
@@ -717,137 +811,30 @@ int mv::melspec_create_mode(const MvMelSpecCfg* cfg, bool spectrogram, MvMelSpec
     h->kpad = (int)mv::round_up(n_fft / 2 + 1, 16);  // folded transform length, padded to the MFMA K block
     h->pad = cfg->center ? n_fft / 2 : 0;
     h->pre_pad = cfg->pad > 0 || (cfg->center && cfg->pad_mode != MV_STFT_PAD_REFLECT);
-    const double pi = 3.14159265358979323846;
-    // the window (periodic Hann of win_length unless the caller passed window_fn's values), centred in n_fft (torch.stft pads it on both sides)
-    std::vector<float> window(n_fft, 0.0f);
-    const int left = (n_fft - cfg->win_length) / 2;
-    for (int i = 0; i < cfg->win_length; ++i)
-        window[left + i] = cfg->window != nullptr ? cfg->window[i] : (float)(0.5 - 0.5 * cos(2.0 * pi * i / cfg->win_length));
-    // normalized = "window": spec / sqrt(sum window^2); "frame_length": torch.stft(normalized=True) = spec / sqrt(n_fft).  Both scale the complex
-    // spectrum, i.e. the window (torchaudio.functional.spectrogram)
-    if (cfg->normalized != MV_STFT_NORM_NONE) {
-        float ss = 0.0f;   // fp32 like window.pow(2.).sum().sqrt()
-        for (int i = 0; i < cfg->win_length; ++i) ss += window[left + i] * window[left + i];
-        const float div = cfg->normalized == MV_STFT_NORM_WINDOW ? sqrtf(ss) : sqrtf((float)n_fft);
-        MV_REQUIRE(div > 0.0f, "mv_melspec_create: normalized with an all-zero window");
-        for (int i = 0; i < cfg->win_length; ++i) window[left + i] /= div;
-    }
-    std::vector<float> dcos((size_t)h->nbin_pad * h->kpad, 0.0f), dsin((size_t)h->nbin_pad * h->kpad, 0.0f);
-    for (int k = 0; k < h->nbin; ++k)
-        for (int n = 0; n <= n_fft / 2; ++n) {
-            const int64_t m = ((int64_t)k * n) % n_fft;  // exact argument reduction
-            const double ang = 2.0 * pi * (double)m / n_fft;
-            dcos[(size_t)k * h->kpad + n] = (float)cos(ang);
-            dsin[(size_t)k * h->kpad + n] = (float)(-sin(ang));
-        }
-    // mel filterbank, triangles in Hz (torchaudio.functional.melscale_fbanks): HTK or Slaney mel points, optional Slaney area normalisation
-    std::vector<float> fbT((size_t)cfg->n_mels * h->nbin_pad, 0.0f);
-    {
-        const int n_mels = cfg->n_mels;
-        const bool slaney = cfg->mel_scale == MV_MEL_SLANEY;
-        const double f_sp = 200.0 / 3.0, min_log_hz = 1000.0, min_log_mel = min_log_hz / f_sp, logstep = log(6.4) / 27.0;
-        auto hz_to_mel = [&](double f) {
-            if (!slaney) return 2595.0 * log10(1.0 + f / 700.0);
-            return f >= min_log_hz ? min_log_mel + log(f / min_log_hz) / logstep : f / f_sp;
-        };
-        const double m_min = hz_to_mel(cfg->f_min), m_max = hz_to_mel(cfg->f_max);
-        std::vector<float> f_pts(n_mels + 2);
-        for (int i = 0; i < n_mels + 2; ++i) {
-            // torch.linspace in fp32, then the mel -> Hz map in fp32
-            const float m = (float)(m_min + (m_max - m_min) * i / (n_mels + 1));
-            if (!slaney) f_pts[i] = 700.0f * (powf(10.0f, m / 2595.0f) - 1.0f);
-            else f_pts[i] = m >= (float)min_log_mel ? (float)min_log_hz * expf((float)logstep * (m - (float)min_log_mel)) : (float)f_sp * m;
-        }
-        for (int k = 0; k < h->nbin; ++k) {
-            const float f = (float)((double)(cfg->sample_rate / 2) * k / (h->nbin - 1));
-            for (int j = 0; j < n_mels; ++j) {
-                const float down = (f - f_pts[j]) / (f_pts[j + 1] - f_pts[j]);
-                const float up = (f_pts[j + 2] - f) / (f_pts[j + 2] - f_pts[j + 1]);
-                const float w = fminf(down, up);
-                const float enorm = cfg->norm == MV_MEL_NORM_SLANEY ? 2.0f / (f_pts[j + 2] - f_pts[j]) : 1.0f;
-                fbT[(size_t)j * h->nbin_pad + k] = w > 0.0f ? w * enorm : 0.0f;
-            }
-        }
-    }
-    int rc;
+    std::vector<float> window, dcos, dsin;
+    if ((rc = stft_window(cfg, &window))) return rc;
+    dense_dft_tables(h.get(), &dcos, &dsin);
+    const std::vector<float> fbT = mel_filterbank(h.get());
     if ((rc = upload_vec(window, &h->d_window)) || (rc = upload_vec(dcos, &h->d_cos)) || (rc = upload_vec(dsin, &h->d_sin)) ||
-        (rc = upload_vec(fbT, &h->d_fbT))) {
-        mv_melspec_destroy(h);
+        (rc = upload_vec(fbT, &h->d_fbT)))
         return rc;
-    }
-    // ---- Spectrogram: melspec_tile_kernel's FFT with the power bins as the features (n_fft = 400), the dense DFT otherwise ----
-    if (spectrogram) {
-        if (n_fft == 400) {
-            std::vector<float> tw(13 * 16 * 2);
-            for (int k1 = 0; k1 < 13; ++k1)
-                for (int n2 = 0; n2 < 16; ++n2) {
-                    tw[2 * (k1 * 16 + n2)] = (float)cos(2.0 * pi * (n2 * k1) / 400.0);
-                    tw[2 * (k1 * 16 + n2) + 1] = (float)sin(2.0 * pi * (n2 * k1) / 400.0);
-                }
-            if ((rc = upload_vec(tw, &h->d_tw400))) {
-                mv_melspec_destroy(h);
-                return rc;
-            }
-            h->tile_kernel = true;
-            if (MV_SET_MAX_SMEM((mv::melspec_tile_kernel<0, 0, true>), 160 * 1024) != hipSuccess) {
-                mv_melspec_destroy(h);
-                return mv::fail(MV_ERR_HIP, "mv_spectrogram_create: cannot reserve dynamic LDS for melspec_tile_kernel");
-            }
-        }
-        *out = h;
-        return MV_OK;
-    }
-    // ---- FFT path (melspec_tile_kernel) when the geometry matches ----
-    if (n_fft == 400 && cfg->power == 2.0f && (cfg->n_mels & 3) == 0 && cfg->n_mels <= 128) {
-        std::vector<std::vector<float>> banks(cfg->n_mels, std::vector<float>(h->nbin, 0.0f));
-        for (int j = 0; j < cfg->n_mels; ++j)
-            for (int k = 0; k < h->nbin; ++k) banks[j][k] = fbT[(size_t)j * h->nbin_pad + k];
+    const bool fft_mel = !spectrogram && cfg->power == 2.0f && (cfg->n_mels & 3) == 0 && cfg->n_mels <= 128;   // what the fused mel stages take
+    if (spectrogram && n_fft == 400) {
+        // ---- Spectrogram: melspec_tile_kernel's FFT with the power bins as the features; any other n_fft runs the dense DFT ----
+        rc = setup_tile_kernel(h.get(), mv::melspec_tile_kernel<0, 0, true>, nullptr, who);
+    } else if (fft_mel && n_fft == 400) {
+        // ---- FFT path (melspec_tile_kernel) when the mel plan matches the instantiation ----
         std::vector<float> melb;
-        const bool ok = mv::build_mel_plan(banks, 208, &h->plan, &melb);  // rows of 201 bins, readable up to 208 (MST_PSTR = 228)
-        if (ok && h->plan.pass_steps[0] == 4 * MST_G0 && h->plan.pass_steps[1] == 4 * MST_G1) {
-            std::vector<float> tw(13 * 16 * 2);
-            for (int k1 = 0; k1 < 13; ++k1)
-                for (int n2 = 0; n2 < 16; ++n2) {
-                    tw[2 * (k1 * 16 + n2)] = (float)cos(2.0 * pi * (n2 * k1) / 400.0);
-                    tw[2 * (k1 * 16 + n2) + 1] = (float)sin(2.0 * pi * (n2 * k1) / 400.0);
-                }
-            if ((rc = upload_vec(tw, &h->d_tw400)) || (rc = upload_vec(melb, &h->d_melb))) {
-                mv_melspec_destroy(h);
-                return rc;
-            }
-            h->tile_kernel = true;
-            if (h->tile_kernel && MV_SET_MAX_SMEM((mv::melspec_tile_kernel<MST_G0, MST_G1>), 160 * 1024) != hipSuccess) {
-                mv_melspec_destroy(h);
-                return mv::fail(MV_ERR_HIP, "mv_melspec_create: cannot reserve dynamic LDS for melspec_tile_kernel");
-            }
-        }
-    }
-    // ---- FFT path for power-of-two transforms (melspec_pow2_kernel: the README's n_fft 1024 / hop 320 / 64 mels, and 128 ... 512) ----
-    if (!h->tile_kernel && (n_fft == 128 || n_fft == 256 || n_fft == 512 || n_fft == 1024) && cfg->power == 2.0f && (cfg->n_mels & 3) == 0 &&
-        cfg->n_mels <= 128) {
-        std::vector<std::vector<float>> banks(cfg->n_mels, std::vector<float>(h->nbin, 0.0f));
-        for (int j = 0; j < cfg->n_mels; ++j)
-            for (int k = 0; k < h->nbin; ++k) banks[j][k] = fbT[(size_t)j * h->nbin_pad + k];
+        const bool ok = mv::build_mel_plan(mel_banks(h.get(), fbT), 208, &h->plan, &melb);  // rows of 201 bins, readable up to 208 (MST_PSTR = 228)
+        if (ok && h->plan.pass_steps[0] == 4 * MST_G0 && h->plan.pass_steps[1] == 4 * MST_G1)
+            rc = setup_tile_kernel(h.get(), mv::melspec_tile_kernel<MST_G0, MST_G1>, &melb, who);
+    } else if (fft_mel && (n_fft == 128 || n_fft == 256 || n_fft == 512 || n_fft == 1024)) {
+        // ---- FFT path for power-of-two transforms (melspec_pow2_kernel: the README's n_fft 1024 / hop 320 / 64 mels, and 128 ... 512) ----
         std::vector<float> melb;
-        if (mv::build_mel_plan(banks, mv::MF_PSTR, &h->plan, &melb)) {
-            std::vector<float> tw(32 * 16 * 2), w1(512 * 2);
-            for (int k1 = 0; k1 < 32; ++k1)
-                for (int l = 0; l < 16; ++l) {
-                    tw[2 * (k1 * 16 + l)] = (float)cos(2.0 * pi * (l * k1) / 512.0);
-                    tw[2 * (k1 * 16 + l) + 1] = (float)sin(2.0 * pi * (l * k1) / 512.0);
-                }
-            for (int k = 0; k < 512; ++k) {
-                w1[2 * k] = (float)cos(2.0 * pi * k / 1024.0);
-                w1[2 * k + 1] = (float)sin(2.0 * pi * k / 1024.0);
-            }
-            if ((rc = upload_vec(tw, &h->d_tw512)) || (rc = upload_vec(w1, &h->d_w1024)) || (rc = upload_vec(melb, &h->d_melb))) {
-                mv_melspec_destroy(h);
-                return rc;
-            }
-            h->pow2_kernel = true;
-        }
+        if (mv::build_mel_plan(mel_banks(h.get(), fbT), mv::MF_PSTR, &h->plan, &melb)) rc = setup_pow2_kernel(h.get(), melb);
     }
-    *out = h;
+    if (rc != MV_OK) return rc;
+    *out = h.release();
     return MV_OK;
 }
 
@@ -875,12 +862,7 @@ int mv_melspec_destroy(MvMelSpec* h) {
 
 int mv_melspec_num_frames(const MvMelSpec* h, int64_t num_samples, int64_t* num_frames) {
     MV_REQUIRE(h != nullptr && num_frames != nullptr, "mv_melspec_num_frames: null argument");
-    num_samples += 2 * (int64_t)h->cfg.pad;
-    if (h->cfg.center) {
-        *num_frames = 1 + num_samples / h->cfg.hop_length;
-    } else {
-        *num_frames = num_samples < h->cfg.n_fft ? 0 : 1 + (num_samples - h->cfg.n_fft) / h->cfg.hop_length;
-    }
+    *num_frames = mv::stft_num_frames(num_samples, h->cfg.pad, h->cfg.center, h->cfg.n_fft, h->cfg.hop_length, 0);
     return MV_OK;
 }
 
@@ -920,105 +902,85 @@ mv::RowLens mv::melspec_row_lens(const MvMelSpec* h, const int64_t* num_samples,
     v.center = h->cfg.center;
     v.n_fft = h->cfg.n_fft;
     v.hop = h->cfg.hop_length;
-    // what the batch form refuses for the whole call: reflect needs more than n_fft / 2 samples, circular at least n_fft / 2
-    v.min_len = !h->cfg.center ? 0 : (h->cfg.pad_mode == MV_STFT_PAD_REFLECT ? h->pad + 1 : (h->cfg.pad_mode == MV_STFT_PAD_CIRCULAR ? h->pad : 0));
+    // reflect needs more than n_fft / 2 samples, circular at least n_fft / 2 (the batch form refuses less for the whole call); replicate and
+    // constant take whatever is not empty
+    v.min_len = !h->cfg.center ? 0 : (h->cfg.pad_mode == MV_STFT_PAD_REFLECT ? h->pad + 1 : (h->cfg.pad_mode == MV_STFT_PAD_CIRCULAR ? h->pad : 1));
     return v;
 }
 
-// the forward of both forms: lens_ratio (batch form, or neither) or num_samples (variable-length form), never both
-int mv::melspec_forward_rows(const MvMelSpec* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
-                             const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
-    MV_REQUIRE(h != nullptr, "mv_melspec_forward: null handle");
-    MV_REQUIRE(B >= 0 && L >= 0 && wav_stride >= L, "mv_melspec_forward: bad batch geometry");
-    MV_REQUIRE(lens_ratio == nullptr || num_samples == nullptr, "mv_melspec_forward: lens_ratio and num_samples are mutually exclusive");
-    int64_t T = 0;
-    mv_melspec_num_frames(h, L, &T);
-    if (B == 0 || T == 0) return MV_OK;
-    MV_REQUIRE(wav != nullptr && out != nullptr && workspace != nullptr, "mv_melspec_forward: null buffer");
-    const mv::RowLens rows = mv::melspec_row_lens(h, num_samples, L);
-    int centre_pad = h->pad;   // what the transform kernels still have to reflect themselves
-    if (h->pre_pad) {
-        const int64_t Lp = L + 2 * (int64_t)h->cfg.pad;
-        if (h->cfg.center && h->cfg.pad_mode == MV_STFT_PAD_REFLECT) MV_REQUIRE(Lp > h->pad, "mv_melspec_forward: reflect padding needs more than n_fft/2 samples (torch.stft raises too)");
-        if (h->cfg.center && h->cfg.pad_mode == MV_STFT_PAD_CIRCULAR) MV_REQUIRE(Lp >= h->pad, "mv_melspec_forward: circular padding needs at least n_fft/2 samples (torch.stft raises too)");
-        const size_t ext = melspec_extended_bytes(h, B, L);
-        MV_REQUIRE(workspace_bytes >= ext && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "mv_melspec_forward: workspace too small for the extended signal (mv_melspec_workspace_bytes)");
-        MV_REQUIRE(B <= 65535, "mv_melspec_forward: pad / pad_mode take at most 65535 rows per call");
-        const int64_t L2 = melspec_extended_len(h, L), stride2 = melspec_extended_stride(h, L);
-        float* dst = static_cast<float*>(workspace);
-        MV_LAUNCH(mv::melspec_extend_kernel, ((unsigned)mv::ceil_div(L2, (int64_t)1024), (unsigned)B, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), wav, wav_stride, L,
-                  dst, stride2, L2, h->cfg.pad, h->pad, h->cfg.pad_mode, num_samples);
-        int rc = mv::check_launch("melspec_extend_kernel");
-        if (rc != MV_OK) return rc;
-        wav = dst;
-        wav_stride = stride2;
-        L = L2;
-        centre_pad = 0;
-        workspace = static_cast<char*>(workspace) + ext;
-        workspace_bytes -= ext;
-    } else if (h->cfg.center) {
-        MV_REQUIRE(L > h->pad, "mv_melspec_forward: reflect padding needs more than n_fft/2 samples (torch.stft raises too)");
-    }
-    if (h->spectrogram && h->tile_kernel && (int64_t)T * h->nbin < ((int64_t)1 << 31)) {
-        mv::MelTileArgs t = {};
-        t.wav = wav; t.wav_stride = wav_stride; t.L = L; t.lens_ratio = lens_ratio; t.out = out;
-        t.window = h->d_window; t.tw400 = h->d_tw400; t.melb = nullptr;
-        t.B = B; t.T = (int)T; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->nbin; t.cmn = h->cfg.subtract_time_mean;
+namespace {
+
+// what a forward transforms once the optional extension pass has run: the signal, and the centre padding the transform kernels still have to
+// reflect themselves
+struct Signal {
+    const float* wav;
+    int64_t stride, L;
+    int centre_pad;
+};
+
+// The feature rows a fused kernel holds in LDS until the time mean is known: as many rows of row_floats floats as fit next to its fixed_bytes
+// in 160 KB, in quads of frames, no more than T frames need (tile_rows); the rest go through global memory.  smem = the launch's dynamic LDS.
+struct ResidentRows {
+    int tile_rows;
+    size_t smem;
+};
+
+ResidentRows resident_rows(size_t fixed_bytes, int row_floats, int64_t T) {
+    const size_t row_bytes = (size_t)row_floats * sizeof(float);
+    const int64_t fit = (int64_t)((160 * 1024 - fixed_bytes) / row_bytes) & ~(int64_t)3, need = (T + 3) & ~(int64_t)3;
+    const int tile_rows = (int)(fit < need ? fit : need);
+    return {tile_rows, fixed_bytes + (size_t)tile_rows * row_bytes};
+}
+
+// melspec_tile_kernel, both instantiations: the spectrogram one holds rows of 201 bins (136 of them), takes any power and has no mel stage
+int tile_forward(const MvMelSpec* h, const Signal& s, int32_t B, int64_t T, int dim, const float* lens_ratio, const mv::RowLens& rows, float* out, hipStream_t st) {
+    mv::MelTileArgs t = {};
+    t.wav = s.wav; t.wav_stride = s.stride; t.L = s.L; t.lens_ratio = lens_ratio; t.out = out;
+    t.window = h->d_window; t.tw400 = h->d_tw400;
+    t.B = B; t.T = (int)T; t.hop = h->cfg.hop_length; t.pad = s.centre_pad; t.n_mels = dim; t.cmn = h->cfg.subtract_time_mean;
+    t.rows = rows;
+    const ResidentRows lds = resident_rows((size_t)mv::MST_WAVES * mv::MST_SLOT_FLOATS * sizeof(float), dim, T);
+    t.tile_rows = lds.tile_rows;
+    if (h->spectrogram) {
         t.power = h->cfg.power;
-        t.rows = rows;
-        // as many 201-float rows as fit next to the wave slots stay in LDS (136); the rest go through global memory
-        const size_t slots = (size_t)mv::MST_WAVES * mv::MST_SLOT_FLOATS * sizeof(float);
-        int64_t rows = (int64_t)((160 * 1024 - slots) / ((size_t)h->nbin * sizeof(float))) & ~(int64_t)3;
-        const int64_t need = (T + 3) & ~(int64_t)3;
-        t.tile_rows = (int)(rows < need ? rows : need);
-        const size_t smem = slots + (size_t)t.tile_rows * h->nbin * sizeof(float);
-        MV_LAUNCH((mv::melspec_tile_kernel<0, 0, true>), ((unsigned)B, 1, 1), (mv::MST_WAVES * 64, 1, 1), smem, static_cast<hipStream_t>(stream), t);
+        MV_LAUNCH((mv::melspec_tile_kernel<0, 0, true>), ((unsigned)B, 1, 1), (mv::MST_WAVES * 64, 1, 1), lds.smem, st, t);
         return mv::check_launch("melspec_tile_kernel<spectrogram>");
     }
-    if (!h->spectrogram && h->tile_kernel && (int64_t)T * h->cfg.n_mels < ((int64_t)1 << 31)) {
-        mv::MelTileArgs t;
-        t.wav = wav; t.wav_stride = wav_stride; t.L = L; t.lens_ratio = lens_ratio; t.out = out;
-        t.window = h->d_window; t.tw400 = h->d_tw400; t.melb = h->d_melb;
-        t.B = B; t.T = (int)T; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->cfg.n_mels; t.cmn = h->cfg.subtract_time_mean;
-        t.plan = h->plan;
-        t.power = 2.0f;
-        t.rows = rows;
-        // feature rows that fit next to the wave slots stay in LDS until the time mean is known; the rest go through global memory
-        const size_t slots = (size_t)mv::MST_WAVES * mv::MST_SLOT_FLOATS * sizeof(float);
-        int64_t rows = (int64_t)((160 * 1024 - slots) / ((size_t)h->cfg.n_mels * sizeof(float))) & ~(int64_t)3;
-        const int64_t need = (T + 3) & ~(int64_t)3;
-        t.tile_rows = (int)(rows < need ? rows : need);
-        const size_t smem = slots + (size_t)t.tile_rows * h->cfg.n_mels * sizeof(float);
-        const int prof = mv::prof_begin(MV_PROF_FBANK, (double)B * (4.0 * (double)L + 4.0 * (double)T * h->cfg.n_mels), static_cast<hipStream_t>(stream));
-        MV_LAUNCH((mv::melspec_tile_kernel<MST_G0, MST_G1>), ((unsigned)B, 1, 1), (mv::MST_WAVES * 64, 1, 1), smem, static_cast<hipStream_t>(stream), t);
-        mv::prof_end(prof, static_cast<hipStream_t>(stream));
-        return mv::check_launch("melspec_tile_kernel");
-    }
-    if (!h->spectrogram && h->pow2_kernel && (int64_t)T * h->cfg.n_mels < ((int64_t)1 << 31)) {
-        mv::MelFftArgs t;
-        t.wav = wav; t.wav_stride = wav_stride; t.L = L; t.lens_ratio = lens_ratio; t.out = out;
-        t.window = h->d_window; t.tw512 = h->d_tw512; t.w1024 = h->d_w1024; t.melb = h->d_melb;
-        t.B = B; t.T = (int)T; t.n_fft = h->cfg.n_fft; t.hop = h->cfg.hop_length; t.pad = centre_pad; t.n_mels = h->cfg.n_mels;
-        t.cmn = h->cfg.subtract_time_mean;
-        t.plan = h->plan;
-        t.rows = rows;
-        const size_t fixed = mv::melfft_fixed_lds_bytes();
-        int64_t rows = (int64_t)((160 * 1024 - fixed) / ((size_t)h->cfg.n_mels * sizeof(float))) & ~(int64_t)3;
-        const int64_t need = (T + 3) & ~(int64_t)3;
-        t.tile_rows = (int)(rows < need ? rows : need);
-        const size_t smem = fixed + (size_t)t.tile_rows * h->cfg.n_mels * sizeof(float);
-        const int prof = mv::prof_begin(MV_PROF_FBANK, (double)B * (4.0 * (double)L + 4.0 * (double)T * h->cfg.n_mels), static_cast<hipStream_t>(stream));
-        const int rc = mv::melfft_launch(t, smem, static_cast<hipStream_t>(stream));
-        mv::prof_end(prof, static_cast<hipStream_t>(stream));
-        return rc;
-    }
+    t.melb = h->d_melb;
+    t.plan = h->plan;
+    t.power = 2.0f;
+    const int prof = mv::prof_begin(MV_PROF_FBANK, (double)B * (4.0 * (double)s.L + 4.0 * (double)T * dim), st);
+    MV_LAUNCH((mv::melspec_tile_kernel<MST_G0, MST_G1>), ((unsigned)B, 1, 1), (mv::MST_WAVES * 64, 1, 1), lds.smem, st, t);
+    mv::prof_end(prof, st);
+    return mv::check_launch("melspec_tile_kernel");
+}
+
+int pow2_forward(const MvMelSpec* h, const Signal& s, int32_t B, int64_t T, const float* lens_ratio, const mv::RowLens& rows, float* out, hipStream_t st) {
+    mv::MelFftArgs t;
+    t.wav = s.wav; t.wav_stride = s.stride; t.L = s.L; t.lens_ratio = lens_ratio; t.out = out;
+    t.window = h->d_window; t.tw512 = h->d_tw512; t.w1024 = h->d_w1024; t.melb = h->d_melb;
+    t.B = B; t.T = (int)T; t.n_fft = h->cfg.n_fft; t.hop = h->cfg.hop_length; t.pad = s.centre_pad; t.n_mels = h->cfg.n_mels;
+    t.cmn = h->cfg.subtract_time_mean;
+    t.plan = h->plan;
+    t.rows = rows;
+    const ResidentRows lds = resident_rows(mv::melfft_fixed_lds_bytes(), h->cfg.n_mels, T);
+    t.tile_rows = lds.tile_rows;
+    const int prof = mv::prof_begin(MV_PROF_FBANK, (double)B * (4.0 * (double)s.L + 4.0 * (double)T * h->cfg.n_mels), st);
+    const int rc = mv::melfft_launch(t, lds.smem, st);
+    mv::prof_end(prof, st);
+    return rc;
+}
+
+// any other geometry: stft_power_kernel into the workspace, then the time mean and mask from the padded bin rows (Spectrogram) or the mel
+// projection and, when there is a mean or a mask to apply, the same kernel in place
+int dense_forward(const MvMelSpec* h, const Signal& s, int32_t B, int64_t T, const float* lens_ratio, const mv::RowLens& rows, float* out,
+                  void* workspace, size_t workspace_bytes, hipStream_t st) {
     MV_REQUIRE(workspace_bytes >= (size_t)B * (size_t)T * h->nbin_pad * sizeof(float), "mv_melspec_forward: workspace too small");
     MV_REQUIRE((int64_t)B * T < ((int64_t)1 << 31), "mv_melspec_forward: too many frames");
-    hipStream_t st = static_cast<hipStream_t>(stream);
     mv::StftArgs a;
-    a.wav = wav;
-    a.wav_stride = wav_stride;
-    a.L = L;
+    a.wav = s.wav;
+    a.wav_stride = s.stride;
+    a.L = s.L;
     a.window = h->d_window;
     a.dcos = h->d_cos;
     a.dsin = h->d_sin;
@@ -1028,7 +990,7 @@ int mv::melspec_forward_rows(const MvMelSpec* h, const float* wav, int32_t B, in
     a.n_fft = h->cfg.n_fft;
     a.kpad = h->kpad;
     a.hop = h->cfg.hop_length;
-    a.pad = centre_pad;
+    a.pad = s.centre_pad;
     a.nbin = h->nbin;
     a.nbin_pad = h->nbin_pad;
     a.power = h->cfg.power;
@@ -1040,18 +1002,57 @@ int mv::melspec_forward_rows(const MvMelSpec* h, const float* wav, int32_t B, in
     MV_LAUNCH(mv::stft_power_kernel<7>, (gx, gy, 1), (256, 1, 1), 0, st, a);
     int rc = mv::check_launch("stft_power_kernel");
     if (rc != MV_OK) return rc;
-    if (h->spectrogram) {
-        MV_LAUNCH(mv::spec_cmn_mask_kernel, ((unsigned)B, 1, 1), (256, 1, 1), 0, st, a.P, h->nbin_pad, out, (int)T, h->nbin, lens_ratio,
-                  h->cfg.subtract_time_mean, rows);
-        return mv::check_launch("spec_cmn_mask_kernel");
+    const float* src = a.P;
+    int ld_src = h->nbin_pad, dim = h->nbin;
+    if (!h->spectrogram) {
+        rc = mv::linear_f32_launch(a.P, h->nbin_pad, h->d_fbT, h->nbin_pad, nullptr, MV_ACT_NONE, out, h->cfg.n_mels, (int)nframes,
+                                   h->nbin, h->cfg.n_mels, 0, st);
+        if (rc != MV_OK || !(h->cfg.subtract_time_mean || lens_ratio != nullptr || rows.num_samples != nullptr)) return rc;
+        src = out;
+        ld_src = dim = h->cfg.n_mels;
     }
-    rc = mv::linear_f32_launch(a.P, h->nbin_pad, h->d_fbT, h->nbin_pad, nullptr, MV_ACT_NONE, out, h->cfg.n_mels, (int)nframes,
-                               h->nbin, h->cfg.n_mels, 0, st);
-    if (rc != MV_OK) return rc;
-    if (h->cfg.subtract_time_mean || lens_ratio != nullptr || num_samples != nullptr) {
-        MV_LAUNCH(mv::cmn_mask_kernel, ((unsigned)B, 1, 1), (256, 1, 1), 0, st, out, (int)T, h->cfg.n_mels, lens_ratio,
-                  h->cfg.subtract_time_mean, rows);
-        rc = mv::check_launch("cmn_mask_kernel");
+    MV_LAUNCH(mv::cmn_mask_kernel, ((unsigned)B, 1, 1), (256, 1, 1), 0, st, src, ld_src, out, (int)T, dim, lens_ratio, h->cfg.subtract_time_mean, rows);
+    return mv::check_launch("cmn_mask_kernel");
+}
+
+}  // namespace
+
+// the forward of both forms: lens_ratio (batch form, or neither) or num_samples (variable-length form), never both.
+// Checks, the optional extension pass, then one of {melspec_tile_kernel, melspec_pow2_kernel, dense DFT}
+int mv::melspec_forward_rows(const MvMelSpec* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
+                             const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    MV_REQUIRE(h != nullptr, "mv_melspec_forward: null handle");
+    MV_REQUIRE(B >= 0 && L >= 0 && wav_stride >= L, "mv_melspec_forward: bad batch geometry");
+    MV_REQUIRE(lens_ratio == nullptr || num_samples == nullptr, "mv_melspec_forward: lens_ratio and num_samples are mutually exclusive");
+    int64_t T = 0;
+    mv_melspec_num_frames(h, L, &T);
+    if (B == 0 || T == 0) return MV_OK;
+    MV_REQUIRE(wav != nullptr && out != nullptr && workspace != nullptr, "mv_melspec_forward: null buffer");
+    const mv::RowLens rows = mv::melspec_row_lens(h, num_samples, L);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // what leaves a row of the variable-length form without frames is refused for the whole call here (replicate and constant padding take any length)
+    const char* too_short = !h->cfg.center ? nullptr
+        : h->cfg.pad_mode == MV_STFT_PAD_REFLECT ? "mv_melspec_forward: reflect padding needs more than n_fft/2 samples (torch.stft raises too)"
+        : h->cfg.pad_mode == MV_STFT_PAD_CIRCULAR ? "mv_melspec_forward: circular padding needs at least n_fft/2 samples (torch.stft raises too)" : nullptr;
+    if (too_short != nullptr) MV_REQUIRE(L + 2 * (int64_t)h->cfg.pad >= rows.min_len, too_short);
+    Signal s = {wav, wav_stride, L, h->pad};
+    if (h->pre_pad) {
+        const size_t ext = melspec_extended_bytes(h, B, L);
+        MV_REQUIRE(workspace_bytes >= ext && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "mv_melspec_forward: workspace too small for the extended signal (mv_melspec_workspace_bytes)");
+        MV_REQUIRE(B <= 65535, "mv_melspec_forward: pad / pad_mode take at most 65535 rows per call");
+        const int64_t L2 = melspec_extended_len(h, L), stride2 = melspec_extended_stride(h, L);
+        float* dst = static_cast<float*>(workspace);
+        MV_LAUNCH(mv::melspec_extend_kernel, ((unsigned)mv::ceil_div(L2, (int64_t)1024), (unsigned)B, 1), (256, 1, 1), 0, st, wav, wav_stride, L,
+                  dst, stride2, L2, h->cfg.pad, h->pad, h->cfg.pad_mode, num_samples);
+        int rc = mv::check_launch("melspec_extend_kernel");
+        if (rc != MV_OK) return rc;
+        s = {dst, stride2, L2, 0};
+        workspace = static_cast<char*>(workspace) + ext;
+        workspace_bytes -= ext;
     }
-    return rc;
+    const int dim = h->spectrogram ? h->nbin : h->cfg.n_mels;   // feature columns
+    const bool fits = T * dim < ((int64_t)1 << 31);              // the fused kernels index a row's features with 32 bits
+    if (h->tile_kernel && fits) return tile_forward(h, s, B, T, dim, lens_ratio, rows, out, st);
+    if (h->pow2_kernel && fits) return pow2_forward(h, s, B, T, lens_ratio, rows, out, st);
+    return dense_forward(h, s, B, T, lens_ratio, rows, out, workspace, workspace_bytes, st);
 }

@@ -5,7 +5,8 @@
 namespace mv {
 
 // mv_melspec_create with a mode: spectrogram = true makes a handle whose features are the n_fft / 2 + 1 power bins (no mel stage);
-// every mv_melspec_* call then works on it, writing [B, T, n_fft / 2 + 1]
+// every mv_melspec_* call then works on it, writing [B, T, n_fft / 2 + 1].  The configuration is checked here for both callers; a refusal
+// names mv_spectrogram_create in spectrogram mode, mv_melspec_create otherwise
 int melspec_create_mode(const MvMelSpecCfg* cfg, bool spectrogram, MvMelSpec** out);
 
 // mv_melspec_forward (num_samples == nullptr) and mv_melspec_forward_varlen (lens_ratio == nullptr) in one: the MFCC mel stage runs either

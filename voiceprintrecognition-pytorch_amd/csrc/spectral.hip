@@ -3,7 +3,7 @@
 //
 // Spectrogram: a MvMelSpec handle in spectrogram mode (melspec.hip).  n_fft = 400 runs melspec_tile_kernel<0, 0, true> -- the real FFT of
 // the MelSpectrogram path with the 201 power bins written as the features, time mean and mask in the same launch; any other geometry
-// stft_power_kernel + spec_cmn_mask_kernel.
+// stft_power_kernel + cmn_mask_kernel reading its padded bin rows.
 //
 // MFCC, three launches after the mel stage:
 //   mel stage             the MelSpectrogram kernels with the time mean off and no mask: mel power [B, T, n_mels] in the caller workspace
@@ -13,6 +13,7 @@
 //                         log(mel + 1e-6)), DCT-II on exact fp32 FMAs in a fixed order, the time mean over all frames, the mask,
 //                         one write of [T, n_mfcc]
 // The batch-wide maximum is a global dependency: it is a launch boundary, not a grid barrier, and it never leaves the device.
+#include <memory>
 #include <vector>
 
 #include "frontend_common.h"
@@ -148,9 +149,21 @@ namespace {
 
 size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
-// the mel stage's output and the per-utterance maxima, behind the mel stage's own workspace
-size_t mfcc_mel_bytes(const MvMfcc* h, int32_t B, int64_t T) { return align256((size_t)B * (size_t)T * h->cfg.mel.n_mels * sizeof(float)); }
-size_t mfcc_max_bytes(int32_t B) { return align256((size_t)B * sizeof(float)); }
+// the caller workspace of an MFCC forward: the mel stage's own workspace, behind it the mel stage's output [B, T, n_mels] and the per-utterance
+// maxima [B]; every section starts on a multiple of 256 bytes
+struct MfccWorkspace {
+    size_t mel, rowmax, total;   // offsets of the last two sections (mel = the bytes of the first), bytes in all
+};
+
+MfccWorkspace mfcc_workspace(const MvMfcc* h, int32_t B, int64_t L) {
+    int64_t T = 0;
+    mv_melspec_num_frames(h->mel, L, &T);
+    MfccWorkspace w;
+    w.mel = align256(mv_melspec_workspace_bytes(h->mel, B, L));
+    w.rowmax = w.mel + align256((size_t)B * (size_t)T * h->cfg.mel.n_mels * sizeof(float));
+    w.total = w.rowmax + align256((size_t)B * sizeof(float));
+    return w;
+}
 
 }  // namespace
 
@@ -171,13 +184,6 @@ void mv_spectrogram_default_cfg(MvSpectrogramCfg* cfg) {
 
 int mv_spectrogram_create(const MvSpectrogramCfg* cfg, MvSpectrogram** out) {
     MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_spectrogram_create: null argument");
-    MV_REQUIRE(cfg->n_fft >= 4 && cfg->n_fft <= 8192, "mv_spectrogram_create: n_fft out of range");
-    MV_REQUIRE(cfg->win_length >= 1 && cfg->win_length <= cfg->n_fft, "mv_spectrogram_create: win_length must be in [1, n_fft]");
-    MV_REQUIRE(cfg->hop_length >= 1, "mv_spectrogram_create: hop_length must be positive");
-    MV_REQUIRE(cfg->power > 0.0f && cfg->power < 64.0f, "mv_spectrogram_create: power must be a positive exponent (power=None, the complex spectrogram, is not implemented)");
-    MV_REQUIRE(cfg->normalized >= MV_STFT_NORM_NONE && cfg->normalized <= MV_STFT_NORM_FRAME_LENGTH, "mv_spectrogram_create: unknown normalized mode");
-    MV_REQUIRE(cfg->pad >= 0 && cfg->pad < (1 << 24), "mv_spectrogram_create: pad must be a non-negative sample count");
-    MV_REQUIRE(cfg->pad_mode >= MV_STFT_PAD_REFLECT && cfg->pad_mode <= MV_STFT_PAD_CIRCULAR, "mv_spectrogram_create: unknown pad_mode");
     MvMelSpecCfg m;
     mv_melspec_default_cfg(&m);
     m.n_fft = cfg->n_fft;
@@ -191,13 +197,10 @@ int mv_spectrogram_create(const MvSpectrogramCfg* cfg, MvSpectrogram** out) {
     m.subtract_time_mean = cfg->subtract_time_mean ? 1 : 0;
     m.window = cfg->window;
     m.n_mels = 1;   // (no mel stage in spectrogram mode)
-    MvSpectrogram* h = new MvSpectrogram();
-    const int rc = mv::melspec_create_mode(&m, true, &h->core);
-    if (rc != MV_OK) {
-        delete h;
-        return rc;
-    }
-    *out = h;
+    std::unique_ptr<MvSpectrogram> h(new MvSpectrogram());
+    const int rc = mv::melspec_create_mode(&m, true, &h->core);   // (checks the fields above under this call's name)
+    if (rc != MV_OK) return rc;
+    *out = h.release();
     return MV_OK;
 }
 
@@ -252,16 +255,13 @@ int mv_mfcc_create(const MvMfccCfg* cfg, MvMfcc** out) {
     MV_REQUIRE(cfg->dct_norm == MV_DCT_NORM_NONE || cfg->dct_norm == MV_DCT_NORM_ORTHO, "mv_mfcc_create: norm must be None or 'ortho'");
     MV_REQUIRE(cfg->log_mels == 0 || cfg->log_mels == 1, "mv_mfcc_create: log_mels must be 0 or 1");
     MV_REQUIRE(cfg->top_db >= 0.0f && cfg->top_db < 1e30f, "mv_mfcc_create: top_db must be a non-negative finite value");
-    MvMfcc* h = new MvMfcc();
+    std::unique_ptr<MvMfcc, decltype(&mv_mfcc_destroy)> h(new MvMfcc(), mv_mfcc_destroy);   // (every early return destroys it)
     h->cfg = *cfg;
     h->cfg.mel.window = nullptr;   // (read by the mel stage's create, not kept)
     MvMelSpecCfg m = cfg->mel;
     m.subtract_time_mean = 0;
     int rc = mv::melspec_create_mode(&m, false, &h->mel);
-    if (rc != MV_OK) {
-        delete h;
-        return rc;
-    }
+    if (rc != MV_OK) return rc;
     // torchaudio.functional.create_dct(n_mfcc, n_mels, norm): dct[m][k] = cos(pi / n_mels * (m + 0.5) * k), 'ortho' scales column 0 by
     // 1 / sqrt(2) and everything by sqrt(2 / n_mels), None everything by 2
     const int nm = cfg->mel.n_mels, nc = cfg->n_mfcc;
@@ -276,16 +276,11 @@ int mv_mfcc_create(const MvMfccCfg* cfg, MvMfcc** out) {
         }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->d_dct), dct.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->d_dct, dct.data(), dct.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        mv_mfcc_destroy(h);
-        return mv::fail(MV_ERR_HIP, std::string("mv_mfcc_create: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return mv::fail(MV_ERR_HIP, std::string("mv_mfcc_create: ") + hipGetErrorString(e));
     h->dct_lds = nm * nc <= mv::MFCC_DCT_LDS_MAX;
-    if ((h->dct_lds ? MV_SET_MAX_SMEM(mv::mfcc_dct_kernel<true>, (int)mv::MFCC_LDS) : MV_SET_MAX_SMEM(mv::mfcc_dct_kernel<false>, (int)mv::MFCC_LDS)) != hipSuccess) {
-        mv_mfcc_destroy(h);
+    if ((h->dct_lds ? MV_SET_MAX_SMEM(mv::mfcc_dct_kernel<true>, (int)mv::MFCC_LDS) : MV_SET_MAX_SMEM(mv::mfcc_dct_kernel<false>, (int)mv::MFCC_LDS)) != hipSuccess)
         return mv::fail(MV_ERR_HIP, "mv_mfcc_create: cannot reserve dynamic LDS for mfcc_dct_kernel");
-    }
-    *out = h;
+    *out = h.release();
     return MV_OK;
 }
 
@@ -309,10 +304,7 @@ int mv_mfcc_num_frames(const MvMfcc* h, int64_t num_samples, int64_t* num_frames
 }
 
 size_t mv_mfcc_workspace_bytes(const MvMfcc* h, int32_t B, int64_t L) {
-    if (h == nullptr || B <= 0) return 0;
-    int64_t T = 0;
-    mv_melspec_num_frames(h->mel, L, &T);
-    return align256(mv_melspec_workspace_bytes(h->mel, B, L)) + mfcc_mel_bytes(h, B, T) + mfcc_max_bytes(B);
+    return h == nullptr || B <= 0 ? 0 : mfcc_workspace(h, B, L).total;
 }
 
 static int mfcc_forward_rows(const MvMfcc* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
@@ -340,13 +332,13 @@ static int mfcc_forward_rows(const MvMfcc* h, const float* wav, int32_t B, int64
     if (B == 0 || T == 0) return MV_OK;
     MV_REQUIRE(wav != nullptr && out != nullptr && workspace != nullptr, "mv_mfcc_forward: null buffer");
     MV_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "mv_mfcc_forward: workspace must be 16-byte aligned");
-    MV_REQUIRE(workspace_bytes >= mv_mfcc_workspace_bytes(h, B, L), "mv_mfcc_forward: workspace too small (mv_mfcc_workspace_bytes)");
+    const MfccWorkspace sec = mfcc_workspace(h, B, L);
+    MV_REQUIRE(workspace_bytes >= sec.total, "mv_mfcc_forward: workspace too small (mv_mfcc_workspace_bytes)");
     MV_REQUIRE((int64_t)T * h->cfg.mel.n_mels < ((int64_t)1 << 31) && (int64_t)T * h->cfg.n_mfcc < ((int64_t)1 << 31), "mv_mfcc_forward: too many frames");
-    const size_t mel_ws = align256(mv_melspec_workspace_bytes(h->mel, B, L));
     char* ws = static_cast<char*>(workspace);
-    float* mel = reinterpret_cast<float*>(ws + mel_ws);
-    float* rowmax = reinterpret_cast<float*>(ws + mel_ws + mfcc_mel_bytes(h, B, T));
-    int rc = mv::melspec_forward_rows(h->mel, wav, B, L, wav_stride, nullptr, num_samples, mel, ws, mel_ws, stream);
+    float* mel = reinterpret_cast<float*>(ws + sec.mel);
+    float* rowmax = reinterpret_cast<float*>(ws + sec.rowmax);
+    int rc = mv::melspec_forward_rows(h->mel, wav, B, L, wav_stride, nullptr, num_samples, mel, ws, sec.mel, stream);
     if (rc != MV_OK) return rc;
     const mv::RowLens row_lens = mv::melspec_row_lens(h->mel, num_samples, L);
     hipStream_t st = static_cast<hipStream_t>(stream);

@@ -284,8 +284,68 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-class Fbank:
+# mv_melspec_info / mv_spectrogram_info / mv_mfcc_info: the kernel behind the STFT of a handle
+_STFT_KERNELS = {0: 'stft_power_kernel (dense DFT)', 1: 'melspec_tile_kernel', 2: 'melspec_pow2_kernel'}
+
+
+def _forward_inputs(wav, lens_ratio, num_samples, check_shape=True):
+    """what every front-end forward does to its arguments first: ``wav`` [B, L] fp32 with unit stride along time; ``lens_ratio`` (fp32) or
+    ``num_samples`` (int64 [B]) -- never both -- contiguous on wav's device"""
+    if lens_ratio is not None and num_samples is not None:
+        raise ValueError('lens_ratio and num_samples are mutually exclusive')
+    assert wav.dim() == 2 and wav.dtype == torch.float32
+    if wav.stride(1) != 1:
+        wav = wav.contiguous()
+    if num_samples is not None:
+        num_samples = num_samples.to(device=wav.device, dtype=torch.int64).contiguous()
+        if check_shape and num_samples.shape != (wav.shape[0],):
+            raise ValueError(f'num_samples must have shape ({wav.shape[0]},), got {tuple(num_samples.shape)}')
+    if lens_ratio is not None:
+        lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
+    return wav, lens_ratio, num_samples
+
+
+class _FrontEnd:
+    """what the front-end handles share: the native handle ``_h`` of the library ``_cdll`` behind the entry points ``_prefix`` + name, its frame
+    count and its release; and the forward of the STFT handles (MelSpec / Spectrogram / Mfcc): [B, L] fp32 -> [B, T, dim]"""
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(self._cdll, self._prefix + name)
+
+    def num_frames(self, num_samples):
+        t = c_i64()
+        check(self._fn('num_frames')(self._h, num_samples, ctypes.byref(t)), self._cdll)
+        return t.value
+
+    def __call__(self, wav, lens_ratio=None, num_samples=None):
+        """wav [B, L] fp32 -> [B, T(L), dim], on the caller's stream with a workspace per call.  ``lens_ratio``: the reference's batched
+        semantics (mean over all T frames, then mask).  ``num_samples`` (int64 [B]): every row featurised on its own length, zero rows beyond
+        it (mv_*_forward_varlen).  One native call either way."""
+        wav, lens_ratio, num_samples = _forward_inputs(wav, lens_ratio, num_samples)
+        B, L = wav.shape
+        T = self.num_frames(L)
+        out = torch.empty((B, T, self.dim), dtype=torch.float32, device=wav.device)
+        if B == 0 or T == 0:
+            return out
+        nbytes = self._fn('workspace_bytes')(self._h, B, L)
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=wav.device)
+        form, lens = ('forward', lens_ratio) if num_samples is None else ('forward_varlen', num_samples)
+        check(self._fn(form)(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens), out.data_ptr(), ws.data_ptr(), nbytes,
+                             current_stream(wav)), self._cdll)
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, '_h', None):
+                self._fn('destroy')(self._h)
+        except Exception:
+            pass
+
+
+class Fbank(_FrontEnd):
     """Handle of the fused Fbank + CMN + mask kernel (mv_fbank_*)."""
+    _prefix = 'mv_fbank_'
 
     WINDOW_TYPES = {'povey': 0, 'hamming': 1, 'hanning': 2, 'rectangular': 3, 'blackman': 4}
     KERNELS = {'auto': 0, 'generic': 1, 'tile': 2}
@@ -336,11 +396,6 @@ class Fbank:
         self._h = c_vp()
         check(self._cdll.mv_fbank_create(ctypes.byref(cfg), ctypes.byref(self._h)), self._cdll)
 
-    def num_frames(self, num_samples):
-        t = c_i64()
-        check(self._cdll.mv_fbank_num_frames(self._h, num_samples, ctypes.byref(t)), self._cdll)
-        return t.value
-
     def info(self):
         """{'tile_kernel': bool, 'pass_steps': (s0, s1)} -- which kernel the handle launches (mv_fbank_info)"""
         tk, steps = c_i32(), (c_i32 * 2)()
@@ -351,10 +406,8 @@ class Fbank:
         """wav [B, L] fp32 -> [B, T(L), F].  ``lens_ratio``: the reference's batched semantics (mean over all T frames,
         then mask).  ``num_samples`` (int64 [B]): every row featurised on its own length, zero rows beyond it.
         ``workspace=False`` keeps one workgroup per utterance (mv_fbank_forward without scratch; same bits, see the header)."""
-        assert wav.dim() == 2 and wav.dtype == torch.float32
         assert lens_ratio is None or num_samples is None
-        if wav.stride(1) != 1:
-            wav = wav.contiguous()
+        wav, lens_ratio, num_samples = _forward_inputs(wav, lens_ratio, num_samples, check_shape=False)
         B, L = wav.shape
         T = self.num_frames(L)
         out = torch.empty((B, T, self.num_columns), dtype=torch.float32, device=wav.device)
@@ -367,7 +420,6 @@ class Fbank:
         check(self._cdll.mv_fbank_workspace_bytes(self._h, B, L, ctypes.byref(need)), self._cdll)
         ws = torch.empty(need.value, dtype=torch.uint8, device=wav.device) if need.value and (workspace or self._needs_ws) else None
         if num_samples is not None:
-            num_samples = num_samples.to(device=wav.device, dtype=torch.int64).contiguous()
             if ws is None:
                 check(self._cdll.mv_fbank_forward_varlen(self._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
                                                          current_stream(wav)), self._cdll)
@@ -375,148 +427,33 @@ class Fbank:
                 check(self._cdll.mv_fbank_forward_varlen_ws(self._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
                                                             _ptr(ws), need.value, current_stream(wav)), self._cdll)
             return out
-        if lens_ratio is not None:
-            lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
         check(self._cdll.mv_fbank_forward_ws(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(), _ptr(ws),
                                              need.value if ws is not None else 0, current_stream(wav)), self._cdll)
         return out
 
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None):
-                self._cdll.mv_fbank_destroy(self._h)
-        except Exception:
-            pass
 
-
-def _stft_forward(handle, prefix, dim, wav, lens_ratio, num_samples):
-    """the forward of the MelSpec / Spectrogram / Mfcc handles: the caller's stream, a workspace per call; the batch form (``lens_ratio`` or
-    neither) or the variable-length form (``num_samples``), one native call either way"""
-    if lens_ratio is not None and num_samples is not None:
-        raise ValueError('lens_ratio and num_samples are mutually exclusive')
-    assert wav.dim() == 2 and wav.dtype == torch.float32
-    cdll = handle._cdll
-    if wav.stride(1) != 1:
-        wav = wav.contiguous()
-    B, L = wav.shape
-    T = handle.num_frames(L)
-    out = torch.empty((B, T, dim), dtype=torch.float32, device=wav.device)
-    if B == 0 or T == 0:
-        return out
-    nbytes = getattr(cdll, prefix + 'workspace_bytes')(handle._h, B, L)
-    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=wav.device)
-    if num_samples is not None:
-        num_samples = num_samples.to(device=wav.device, dtype=torch.int64).contiguous()
-        if num_samples.shape != (B,):
-            raise ValueError(f'num_samples must have shape ({B},), got {tuple(num_samples.shape)}')
-        check(getattr(cdll, prefix + 'forward_varlen')(handle._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
-                                                       ws.data_ptr(), nbytes, current_stream(wav)), cdll)
-        return out
-    if lens_ratio is not None:
-        lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
-    check(getattr(cdll, prefix + 'forward')(handle._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(),
-                                            ws.data_ptr(), nbytes, current_stream(wav)), cdll)
-    return out
-
-
-class MelSpec:
-    """Handle of the MelSpectrogram + CMN + mask path (mv_melspec_*)."""
-
-    PAD_MODES = {'reflect': 0, 'constant': 1, 'replicate': 2, 'circular': 3}
-
-    def __init__(self, method_args=None, subtract_time_mean=True, cdll=None):
-        self._cdll = cdll or lib()
-        cfg = MvMelSpecCfg()
-        self._cdll.mv_melspec_default_cfg(ctypes.byref(cfg))
-        win_host = self.fill_cfg(cfg, method_args, subtract_time_mean)  # noqa: F841  (alive until create has copied it)
-        self.n_mels = cfg.n_mels
-        self._h = c_vp()
-        check(self._cdll.mv_melspec_create(ctypes.byref(cfg), ctypes.byref(self._h)), self._cdll)
-
-    @classmethod
-    def fill_cfg(cls, cfg, method_args, subtract_time_mean=True):
-        """MelSpectrogram(**method_args) checked as torchaudio checks it, into an MvMelSpecCfg (also the mel stage of Mfcc); returns the
-        host window tensor that cfg.window points to (None for the default), which must stay alive until create"""
-        a = dict(method_args or {})
-        allowed = {'sample_rate', 'n_fft', 'win_length', 'hop_length', 'f_min', 'f_max', 'pad', 'n_mels', 'power',
-                   'normalized', 'center', 'pad_mode', 'onesided', 'norm', 'mel_scale', 'window_fn', 'wkwargs'}
-        for k in a:
-            if k not in allowed:
-                raise TypeError(f"MelSpectrogram got an unexpected keyword argument '{k}'")
-        # not implemented: two-sided spectra (torchaudio's own MelScale refuses their bin count), power=None (a complex spectrogram has no mel scale)
-        if a.get('onesided') not in (None, True) or a.get('power', 2.0) is None:
-            raise NotImplementedError('MelSpectrogram option not implemented by the HIP kernel')
-        if a.get('pad_mode', 'reflect') not in cls.PAD_MODES:
-            raise NotImplementedError(f"Unrecognised padding mode {a.get('pad_mode')}")   # (torch.nn.functional.pad's own error class)
-        if a.get('norm') not in (None, 'slaney'):
-            raise ValueError('norm must be one of None or "slaney"')          # torchaudio.functional.melscale_fbanks' own messages
-        if a.get('mel_scale', 'htk') not in ('htk', 'slaney'):
-            raise ValueError('mel_scale should be one of "htk" or "slaney".')
-        if a.get('normalized', False) not in (False, True, 'window', 'frame_length'):
-            raise ValueError(f"Invalid normalized parameter: {a.get('normalized')}")
-        cfg.sample_rate = int(a.get('sample_rate', 16000))
-        cfg.n_fft = int(a.get('n_fft', 400))
-        win = a.get('win_length')
-        cfg.win_length = int(win if win is not None else cfg.n_fft)
-        hop = a.get('hop_length')
-        cfg.hop_length = int(hop if hop is not None else cfg.win_length // 2)
-        cfg.f_min = float(a.get('f_min', 0.0))
-        f_max = a.get('f_max')
-        cfg.f_max = float(f_max if f_max is not None else cfg.sample_rate // 2)
-        cfg.n_mels = int(a.get('n_mels', 128))
-        cfg.power = float(a.get('power', 2.0))
-        cfg.center = 1 if a.get('center', True) else 0
-        cfg.subtract_time_mean = 1 if subtract_time_mean else 0
-        cfg.mel_scale = 1 if a.get('mel_scale', 'htk') == 'slaney' else 0
-        cfg.norm = 1 if a.get('norm') == 'slaney' else 0
-        cfg.normalized = {False: 0, True: 1, 'window': 1, 'frame_length': 2}[a.get('normalized', False)]
-        cfg.pad = int(a.get('pad', 0))
-        cfg.pad_mode = cls.PAD_MODES[a.get('pad_mode', 'reflect')]
-        win_host = None
-        if a.get('window_fn') is not None:   # torchaudio evaluates window_fn(win_length, **wkwargs) once, at construction: so does this
-            win_host = a['window_fn'](cfg.win_length, **(a.get('wkwargs') or {})).detach().to(device='cpu', dtype=torch.float32).contiguous()
-            if win_host.shape != (cfg.win_length,):
-                raise ValueError(f'window_fn returned {tuple(win_host.shape)}, expected ({cfg.win_length},)')
-            cfg.window = win_host.data_ptr()
-        return win_host
-
-    def info(self):
-        """{'tile_kernel': bool, 'kernel': name}: True when an FFT kernel runs -- melspec_tile_kernel (n_fft = 400) or melspec_pow2_kernel
-        (n_fft 128 ... 1024, power of two) --, False for the dense-DFT kernels"""
-        tk = c_i32()
-        check(self._cdll.mv_melspec_info(self._h, ctypes.byref(tk)), self._cdll)
-        return {'tile_kernel': bool(tk.value), 'kernel': {0: 'stft_power_kernel (dense DFT)', 1: 'melspec_tile_kernel', 2: 'melspec_pow2_kernel'}[tk.value]}
-
-    def num_frames(self, num_samples):
-        t = c_i64()
-        check(self._cdll.mv_melspec_num_frames(self._h, num_samples, ctypes.byref(t)), self._cdll)
-        return t.value
-
-    def __call__(self, wav, lens_ratio=None, num_samples=None):
-        """wav [B, L] fp32 -> [B, T(L), n_mels].  ``lens_ratio``: the reference's batched semantics (mean over all T frames, then mask).
-        ``num_samples`` (int64 [B]): every row featurised on its own length, zero rows beyond it (mv_melspec_forward_varlen)."""
-        return _stft_forward(self, 'mv_melspec_', self.n_mels, wav, lens_ratio, num_samples)
-
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None):
-                self._cdll.mv_melspec_destroy(self._h)
-        except Exception:
-            pass
-
-
+_PAD_MODES = {'reflect': 0, 'constant': 1, 'replicate': 2, 'circular': 3}
+_MEL_KEYS = ('sample_rate', 'n_fft', 'win_length', 'hop_length', 'f_min', 'f_max', 'pad', 'n_mels', 'power', 'normalized', 'center', 'pad_mode',
+             'onesided', 'norm', 'mel_scale', 'window_fn', 'wkwargs')
 _SPEC_KEYS = ('n_fft', 'win_length', 'hop_length', 'pad', 'window_fn', 'power', 'normalized', 'wkwargs', 'center', 'pad_mode', 'onesided',
               'return_complex')
 _MFCC_KEYS = ('sample_rate', 'n_mfcc', 'dct_type', 'norm', 'log_mels', 'melkwargs')
 
 
-def _stft_fields(cfg, a, what):
-    """the STFT keyword arguments torchaudio's Spectrogram / MelSpectrogram share, checked as torchaudio checks them, into `cfg`;
-    returns the host window tensor (kept alive by the caller until create has copied it) or None"""
+def _stft_unsupported(a, what):
+    """the STFT options the kernels do not implement: two-sided spectra (torchaudio's own MelScale refuses their bin count), power=None (the
+    complex spectrogram) and padding modes torch.nn.functional.pad does not know (its own error class)"""
     if a.get('onesided') not in (None, True) or ('power' in a and a['power'] is None):
-        raise NotImplementedError(f'{what} option not implemented by the HIP kernel')   # complex / two-sided output
-    if a.get('pad_mode', 'reflect') not in MelSpec.PAD_MODES:
+        raise NotImplementedError(f'{what} option not implemented by the HIP kernel')
+    if a.get('pad_mode', 'reflect') not in _PAD_MODES:
         raise NotImplementedError(f"Unrecognised padding mode {a.get('pad_mode')}")
+
+
+def _stft_fields(cfg, a, what):
+    """the STFT keyword arguments torchaudio's Spectrogram / MelSpectrogram share, checked as torchaudio checks them, into `cfg`
+    (an MvSpectrogramCfg or an MvMelSpecCfg); returns the host window tensor that cfg.window points to (None for the default), which the
+    caller keeps alive until create has copied it"""
+    _stft_unsupported(a, what)
     if a.get('normalized', False) not in (False, True, 'window', 'frame_length'):
         raise ValueError(f"Invalid normalized parameter: {a.get('normalized')}")
     cfg.n_fft = int(a.get('n_fft', 400))
@@ -528,9 +465,9 @@ def _stft_fields(cfg, a, what):
     cfg.center = 1 if a.get('center', True) else 0
     cfg.normalized = {False: 0, True: 1, 'window': 1, 'frame_length': 2}[a.get('normalized', False)]
     cfg.pad = int(a.get('pad', 0))
-    cfg.pad_mode = MelSpec.PAD_MODES[a.get('pad_mode', 'reflect')]
+    cfg.pad_mode = _PAD_MODES[a.get('pad_mode', 'reflect')]
     win_host = None
-    if a.get('window_fn') is not None:
+    if a.get('window_fn') is not None:   # torchaudio evaluates window_fn(win_length, **wkwargs) once, at construction: so does this
         win_host = a['window_fn'](cfg.win_length, **(a.get('wkwargs') or {})).detach().to(device='cpu', dtype=torch.float32).contiguous()
         if win_host.shape != (cfg.win_length,):
             raise ValueError(f'window_fn returned {tuple(win_host.shape)}, expected ({cfg.win_length},)')
@@ -538,25 +475,50 @@ def _stft_fields(cfg, a, what):
     return win_host
 
 
-class _FrontEnd:
-    """shared forward of the Spectrogram / MFCC handles: [B, L] fp32 -> [B, T, dim] with the caller's stream and a workspace per call"""
-    _prefix = None
+class MelSpec(_FrontEnd):
+    """Handle of the MelSpectrogram + CMN + mask path (mv_melspec_*).  Output [B, T, n_mels]."""
+    _prefix = 'mv_melspec_'
+    PAD_MODES = _PAD_MODES
 
-    def num_frames(self, num_samples):
-        t = c_i64()
-        check(getattr(self._cdll, self._prefix + 'num_frames')(self._h, num_samples, ctypes.byref(t)), self._cdll)
-        return t.value
+    def __init__(self, method_args=None, subtract_time_mean=True, cdll=None):
+        self._cdll = cdll or lib()
+        cfg = MvMelSpecCfg()
+        self._cdll.mv_melspec_default_cfg(ctypes.byref(cfg))
+        win_host = self.fill_cfg(cfg, method_args, subtract_time_mean)  # noqa: F841  (alive until create has copied it)
+        self.n_mels = self.dim = cfg.n_mels
+        self._h = c_vp()
+        check(self._cdll.mv_melspec_create(ctypes.byref(cfg), ctypes.byref(self._h)), self._cdll)
 
-    def __call__(self, wav, lens_ratio=None, num_samples=None):
-        """wav [B, L] fp32 -> [B, T(L), dim]; ``lens_ratio`` (batch form) or ``num_samples`` (int64 [B]: every row on its own length), as MelSpec"""
-        return _stft_forward(self, self._prefix, self.dim, wav, lens_ratio, num_samples)
+    @classmethod
+    def fill_cfg(cls, cfg, method_args, subtract_time_mean=True):
+        """MelSpectrogram(**method_args) checked as torchaudio checks it, into an MvMelSpecCfg (also the mel stage of Mfcc); returns the
+        host window tensor that cfg.window points to (None for the default), which must stay alive until create"""
+        a = dict(method_args or {})
+        for k in a:
+            if k not in _MEL_KEYS:
+                raise TypeError(f"MelSpectrogram got an unexpected keyword argument '{k}'")
+        _stft_unsupported(a, 'MelSpectrogram')   # (in front of MelScale's checks, which torchaudio makes at construction; `normalized` is read later)
+        if a.get('norm') not in (None, 'slaney'):
+            raise ValueError('norm must be one of None or "slaney"')          # torchaudio.functional.melscale_fbanks' own messages
+        if a.get('mel_scale', 'htk') not in ('htk', 'slaney'):
+            raise ValueError('mel_scale should be one of "htk" or "slaney".')
+        win_host = _stft_fields(cfg, a, 'MelSpectrogram')
+        cfg.sample_rate = int(a.get('sample_rate', 16000))
+        cfg.f_min = float(a.get('f_min', 0.0))
+        f_max = a.get('f_max')
+        cfg.f_max = float(f_max if f_max is not None else cfg.sample_rate // 2)
+        cfg.n_mels = int(a.get('n_mels', 128))
+        cfg.subtract_time_mean = 1 if subtract_time_mean else 0
+        cfg.mel_scale = 1 if a.get('mel_scale', 'htk') == 'slaney' else 0
+        cfg.norm = 1 if a.get('norm') == 'slaney' else 0
+        return win_host
 
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None):
-                getattr(self._cdll, self._prefix + 'destroy')(self._h)
-        except Exception:
-            pass
+    def info(self):
+        """{'tile_kernel': bool, 'kernel': name}: True when an FFT kernel runs -- melspec_tile_kernel (n_fft = 400) or melspec_pow2_kernel
+        (n_fft 128 ... 1024, power of two) --, False for the dense-DFT kernels"""
+        tk = c_i32()
+        check(self._cdll.mv_melspec_info(self._h, ctypes.byref(tk)), self._cdll)
+        return {'tile_kernel': bool(tk.value), 'kernel': _STFT_KERNELS[tk.value]}
 
 
 class Spectrogram(_FrontEnd):
@@ -582,7 +544,7 @@ class Spectrogram(_FrontEnd):
         """{'kernel': name}: the fused n_fft = 400 launch or the dense DFT"""
         k = c_i32()
         check(self._cdll.mv_spectrogram_info(self._h, ctypes.byref(k)), self._cdll)
-        return {'kernel': {0: 'stft_power_kernel (dense DFT)', 1: 'melspec_tile_kernel (spectrogram)'}[k.value]}
+        return {'kernel': _STFT_KERNELS[k.value] + (' (spectrogram)' if k.value == 1 else '')}
 
 
 class Mfcc(_FrontEnd):
@@ -625,8 +587,7 @@ class Mfcc(_FrontEnd):
         """{'mel_kernel': name of the mel stage's kernel, 'dct_lds': bool}"""
         k, d = c_i32(), c_i32()
         check(self._cdll.mv_mfcc_info(self._h, ctypes.byref(k), ctypes.byref(d)), self._cdll)
-        return {'mel_kernel': {0: 'stft_power_kernel (dense DFT)', 1: 'melspec_tile_kernel', 2: 'melspec_pow2_kernel'}[k.value],
-                'dct_lds': bool(d.value)}
+        return {'mel_kernel': _STFT_KERNELS[k.value], 'dct_lds': bool(d.value)}
 
 
 def _tensor_refs(state_dict, device=None):
@@ -646,7 +607,7 @@ def _tensor_refs(state_dict, device=None):
     return refs, tensors, names
 
 
-class HfEncoder:
+class HfEncoder(_FrontEnd):
     """Handle of the HuggingFace (Wav2Vec2 / WavLM) front-end (mv_hfenc_*): the processor's z-score, the convolutional feature encoder and
     feature_projection.layer_norm -- `extract_features` --, then AudioFeaturizer's time mean and mask.  Output [B, T', conv_dim[-1]].
 
@@ -654,6 +615,7 @@ class HfEncoder:
     feat_extract_activation, conv_bias, layer_norm_eps) plus ``do_normalize`` (the processor's); ``state_dict``: the Wav2Vec2Model / WavLMModel's,
     under its own key names, on the device the handle is to run on.  Needs no `transformers`."""
 
+    _prefix = 'mv_hfenc_'
     NORMS = {'group': MV_HF_NORM_GROUP, 'layer': MV_HF_NORM_LAYER}
 
     def __init__(self, cfg, state_dict, subtract_time_mean=True, cdll=None, device=None):
@@ -687,23 +649,14 @@ class HfEncoder:
         self._h = c_vp()
         check(self._cdll.mv_hfenc_create(ctypes.byref(c), refs, len(tensors), ctypes.byref(self._h)), self._cdll)
 
-    def num_frames(self, num_samples):
-        t = c_i64()
-        check(self._cdll.mv_hfenc_num_frames(self._h, num_samples, ctypes.byref(t)), self._cdll)
-        return t.value
-
     def __call__(self, wav, lens_ratio=None, num_samples=None, stage_ms=None):
         """wav [B, L] fp32 -> [B, T', dim] fp32 on the same device, the caller's stream, a workspace per call.  ``lens_ratio``: the reference's
         batched semantics (mean over all T' frames, then mask).  ``num_samples`` (int64 [B]): every row featurised on its own length, zero
         frames beyond it (mv_hfenc_forward_varlen; the lengths go to the device and are never read back).  ``stage_ms``: a list that receives
         the milliseconds of every layer and of the tail (mv_hfenc_forward_timed: waits for the forward; tools only; not with ``num_samples``)"""
-        if lens_ratio is not None and num_samples is not None:
-            raise ValueError('lens_ratio and num_samples are mutually exclusive')
+        wav, lens_ratio, num_samples = _forward_inputs(wav, lens_ratio, None if num_samples is None else torch.as_tensor(num_samples))
         if num_samples is not None and stage_ms is not None:
             raise ValueError('stage_ms times the fixed-length forward: it cannot be combined with num_samples')
-        assert wav.dim() == 2 and wav.dtype == torch.float32
-        if wav.stride(1) != 1:
-            wav = wav.contiguous()
         B, L = wav.shape
         T = self.num_frames(L)
         if B == 0:
@@ -713,14 +666,9 @@ class HfEncoder:
         ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=wav.device)
         out = torch.empty((B, max(T, 1), self.dim), dtype=torch.float32, device=wav.device)   # (T <= 0: the forward refuses, with its message)
         if num_samples is not None:
-            num_samples = torch.as_tensor(num_samples).to(device=wav.device, dtype=torch.int64).contiguous()
-            if num_samples.shape != (B,):
-                raise ValueError(f'num_samples must have shape ({B},), got {tuple(num_samples.shape)}')
             check(self._cdll.mv_hfenc_forward_varlen(self._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
                                                      ws.data_ptr(), need.value, current_stream(wav)), self._cdll)
             return out
-        if lens_ratio is not None:
-            lens_ratio = lens_ratio.to(device=wav.device, dtype=torch.float32).contiguous()
         if stage_ms is not None:
             ms = (c_f32 * (self.num_layers + 1))()
             check(self._cdll.mv_hfenc_forward_timed(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(), ws.data_ptr(),
@@ -730,13 +678,6 @@ class HfEncoder:
         check(self._cdll.mv_hfenc_forward(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(), ws.data_ptr(), need.value,
                                           current_stream(wav)), self._cdll)
         return out
-
-    def __del__(self):
-        try:
-            if getattr(self, '_h', None):
-                self._cdll.mv_hfenc_destroy(self._h)
-        except Exception:
-            pass
 
 
 class Model:
@@ -755,18 +696,7 @@ class Model:
             pool = int(pooling_type)   # (a code the library does not know is refused by the create call, with its message)
         if pool != MV_POOL_ASP and kind not in ('ecapa', 'tdnn'):
             raise ValueError(f'pooling_type {pooling_type!r}: only the ecapa and tdnn handles take a pooling head')
-        names, tensors = [], []
-        for k, v in state_dict.items():
-            if not torch.is_floating_point(v):
-                continue  # num_batches_tracked
-            t = v.detach().to(torch.float32).contiguous()
-            names.append(k.encode())
-            tensors.append(t)
-        refs = (MvTensorRef * len(tensors))()
-        for i, (n, t) in enumerate(zip(names, tensors)):
-            refs[i].name = n
-            refs[i].data = t.data_ptr()
-            refs[i].numel = t.numel()
+        refs, tensors, _ = _tensor_refs(state_dict)   # (floating-point entries only: no num_batches_tracked)
         self._h = c_vp()
         if isinstance(cfg, MvEcapaCfgEx):   # EcapaTdnn with other block counts / grouped convolutions: one create call for every head
             if kind != 'ecapa':
