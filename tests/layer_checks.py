@@ -854,6 +854,71 @@ FBANK_ARG_CASES = (
      (dict(sample_frequency=16000, num_mel_bins=40, use_energy=True, energy_floor=0.0, snip_edges=False), dict(varlen=True))])
 
 
+FBANK_FRAME_LENGTHS = [20.0, 24.0, 25.0, 26.0, 27.0, 28.0, 30.0, 32.0]   # ms at 16 kHz: 10, 12, 13, 13, 14, 14, 15, 16 groups of 32 samples
+
+
+def fbank_frame_length_case(cdll, device, frame_length):
+    """80 bins at one frame length on rows that start on 8-byte boundaries (the VEC2 instantiations): fbank_tile_kernel and fbank_kernel against the oracle"""
+    from oracle import frontend
+    args = dict(_FB80, frame_length=frame_length)
+    assert _hip.Fbank(args, cdll=cdll).info()['tile_kernel']
+    assert not _hip.Fbank(args, cdll=cdll, kernel='generic').info()['tile_kernel']
+    wav = frontend.synth_waveforms(2, 24080, seed=3)
+    ratio = torch.tensor([1.0, 0.6])
+    fbank_case(cdll, device, wav, ratio, args)
+    fbank_case(cdll, device, wav, ratio, args, kernel='generic')
+
+
+def fbank_generic_waves(pass_steps):
+    """waves per workgroup of fbank_kernel by the LDS rule of csrc/fbank.hip (generic_waves): the most of 15, 12, 8 whose frame slots (4 frames of 548
+    floats per wave) fit 160 KB next to three 512-float tables and the mel weights (64 floats per step of the two passes)"""
+    for waves in (15, 12, 8):
+        if (waves * 4 * 548 + 3 * 512 + 64 * sum(pass_steps)) * 4 <= 160 * 1024:
+            return waves
+    return 0
+
+
+_VTLN12 = dict(sample_frequency=16000, num_mel_bins=40, vtln_warp=1.2, vtln_low=300.0, vtln_high=-800.0)   # 104 mel steps: fbank_kernel on 12 waves
+
+
+def fbank_generic_kernel_rows(cdll):
+    """Which rows of fbank.hip's GENERIC_KERNELS table -- (13 or 16 sample groups, alignment, waves) -- the Fbank tests launch.  The groups follow the
+    window (FBANK_ARG_CASES and test_*_fbank_other_frame_lengths_with_80_bins hold 400- and 416-sample windows = 13 groups, and others = 16), the
+    alignment the rows (odd strides in fbank_arguments_case, even ones in the frame-length sweep), the waves the mel table: computed here for every
+    configuration of both lists, 15 each time except the 40-bin VTLN warp of 1.2 (104 steps, 15 waves hold 102), which runs <13, unaligned, 12>; the
+    other three 12-wave rows are fbank_generic_12_waves_case's.  The 8-wave rows (more than 205 steps) are launched by no test: no configuration
+    that reaches them is known."""
+    cfgs = [args for args, _ in FBANK_ARG_CASES] + [dict(_FB80, frame_length=fl) for fl in FBANK_FRAME_LENGTHS]
+    for args in cfgs:
+        steps = _hip.Fbank(args, cdll=cdll, kernel='generic').info()['pass_steps']
+        assert fbank_generic_waves(steps) == (12 if args.get('vtln_warp') == 1.2 else 15), (args, steps)
+
+
+FBANK_12_WAVE_CASES = [(25.0, False), (20.0, False), (20.0, True)]   # (frame_length, misaligned) = the rows <13, aligned>, <16, aligned>, <16, unaligned>
+
+
+def fbank_generic_12_waves_case(cdll, device, frame_length, misaligned):
+    """fbank_kernel<NG, VEC2, 12> on B = 2, T = 5 frames (one full quad and one partial) against the oracle"""
+    from oracle import frontend
+    args = dict(_VTLN12, frame_length=frame_length)
+    assert fbank_generic_waves(_hip.Fbank(args, cdll=cdll, kernel='generic').info()['pass_steps']) == 12
+    wav = frontend.synth_waveforms(2, int(16 * frame_length) + 160 * 4, seed=52)
+    return fbank_case(cdll, device, wav, torch.tensor([1.0, 0.6]), args, kernel='generic', misaligned=misaligned)
+
+
+def fbank_tile_16_groups_unaligned_case(cdll, device, form):
+    """fbank_tile_kernel<16, VEC2 = false>, the one row of fbank.hip's TILE_KERNELS table no other test launches (the 80-bin tests with unaligned
+    rows hold windows of 10 / 12 / 13 / 15 sample groups): a 28 ms window (448 samples = 14 groups, no row of its own) on a waveform view that starts
+    one float into its buffer.  form 'chunked': B = 2, T = 64 frames with the product workspace (two chunks of 8 quads + the finish pass);
+    'beyond_lds': B = 2, T = 300 frames on one workgroup each, more rows than stay in LDS."""
+    from oracle import frontend
+    args = dict(_FB80, frame_length=28.0)
+    T = dict(chunked=64, beyond_lds=300)[form]
+    wav = frontend.synth_waveforms(2, 448 + 160 * (T - 1), seed=51)
+    assert _hip.Fbank(args, cdll=cdll, kernel='tile').num_frames(wav.shape[1]) == T
+    return fbank_case(cdll, device, wav, torch.tensor([1.0, 0.7]), args, kernel='tile', misaligned=True, workspace=form == 'chunked')
+
+
 def fbank_arguments_case(cdll, device, idx, B=3, seconds=0.5, seed=None, check_rows=None):
     """one entry of FBANK_ARG_CASES on B utterances of `seconds`: a fixed-length batch with a length mask (or bare rows / ragged true lengths).
     check_rows: compare only these rows with the oracle (rows are independent; a batch larger than the chip then costs a few oracle rows)"""
@@ -889,14 +954,21 @@ def fbank_min_duration_edge(cdll, device):
             fbank_case(cdll, device, wav, None, args, kernel=kernel, num_samples=ns)
 
 
-def fbank_case(cdll, device, wav, ratio, method_args, kernel='auto', cmn=True, num_samples=None, check_rows=None):
+def fbank_case(cdll, device, wav, ratio, method_args, kernel='auto', cmn=True, num_samples=None, check_rows=None, misaligned=False, workspace=True):
     """HIP Fbank (+ time mean + mask) against the fp32 oracle AND the fp64 arbiter of the same algorithm.  `kernel`: 'auto' | 'generic' | 'tile'
     (MvFbankCfg.kernel).  cmn=False: the bare kaldi.fbank rows (KaldiFbank, featurizer.py:114-132).  num_samples: the variable-length entry point
-    (every row on its own length, zero rows behind it).  Log energies are compared in absolute terms (the stated 1e-3); linear ones
-    (use_log_fbank=False) relative to the largest energy of the batch."""
+    (every row on its own length, zero rows behind it).  misaligned: the waveform is a view that starts one float into its buffer (the kernels'
+    VEC2 = false instantiations).  workspace=False: one workgroup per utterance.  Log energies are compared in absolute terms (the stated 1e-3);
+    linear ones (use_log_fbank=False) relative to the largest energy of the batch."""
     from oracle import frontend
     fb = _hip.Fbank(method_args, cdll=cdll, kernel=kernel, subtract_time_mean=cmn)
-    out = fb(wav.to(device), None if ratio is None else ratio.to(device), None if num_samples is None else num_samples.to(device)).cpu()
+    dwav = wav.to(device)
+    if misaligned:
+        flat = torch.empty(wav.numel() + 1, device=device)
+        flat[1:] = wav.reshape(-1)
+        dwav = flat[1:].view(wav.shape)
+        assert dwav.data_ptr() % 8 == 4 and dwav.is_contiguous()
+    out = fb(dwav, None if ratio is None else ratio.to(device), None if num_samples is None else num_samples.to(device), workspace=workspace).cpu()
     if check_rows is not None:   # the launch saw the whole batch; the oracle only these rows
         rows = torch.as_tensor(check_rows)
         out, wav = out[rows], wav[rows]

@@ -451,18 +451,12 @@ def test_unsupported_constructor_arguments_are_named_not_approximated():
     assert not ok and 'growth_rate' in why
 
 
-@pytest.mark.parametrize('frame_length', [20.0, 24.0, 25.0, 26.0, 27.0, 28.0, 30.0, 32.0])
+@pytest.mark.parametrize('frame_length', lc.FBANK_FRAME_LENGTHS)
 def test_emu_fbank_other_frame_lengths_with_80_bins(frame_length):
     """kaldi.fbank's frame_length is a method argument (featurizer.py:128).  Windows of 385 .. 416 samples (25 / 26 ms at 16 kHz) run the 13-group instantiation of
     fbank_tile_kernel, every other even window the 16-group one -- which gave wrong features for windows of <= 384 samples until round 5 (20 ms: 9.9 off; its LDS window
     table was 448 taps, groups 14 / 15 read behind it; found by tools/emu_fuzz.py).  Both kernels, every window, against the oracle."""
-    args = dict(sample_frequency=16000, num_mel_bins=80, frame_length=frame_length)
-    assert lc._hip.Fbank(args, cdll=emu_cdll()).info()['tile_kernel']
-    assert not lc._hip.Fbank(args, cdll=emu_cdll(), kernel='generic').info()['tile_kernel']
-    wav = frontend.synth_waveforms(2, 24080, seed=3)
-    ratio = torch.tensor([1.0, 0.6])
-    lc.fbank_case(emu_cdll(), 'cpu', wav, ratio, args)
-    lc.fbank_case(emu_cdll(), 'cpu', wav, ratio, args, kernel='generic')
+    lc.fbank_frame_length_case(emu_cdll(), 'cpu', frame_length)
 
 
 @pytest.mark.parametrize('idx', range(len(lc.FBANK_ARG_CASES)))
@@ -471,6 +465,20 @@ def test_emu_fbank_arguments(idx):
     magnitude / linear outputs, DC / pre-emphasis switches, the five window types, snip_edges=False, subtract_mean, min_duration, VTLN warps) x (kernel, bare rows, true lengths):
     tests/layer_checks.py::FBANK_ARG_CASES, the list the device sweep (test_gpu_fbank_arguments) runs at 3 s"""
     lc.fbank_arguments_case(emu_cdll(), 'cpu', idx)
+
+
+def test_emu_fbank_generic_kernel_table_rows_of_the_suite():
+    lc.fbank_generic_kernel_rows(emu_cdll())
+
+
+@pytest.mark.parametrize('frame_length,misaligned', lc.FBANK_12_WAVE_CASES)
+def test_emu_fbank_generic_kernel_on_12_waves(frame_length, misaligned):
+    lc.fbank_generic_12_waves_case(emu_cdll(), 'cpu', frame_length, misaligned)
+
+
+@pytest.mark.parametrize('form', ['chunked', 'beyond_lds'])
+def test_emu_fbank_tile_kernel_16_groups_on_unaligned_rows(form):
+    lc.fbank_tile_16_groups_unaligned_case(emu_cdll(), 'cpu', form)
 
 
 def test_emu_fbank_clip_of_exactly_min_duration_keeps_its_frames():

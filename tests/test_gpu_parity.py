@@ -299,6 +299,27 @@ def test_gpu_fbank_arguments(idx):
     lc.fbank_arguments_case(product_lib(), DEV, idx, B=260, seconds=0.5, seed=7, check_rows=[0, 1, 2, 3, 4, 130, 255, 256, 257, 258, 259])
 
 
+@pytest.mark.parametrize('frame_length', lc.FBANK_FRAME_LENGTHS)
+def test_gpu_fbank_other_frame_lengths_with_80_bins(frame_length):
+    """the aligned (VEC2) rows of both kernel tables on the device: fbank_tile_kernel<10 / 12 / 13 / 15 / 16> and fbank_kernel<13 / 16> on rows that
+    start on 8-byte boundaries, which test_gpu_fbank_arguments' odd strides do not reach"""
+    lc.fbank_frame_length_case(product_lib(), DEV, frame_length)
+
+
+def test_gpu_fbank_generic_kernel_table_rows_of_the_suite():
+    lc.fbank_generic_kernel_rows(product_lib())
+
+
+@pytest.mark.parametrize('frame_length,misaligned', lc.FBANK_12_WAVE_CASES)
+def test_gpu_fbank_generic_kernel_on_12_waves(frame_length, misaligned):
+    lc.fbank_generic_12_waves_case(product_lib(), DEV, frame_length, misaligned)
+
+
+@pytest.mark.parametrize('form', ['chunked', 'beyond_lds'])
+def test_gpu_fbank_tile_kernel_16_groups_on_unaligned_rows(form):
+    lc.fbank_tile_16_groups_unaligned_case(product_lib(), DEV, form)
+
+
 def test_gpu_fbank_clip_of_exactly_min_duration_keeps_its_frames():
     """L == min_duration * sample_frequency is featurised (torchaudio's double compare), L - 1 is not -- both kernels, device"""
     lc.fbank_min_duration_edge(product_lib(), DEV)

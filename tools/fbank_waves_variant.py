@@ -88,8 +88,8 @@ def make(name, waves, lean=True, bounds=None):
         load_quad(q, ra);
         process_quad(q, ra, ra);
     }''')
-        rep('    return ((size_t)mv::FBT_WAVES * mv::FBT_SLOT_FLOATS + mv::FBT_WIN_FLOATS + 512) * sizeof(float);',
-            '    return ((size_t)mv::FBT_WAVES * mv::FBT_SLOT_FLOATS + mv::FBT_WIN_FLOATS + 512 + 512) * sizeof(float);')
+        rep('    return ((size_t)mv::FBT_WAVES * mv::FBT_SLOT_FLOATS + mv::fbt_win_floats(tile_ng(win)) + 512) * sizeof(float);',
+            '    return ((size_t)mv::FBT_WAVES * mv::FBT_SLOT_FLOATS + mv::fbt_win_floats(tile_ng(win)) + 512 + 512) * sizeof(float);')
     open(d + '/fbank.hip', 'w').write(s)
     obj = d + '/fbank.o'
     r = subprocess.run(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '-DNDEBUG', '-fno-slp-vectorize',

@@ -27,8 +27,8 @@ def edits(name):
     if name == 'trace':
         E += [('namespace mv {\n', TRACE_DEF, 'first'),
               ("    float csum0 = 0.0f, csum1 = 0.0f;   // this wave's column sums (slot", "    int fb_it = 0;\n    float csum0 = 0.0f, csum1 = 0.0f;   // this wave's column sums (slot", 'only'),
-              ('        float x0[NG], x1[NG];\n#pragma unroll\n        for (int n1 = 0; n1 < NG; ++n1) {\n            const int idx = 32 * n1 + 2 * l16;\n            const bool full = NG == 13 ? n1 < 12 : 32 * n1 + 32 <= a.win;\n            x0[n1] = full',
-               '        FB_T(0);\n        float x0[NG], x1[NG];\n#pragma unroll\n        for (int n1 = 0; n1 < NG; ++n1) {\n            const int idx = 32 * n1 + 2 * l16;\n            const bool full = NG == 13 ? n1 < 12 : 32 * n1 + 32 <= a.win;\n            x0[n1] = full', 'last'),
+              ('        float x0[NG], x1[NG];\n#pragma unroll\n        for (int n1 = 0; n1 < NG; ++n1) {\n            const int idx = 32 * n1 + 2 * l16;\n            const bool full = NG < 16 ? n1 < NG - 1 : 32 * n1 + 32 <= a.win;   // NG < 16 is launched for 32 (NG - 1) < win <= 32 NG only\n            x0[n1] = full',
+               '        FB_T(0);\n        float x0[NG], x1[NG];\n#pragma unroll\n        for (int n1 = 0; n1 < NG; ++n1) {\n            const int idx = 32 * n1 + 2 * l16;\n            const bool full = NG < 16 ? n1 < NG - 1 : 32 * n1 + 32 <= a.win;   // NG < 16 is launched for 32 (NG - 1) < win <= 32 NG only\n            x0[n1] = full', 'last'),
               ('        if (q + FBT_WAVES < nquads) load_quad(q + FBT_WAVES, r_next);\n', '        FB_T(1);\n        if (q + FBT_WAVES < nquads) load_quad(q + FBT_WAVES, r_next);\n', 'only'),
               ('        // ---- the one transpose ----\n', '        FB_T(2);\n        // ---- the one transpose ----\n', 'last'),
               ('        // ---- stage 2 -> z[k2] = Z[l16 + 16 k2] (halved) ----\n        fft16(z);\n', '        FB_T(3);\n        // ---- stage 2 -> z[k2] = Z[l16 + 16 k2] (halved) ----\n        fft16(z);\n        FB_T(4);\n', 'only'),
@@ -79,7 +79,7 @@ def edits(name):
                '        for (int j = 0; j < 1; ++j) p_own[16 * j] = pk[0] + pk[1] + pk[2] + pk[3] + pk[4] + pk[5] + pk[6] + pk[7] + pp[0] + pp[1] + pp[2] + pp[3] + pp[4] + pp[5] + pp[6] + pp[7];\n', 'only')]
     elif name == 'occ4':
         E += [('__global__ __launch_bounds__(FBT_WAVES * 64) void fbank_tile_kernel', '__global__ __launch_bounds__(FBT_WAVES * 64, 4) void fbank_tile_kernel', 'only'),
-              ('            a.tile_rows = (int)(plan.fit < plan.need ? plan.fit : plan.need);\n', '            a.tile_rows = 0;  // PROBE: no LDS block -> 70 KB per workgroup, two workgroups per CU\n', 'only')]
+              ('        a.tile_rows = (int)(plan.fit < plan.need ? plan.fit : plan.need);\n', '        a.tile_rows = 0;  // PROBE: no LDS block -> 70 KB per workgroup, two workgroups per CU\n', 'only')]
     return E
 
 

@@ -22,6 +22,11 @@
 // One workgroup owns one utterance, so the per-utterance time mean is a workgroup reduction and the
 // second pass (subtract mean, apply the length mask) re-reads rows this CU has just written (L2 hits).
 //
+// Host side (below the kernels): mv_fbank_create = check_cfg, the table builders (window, twiddles, mel banks on the FFT grid, LDS budget) and
+// a handle owned by unique_ptr until it is handed out; the instantiations are named once, in GENERIC_KERNELS and TILE_KERNELS, and a handle holds
+// its two rows.  A forward = fbank_plan (T and the workspace sections), checks, the optional mirror pass, one of three mel launches (tile kernel
+// in chunks + finish pass, tile kernel on one workgroup per utterance, generic kernel), the optional energy pass.
+//
 // hipcc-flags: -fno-slp-vectorize -fno-signed-zeros
 //   (complex math is written on float2 vectors where packed ops pay; the SLP pass would additionally pair up scalar chains
 //    -- DC sums, pre-emphasis, the paired post-processing -- at the price of two v_mov per packed op; without signed zeros
@@ -29,6 +34,7 @@
 #include "frontend_common.h"
 
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 namespace mv {
@@ -46,11 +52,7 @@ struct FbankTables {
     const float* tw512;     // [256][2] cos, sin of 2 pi k / 512
     const float* melb;      // [steps/4][64 lanes][4] mel weights in MFMA B-operand order, passes back to back
     int melb_elems;
-    int passes;                           // (copied from the MelPlan of frontend_common.h)
-    int pass_steps[FB_MAX_PASSES];        // bins walked per pass (multiple of 4)
-    int pass_split[FB_MAX_PASSES];        // 1, 2 or 4 adjacent blocks share one filter group (each walks a part of its bins)
-    int pass_gbase[FB_MAX_PASSES];        // first filter group (4 filters) of the pass
-    int pass_start[FB_MAX_PASSES][16];    // first bin of each block (multiple of 4, start + steps <= 256)
+    MelPlan plan;           // the walk of the mel stage over the 256 bins of a power row (frontend_common.h: start + steps <= 256)
 };
 
 struct FbankArgs {
@@ -109,7 +111,7 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_kernel(FbankArgs a) {
     int T = a.T;
     if (a.num_samples != nullptr) {
         const int64_t ns = a.num_samples[b];
-        const int64_t tb = ns < a.min_len ? 0 : 1 + (ns - a.win) / a.shift;
+        const int64_t tb = fbank_num_frames(ns, a.min_len, a.win, a.shift);
         T = (int)(tb < a.T ? tb : a.T);
     }
     const int nbins = a.nbins;
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_kernel(FbankArgs a) {
     const float* arow = wslots + (lane & 3) * FB_SLOT_FLOATS;
     int mstart[FB_MAX_PASSES];
 #pragma unroll
-    for (int p = 0; p < FB_MAX_PASSES; ++p) mstart[p] = a.tab.pass_start[p][lane >> 2];
+    for (int p = 0; p < FB_MAX_PASSES; ++p) mstart[p] = a.tab.plan.pass_start[p][lane >> 2];
     float csum[FB_MAX_PASSES];
 #pragma unroll
     for (int p = 0; p < FB_MAX_PASSES; ++p) csum[p] = 0.0f;
@@ -266,9 +268,9 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_kernel(FbankArgs a) {
         int moff = 0;
 #pragma unroll
         for (int p = 0; p < FB_MAX_PASSES; ++p) {
-            if (p < a.tab.passes) {
+            if (p < a.tab.plan.passes) {
                 float4v acc = float4v{0.0f, 0.0f, 0.0f, 0.0f}, acc2 = float4v{0.0f, 0.0f, 0.0f, 0.0f};
-                const int ngrp = a.tab.pass_steps[p] >> 2;
+                const int ngrp = a.tab.plan.pass_steps[p] >> 2;
                 const float* ap = arow + mstart[p];
                 const float* bp = melb + moff * 64 + lane * 4;
                 for (int g = 0; g < ngrp; ++g) {
@@ -280,9 +282,9 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_kernel(FbankArgs a) {
                     acc2 = fb_mfma4(av[3], bv[3], acc2);
                 }
                 acc += acc2;
-                moff += a.tab.pass_steps[p];
+                moff += a.tab.plan.pass_steps[p];
                 // blocks that share a filter group hold partial sums over disjoint bin ranges: add them up
-                const int split = a.tab.pass_split[p];
+                const int split = a.tab.plan.pass_split[p];
                 if (split >= 2) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) acc[r] += __shfl_xor(acc[r], 4);
@@ -292,7 +294,7 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_kernel(FbankArgs a) {
                     for (int r = 0; r < 4; ++r) acc[r] += __shfl_xor(acc[r], 8);
                 }
                 const int blk = lane >> 2;
-                const int m = 4 * (a.tab.pass_gbase[p] + blk / split) + (lane & 3);  // filter of this lane
+                const int m = 4 * (a.tab.plan.pass_gbase[p] + blk / split) + (lane & 3);  // filter of this lane
                 if (m < nbins && (blk & (split - 1)) == 0) {
                     float val[4];
 #pragma unroll
@@ -321,9 +323,9 @@ __global__ __launch_bounds__(FB_WAVES * 64) void fbank_kernel(FbankArgs a) {
     __syncthreads();  // every wave has left the frame loop: the slot area becomes the reduction buffer
 #pragma unroll
     for (int p = 0; p < FB_MAX_PASSES; ++p) {
-        if (p < a.tab.passes) {
-            const int split = a.tab.pass_split[p], blk = lane >> 2;
-            const int m = 4 * (a.tab.pass_gbase[p] + blk / split) + (lane & 3);
+        if (p < a.tab.plan.passes) {
+            const int split = a.tab.plan.pass_split[p], blk = lane >> 2;
+            const int m = 4 * (a.tab.plan.pass_gbase[p] + blk / split) + (lane & 3);
             if (m < 128 && (blk & (split - 1)) == 0) colsum[wave * 128 + m] = csum[p];  // every filter has exactly one owner lane
         }
     }
@@ -411,7 +413,7 @@ __global__ __launch_bounds__(FBT_WAVES * 64) void fbank_tile_kernel(FbankArgs a)
     int T = a.T;
     if (a.num_samples != nullptr) {
         const int64_t ns = a.num_samples[b];
-        const int64_t tb = ns < a.min_len ? 0 : 1 + (ns - a.win) / a.shift;
+        const int64_t tb = fbank_num_frames(ns, a.min_len, a.win, a.shift);
         T = (int)(tb < a.T ? tb : a.T);
     }
     const int nbins = a.nbins;
@@ -443,12 +445,12 @@ __global__ __launch_bounds__(FBT_WAVES * 64) void fbank_tile_kernel(FbankArgs a)
 
     // mel stage: lane = (block = lane / 4, i = lane % 4): A operand = power of frame i, D = 4 frames x filter
     const float* arow = wslot + (lane & 3) * FBT_PSTR;
-    const float* ap0 = arow + a.tab.pass_start[0][lane >> 2];
-    const float* ap1 = arow + a.tab.pass_start[1][lane >> 2];
+    const float* ap0 = arow + a.tab.plan.pass_start[0][lane >> 2];
+    const float* ap1 = arow + a.tab.plan.pass_start[1][lane >> 2];
     const int blk = lane >> 2;
-    const int split1 = a.tab.pass_split[1];
-    const int m0 = 4 * (a.tab.pass_gbase[0] + blk) + (lane & 3);                // pass 0: one block per filter group
-    const int m1 = 4 * (a.tab.pass_gbase[1] + blk / split1) + (lane & 3);
+    const int split1 = a.tab.plan.pass_split[1];
+    const int m0 = 4 * (a.tab.plan.pass_gbase[0] + blk) + (lane & 3);                // pass 0: one block per filter group
+    const int m1 = 4 * (a.tab.plan.pass_gbase[1] + blk / split1) + (lane & 3);
     const bool own0 = m0 < nbins, own1 = m1 < nbins && (blk & (split1 - 1)) == 0;
     float csum0 = 0.0f, csum1 = 0.0f;   // this wave's column sums (slot `wave` of FbankArgs' summation order)
     const int tile_rows = a.tile_rows;
@@ -861,6 +863,14 @@ __global__ __launch_bounds__(256) void fbank_mirror_kernel(const float* wav, int
     }
 }
 
+// one instantiation of fbank_kernel or fbank_tile_kernel as the host tables list it: NG sample groups, VEC2, waves per workgroup
+struct FbankKernelRow {
+    int ng;
+    bool vec2;
+    int waves;
+    void (*fn)(FbankArgs);
+};
+
 }  // namespace mv
 
 // ------------------------------------------------------------------------------------------ host side
@@ -876,12 +886,15 @@ struct MvFbank {
     float* d_tw512 = nullptr;
     float* d_melb = nullptr;
     mv::FbankTables tab;
-    size_t smem_bytes = 0;
-    int waves = 15;  // fbank_kernel: workgroup size in waves (15 waves x 5 quads = the 75 quads of a 3 s utterance); 12 / 8 when a long mel table leaves less LDS
+    size_t smem_bytes = 0;     // fbank_kernel: dynamic LDS of a launch
+    int waves = 15;            // fbank_kernel: workgroup size in waves (generic_waves)
     bool tile_kernel = false;  // the mel geometry matches an instantiation of fbank_tile_kernel (every other geometry: fbank_kernel)
+    const mv::FbankKernelRow* kernel[2] = {nullptr, nullptr};   // the table rows this handle launches: [1] when rows and frames start on 8-byte boundaries, else [0]
 };
 
 namespace {
+
+using mv::FbankKernelRow;
 
 // Kaldi mel banks, triangles in mel space (oracle/frontend.py::kaldi_mel_banks = torchaudio.compliance.kaldi.get_mel_banks), fp32 like torchaudio.
 // vtln_warp != 1: the filter edges pass through Kaldi's 3-piece linear VTLN warp (vtln_warp_freq) and the weights follow the warped branch's
@@ -936,102 +949,152 @@ bool kaldi_mel_banks(int num_bins, int padded, float sample_freq, float low_freq
     return true;
 }
 
-template <typename T>
-int upload(const std::vector<T>& v, T** dptr) {
-    MV_HIP_OK(hipMalloc(reinterpret_cast<void**>(dptr), v.size() * sizeof(T)));
-    MV_HIP_OK(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+// a create call's handle until it is handed to the caller: every early return destroys it
+using FbankPtr = std::unique_ptr<MvFbank, decltype(&mv_fbank_destroy)>;
+
+// ---- the kernel tables: the only places that name the instantiations.  The attribute loop (dynamic LDS above 64 KiB has to be requested per
+// kernel) and every launch go through them; a handle resolves its two rows (rows on 8-byte boundaries or not) at create.
+// fbank_kernel: 13 sample groups when 384 < win <= 416, else 16; 15, 12 or 8 waves (generic_waves).
+// fbank_tile_kernel, instantiated for the mel geometry of the reference configurations -- 80 bins at 16 kHz on a 512-point FFT = a pass of 16
+// filter groups (7 four-bin steps) and a pass of 4 groups, each split over 4 blocks (3 steps): the window's own group count when listed, else 16.
+constexpr int FBT_G0 = 7, FBT_G1 = 3;
+
+#define MV_FB_ROWS(NG, V) {NG, V, 15, mv::fbank_kernel<NG, V, 15>}, {NG, V, 12, mv::fbank_kernel<NG, V, 12>}, {NG, V, 8, mv::fbank_kernel<NG, V, 8>}
+constexpr FbankKernelRow GENERIC_KERNELS[] = {MV_FB_ROWS(13, true), MV_FB_ROWS(13, false), MV_FB_ROWS(16, true), MV_FB_ROWS(16, false)};
+#undef MV_FB_ROWS
+#define MV_FBT_ROWS(NG) {NG, true, mv::FBT_WAVES, mv::fbank_tile_kernel<NG, true, FBT_G0, FBT_G1>}, {NG, false, mv::FBT_WAVES, mv::fbank_tile_kernel<NG, false, FBT_G0, FBT_G1>}
+constexpr FbankKernelRow TILE_KERNELS[] = {MV_FBT_ROWS(10), MV_FBT_ROWS(12), MV_FBT_ROWS(13), MV_FBT_ROWS(15), MV_FBT_ROWS(16)};
+#undef MV_FBT_ROWS
+
+template <size_t N>
+constexpr const FbankKernelRow* find_kernel(const FbankKernelRow (&table)[N], int ng, bool vec2, int waves) {
+    for (size_t i = 0; i < N; ++i)
+        if (table[i].ng == ng && table[i].vec2 == vec2 && table[i].waves == waves) return &table[i];
+    return nullptr;
+}
+
+template <size_t N>
+hipError_t reserve_lds(const FbankKernelRow (&table)[N], size_t bytes) {
+    hipError_t e = hipSuccess;
+    for (size_t i = 0; i < N && e == hipSuccess; ++i) e = MV_SET_MAX_SMEM(table[i].fn, bytes);
+    return e;
+}
+
+int generic_ng(int win) { return win > 12 * 32 && win <= 13 * 32 ? 13 : 16; }
+
+int tile_ng(int win) {
+    const int ng = (win + 31) / 32;
+    return find_kernel(TILE_KERNELS, ng, true, mv::FBT_WAVES) != nullptr ? ng : 16;
+}
+
+// every (window, alignment, waves) a handle can ask for has its row: no lookup comes back empty
+constexpr bool generic_kernels_complete() {
+    for (int ng : {13, 16})
+        for (int waves : {15, 12, 8})
+            if (find_kernel(GENERIC_KERNELS, ng, true, waves) == nullptr || find_kernel(GENERIC_KERNELS, ng, false, waves) == nullptr) return false;
+    return true;
+}
+static_assert(generic_kernels_complete(), "GENERIC_KERNELS: 13 and 16 groups x both alignments x 15, 12, 8 waves");
+static_assert(find_kernel(TILE_KERNELS, 16, true, mv::FBT_WAVES) != nullptr && find_kernel(TILE_KERNELS, 16, false, mv::FBT_WAVES) != nullptr,
+              "TILE_KERNELS: the 16-group rows take every window without a row of its own");
+
+// ---- create: checks, table builders
+
+// what create refuses before it allocates, in this order (when two fields are wrong the earlier message wins)
+int check_cfg(const MvFbankCfg* cfg, int win, int shift) {
+    MV_REQUIRE(shift >= 1, "mv_fbank_create: frame shift must be at least one sample");
+    MV_REQUIRE(cfg->num_mel_bins >= 4 && cfg->num_mel_bins <= 64 * mv::FB_MAX_PASSES,
+               "mv_fbank_create: num_mel_bins must be in [4, 128] (torchaudio's get_mel_banks asserts num_bins > 3)");
+    {   // torchaudio.compliance.kaldi.get_mel_banks asserts on the band the same way ("Bad values in options: low-freq ... and high-freq ... vs. nyquist ...")
+        const float nyq = 0.5f * cfg->sample_frequency, hi = cfg->high_freq <= 0.0f ? cfg->high_freq + nyq : cfg->high_freq;
+        MV_REQUIRE(cfg->low_freq >= 0.0f && cfg->low_freq < nyq && hi > 0.0f && hi <= nyq && cfg->low_freq < hi,
+                   "mv_fbank_create: bad band (need 0 <= low_freq < nyquist, 0 < high_freq <= nyquist and low_freq < high_freq; high_freq <= 0 counts from nyquist)");
+    }
+    if (win < 2 || win > mv::FB_NFFT)
+        return mv::fail(MV_ERR_UNSUPPORTED,
+                        "mv_fbank_create: only frame lengths of 2 .. 512 samples (an FFT of up to 512 points, e.g. 25 ms at 16 kHz) are "
+                        "implemented on gfx950");
+    MV_REQUIRE(cfg->window_type >= MV_WINDOW_POVEY && cfg->window_type <= MV_WINDOW_BLACKMAN, "mv_fbank_create: unknown window_type");
+    MV_REQUIRE(cfg->kernel >= MV_FBANK_KERNEL_AUTO && cfg->kernel <= MV_FBANK_KERNEL_TILE, "mv_fbank_create: unknown kernel selector");
+    MV_REQUIRE(cfg->min_duration >= 0.0f, "mv_fbank_create: negative min_duration");
+    MV_REQUIRE(cfg->preemphasis_coefficient >= 0.0f && cfg->preemphasis_coefficient <= 1.0f,
+               "mv_fbank_create: preemphasis_coefficient must be in [0, 1] (torchaudio asserts the same)");
+    MV_REQUIRE(cfg->vtln_warp > 0.0f, "mv_fbank_create: vtln_warp must be positive");
+    MV_REQUIRE((cfg->use_energy == 0 || cfg->use_energy == 1) && (cfg->raw_energy == 0 || cfg->raw_energy == 1) && (cfg->htk_compat == 0 || cfg->htk_compat == 1) &&
+                   cfg->energy_floor >= 0.0f, "mv_fbank_create: use_energy / raw_energy / htk_compat are 0 or 1, energy_floor is not negative");
+    MV_REQUIRE(cfg->min_samples >= 0, "mv_fbank_create: negative min_samples");
     return MV_OK;
 }
 
+// torchaudio.compliance.kaldi._feature_window_function (all symmetric, periodic=False) on the 512-point grid, zero beyond the frame length, and its half
+void kaldi_window(const MvFbankCfg* cfg, int win, std::vector<float>* window, std::vector<float>* window_half) {
+    const double pi = 3.14159265358979323846;
+    window->assign(512, 0.0f);
+    window_half->assign(512, 0.0f);
+    for (int i = 0; i < win; ++i) {
+        const double a = 2.0 * pi / (win - 1);
+        double w = 1.0;                                                                       // rectangular
+        if (cfg->window_type == MV_WINDOW_POVEY) w = pow(0.5 - 0.5 * cos(a * i), 0.85);       // hann ** 0.85
+        if (cfg->window_type == MV_WINDOW_HANNING) w = 0.5 - 0.5 * cos(a * i);
+        if (cfg->window_type == MV_WINDOW_HAMMING) w = 0.54 - 0.46 * cos(a * i);
+        if (cfg->window_type == MV_WINDOW_BLACKMAN) w = cfg->blackman_coeff - 0.5 * cos(a * i) + (0.5 - cfg->blackman_coeff) * cos(2.0 * a * i);
+        (*window)[i] = (float)w;
+        (*window_half)[i] = 0.5f * (*window)[i];  // exact: the halved spectrum squares to |X|^2 without a final scale
+    }
+}
+
+// tw256 [16 k1][16 n2][2]: the twiddle W256^(n2 * k1) between the two radix-16 stages; tw512 [256][2]: W512^k of the real-input post-processing
+void fft_twiddles(std::vector<float>* tw256, std::vector<float>* tw512) {
+    const double pi = 3.14159265358979323846;
+    tw256->resize(512);
+    tw512->resize(512);
+    for (int m = 0; m < 256; ++m) {
+        const int k1 = m >> 4, n2 = m & 15;
+        (*tw256)[2 * m] = (float)cos(2.0 * pi * ((n2 * k1) & 255) / 256.0);
+        (*tw256)[2 * m + 1] = (float)sin(2.0 * pi * ((n2 * k1) & 255) / 256.0);
+        (*tw512)[2 * m] = (float)cos(2.0 * pi * m / 512.0);
+        (*tw512)[2 * m + 1] = (float)sin(2.0 * pi * m / 512.0);
+    }
+}
+
+// kaldi_mel_banks on the 256 bins of the kernels' 512-point transform.  Windows that round up to an FFT of P < 512 points (8 kHz: 25 ms = 200
+// samples, P = 256): the kernels still transform the frame zero-padded to 512 points; bin k of the P-point transform of a zero-padded frame IS
+// bin k * 512 / P of the 512-point one, so kaldi's filter weights (built for P) are placed on those bins and the bins in between carry zero weight.
+bool banks_on_fft_grid(const MvFbank* h, std::vector<std::vector<float>>* banks) {
+    const MvFbankCfg& c = h->cfg;
+    std::vector<std::vector<float>> banks_p;
+    if (!kaldi_mel_banks(h->nbins, h->padded, c.sample_frequency, c.low_freq, c.high_freq, c.vtln_low, c.vtln_high, c.vtln_warp, &banks_p)) return false;
+    banks->assign(h->nbins, std::vector<float>(mv::FB_NFFT / 2, 0.0f));
+    const int stride = mv::FB_NFFT / h->padded;
+    for (int m = 0; m < h->nbins; ++m)
+        for (int k = 0; k < h->padded / 2; ++k) (*banks)[m][k * stride] = banks_p[m][k];
+    return true;
+}
+
+// fbank_kernel's workgroup: 15 waves (15 waves x 5 quads = the 75 quads of a 3 s utterance) when their frame slots fit the 160 KB of LDS next to
+// the tables, 12 or 8 when a long mel table leaves less; 0 when not even 8 fit.  *smem_bytes = the launch's dynamic LDS.
+int generic_waves(size_t melb_elems, size_t* smem_bytes) {
+    for (int waves : {15, 12, 8}) {
+        *smem_bytes = ((size_t)waves * 4 * mv::FB_SLOT_FLOATS + 3 * 512 + melb_elems) * sizeof(float);
+        if (*smem_bytes <= 160 * 1024) return waves;
+    }
+    return 0;
+}
+
+// The geometry fbank_tile_kernel is instantiated for: log power spectra, an even window and mel passes of 28 + 12 bins with one block per filter
+// group in the first.  Windows of 385 .. 416 samples -- 25 ms at 16 kHz is 400 -- run the 13-group rows, 20 / 24 / 30 ms their own, every other
+// even window the 16-group ones (tests/test_gpu_parity.py::test_gpu_fbank_arguments runs them against the oracle).
+bool fbank_tile_geometry_ok(const MvFbank* h) {
+    const mv::MelPlan& p = h->tab.plan;
+    return p.passes == 2 && p.pass_steps[0] == 4 * FBT_G0 && p.pass_steps[1] == 4 * FBT_G1 && p.pass_split[0] == 1 &&
+           (h->nbins & 3) == 0 && h->nbins <= 128 && h->win >= 4 && (h->win & 1) == 0 && h->cfg.use_power && h->cfg.use_log_fbank;
+}
+
+size_t fbank_tile_fixed_lds_bytes(int win) {
+    return ((size_t)mv::FBT_WAVES * mv::FBT_SLOT_FLOATS + mv::fbt_win_floats(tile_ng(win)) + 512) * sizeof(float);
+}
+
 }  // namespace
-
-template <int NG, bool V>
-hipError_t fbank_set_smem_v(size_t bytes) {
-    hipError_t e = MV_SET_MAX_SMEM((mv::fbank_kernel<NG, V, 8>), bytes);
-    if (e == hipSuccess) e = MV_SET_MAX_SMEM((mv::fbank_kernel<NG, V, 12>), bytes);
-    if (e == hipSuccess) e = MV_SET_MAX_SMEM((mv::fbank_kernel<NG, V, 15>), bytes);
-    return e;
-}
-
-hipError_t fbank_set_smem(size_t bytes) {
-    hipError_t e = fbank_set_smem_v<13, true>(bytes);
-    if (e == hipSuccess) e = fbank_set_smem_v<13, false>(bytes);
-    if (e == hipSuccess) e = fbank_set_smem_v<16, true>(bytes);
-    if (e == hipSuccess) e = fbank_set_smem_v<16, false>(bytes);
-    return e;
-}
-
-template <int NG, bool V>
-void fbank_launch_v(int B, size_t smem, hipStream_t st, const mv::FbankArgs& a, int waves) {
-    if (waves == 15) {
-        MV_LAUNCH((mv::fbank_kernel<NG, V, 15>), (B, 1, 1), (15 * 64, 1, 1), smem, st, a);
-    } else if (waves == 12) {
-        MV_LAUNCH((mv::fbank_kernel<NG, V, 12>), (B, 1, 1), (12 * 64, 1, 1), smem, st, a);
-    } else {
-        MV_LAUNCH((mv::fbank_kernel<NG, V, 8>), (B, 1, 1), (8 * 64, 1, 1), smem, st, a);
-    }
-}
-
-void fbank_launch(int B, size_t smem, hipStream_t st, const mv::FbankArgs& a, int waves, bool vec2) {
-    const bool ng13 = a.win > 12 * 32 && a.win <= 13 * 32;
-    if (ng13 && vec2) return fbank_launch_v<13, true>(B, smem, st, a, waves);
-    if (ng13) return fbank_launch_v<13, false>(B, smem, st, a, waves);
-    if (vec2) return fbank_launch_v<16, true>(B, smem, st, a, waves);
-    return fbank_launch_v<16, false>(B, smem, st, a, waves);
-}
-
-// fbank_tile_kernel is instantiated for the mel geometry of the reference configurations: 80 bins at 16 kHz on a 512-point
-// FFT = a pass of 16 filter groups (7 four-bin steps) and a pass of 4 groups, each split over 4 blocks (3 steps)
-constexpr int FBT_G0 = 7, FBT_G1 = 3;
-
-static bool fbank_tile_geometry_ok(const MvFbank* h) {
-    const mv::FbankTables& t = h->tab;
-    return t.passes == 2 && t.pass_steps[0] == 4 * FBT_G0 && t.pass_steps[1] == 4 * FBT_G1 && t.pass_split[0] == 1 &&
-           (h->nbins & 3) == 0 && h->nbins <= 128 && h->win >= 4 && (h->win & 1) == 0 && h->cfg.use_power && h->cfg.use_log_fbank;  // log power spectra only
-    // (windows of 385 .. 416 samples -- 25 ms at 16 kHz is 400 -- run the 13-group instantiation, every other even window the 16-group one, whose
-    // LDS window table holds all 512 taps since round 5: in rounds 2 - 4 it held 448, and groups 14 / 15 read the twiddle table behind it -- the
-    // wrong features of 20 / 24 ms windows.  tests/test_gpu_parity.py::test_gpu_fbank_arguments runs both instantiations against the oracle.)
-}
-
-// sample groups of the instantiation a window runs: its own count when that is instantiated (20 / 24 / 25 / 30 ms at 16 kHz), else 16
-static int fbank_tile_ng(int win) {
-    const int ng = (win + 31) / 32;
-    return (ng == 10 || ng == 12 || ng == 13 || ng == 15) ? ng : 16;
-}
-
-static size_t fbank_tile_fixed_lds_bytes(int win) {
-    return ((size_t)mv::FBT_WAVES * mv::FBT_SLOT_FLOATS + mv::fbt_win_floats(fbank_tile_ng(win)) + 512) * sizeof(float);
-}
-
-template <int NG, bool V>
-static hipError_t fbank_tile_set_smem() {
-    return MV_SET_MAX_SMEM((mv::fbank_tile_kernel<NG, V, FBT_G0, FBT_G1>), 160 * 1024);
-}
-
-template <int NG>
-static void fbank_tile_launch_ng(int B, size_t smem, hipStream_t st, const mv::FbankArgs& a, bool vec2) {
-    if (vec2) {
-        MV_LAUNCH((mv::fbank_tile_kernel<NG, true, FBT_G0, FBT_G1>), (B, 1, 1), (mv::FBT_WAVES * 64, 1, 1), smem, st, a);
-    } else {
-        MV_LAUNCH((mv::fbank_tile_kernel<NG, false, FBT_G0, FBT_G1>), (B, 1, 1), (mv::FBT_WAVES * 64, 1, 1), smem, st, a);
-    }
-}
-
-static void fbank_tile_launch(int B, size_t smem, hipStream_t st, const mv::FbankArgs& a, bool vec2) {
-    switch (fbank_tile_ng(a.win)) {
-        case 10: return fbank_tile_launch_ng<10>(B, smem, st, a, vec2);
-        case 12: return fbank_tile_launch_ng<12>(B, smem, st, a, vec2);
-        case 13: return fbank_tile_launch_ng<13>(B, smem, st, a, vec2);
-        case 15: return fbank_tile_launch_ng<15>(B, smem, st, a, vec2);
-        default: return fbank_tile_launch_ng<16>(B, smem, st, a, vec2);
-    }
-}
-
-template <int NG>
-static hipError_t fbank_tile_set_smem_ng() {
-    hipError_t e = fbank_tile_set_smem<NG, true>();
-    return e == hipSuccess ? fbank_tile_set_smem<NG, false>() : e;
-}
 
 extern "C" {
 
@@ -1063,128 +1126,55 @@ void mv_fbank_default_cfg(MvFbankCfg* cfg) {
     cfg->htk_compat = 0;
 }
 
+// checks, the host tables, their upload, then the kernel: fbank_tile_kernel where the geometry has an instantiation, else fbank_kernel
 int mv_fbank_create(const MvFbankCfg* cfg, MvFbank** out) {
     MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_fbank_create: null argument");
     const int win = (int)(cfg->sample_frequency * cfg->frame_length_ms * 0.001f);
     const int shift = (int)(cfg->sample_frequency * cfg->frame_shift_ms * 0.001f);
-    MV_REQUIRE(shift >= 1, "mv_fbank_create: frame shift must be at least one sample");
-    MV_REQUIRE(cfg->num_mel_bins >= 4 && cfg->num_mel_bins <= 64 * mv::FB_MAX_PASSES,
-               "mv_fbank_create: num_mel_bins must be in [4, 128] (torchaudio's get_mel_banks asserts num_bins > 3)");
-    {   // torchaudio.compliance.kaldi.get_mel_banks asserts on the band the same way ("Bad values in options: low-freq ... and high-freq ... vs. nyquist ...")
-        const float nyq = 0.5f * cfg->sample_frequency, hi = cfg->high_freq <= 0.0f ? cfg->high_freq + nyq : cfg->high_freq;
-        MV_REQUIRE(cfg->low_freq >= 0.0f && cfg->low_freq < nyq && hi > 0.0f && hi <= nyq && cfg->low_freq < hi,
-                   "mv_fbank_create: bad band (need 0 <= low_freq < nyquist, 0 < high_freq <= nyquist and low_freq < high_freq; high_freq <= 0 counts from nyquist)");
-    }
-    if (win < 2 || win > mv::FB_NFFT)
-        return mv::fail(MV_ERR_UNSUPPORTED,
-                        "mv_fbank_create: only frame lengths of 2 .. 512 samples (an FFT of up to 512 points, e.g. 25 ms at 16 kHz) are "
-                        "implemented on gfx950");
-    MV_REQUIRE(cfg->window_type >= MV_WINDOW_POVEY && cfg->window_type <= MV_WINDOW_BLACKMAN, "mv_fbank_create: unknown window_type");
-    MV_REQUIRE(cfg->kernel >= MV_FBANK_KERNEL_AUTO && cfg->kernel <= MV_FBANK_KERNEL_TILE, "mv_fbank_create: unknown kernel selector");
-    MV_REQUIRE(cfg->min_duration >= 0.0f, "mv_fbank_create: negative min_duration");
-    MV_REQUIRE(cfg->preemphasis_coefficient >= 0.0f && cfg->preemphasis_coefficient <= 1.0f,
-               "mv_fbank_create: preemphasis_coefficient must be in [0, 1] (torchaudio asserts the same)");
-    MV_REQUIRE(cfg->vtln_warp > 0.0f, "mv_fbank_create: vtln_warp must be positive");
-    MV_REQUIRE((cfg->use_energy == 0 || cfg->use_energy == 1) && (cfg->raw_energy == 0 || cfg->raw_energy == 1) && (cfg->htk_compat == 0 || cfg->htk_compat == 1) &&
-                   cfg->energy_floor >= 0.0f, "mv_fbank_create: use_energy / raw_energy / htk_compat are 0 or 1, energy_floor is not negative");
-    MvFbank* h = new MvFbank();
+    int rc = check_cfg(cfg, win, shift);
+    if (rc != MV_OK) return rc;
+    FbankPtr h(new MvFbank(), mv_fbank_destroy);
     h->cfg = *cfg;
     h->win = win;
     h->shift = shift;
     h->nbins = cfg->num_mel_bins;
     h->padded = 2;
     while (h->padded < win) h->padded *= 2;   // round_to_power_of_two=True (the only form implemented)
-    MV_REQUIRE(cfg->min_samples >= 0, "mv_fbank_create: negative min_samples");
     // len < min_duration * sf  <=>  len < ceil(...); the caller's own double evaluation (min_samples) wins over the float32 field
     h->min_samples = cfg->min_samples > 0 ? cfg->min_samples : (int64_t)ceil((double)cfg->min_duration * (double)cfg->sample_frequency);
 
-    const double pi = 3.14159265358979323846;
-    std::vector<float> window(512, 0.0f), window_half(512, 0.0f), tw256(512), tw512(512);
-    for (int i = 0; i < win; ++i) {
-        // torchaudio.compliance.kaldi._feature_window_function (all symmetric, periodic=False)
-        const double a = 2.0 * pi / (win - 1);
-        double w = 1.0;                                                                       // rectangular
-        if (cfg->window_type == MV_WINDOW_POVEY) w = pow(0.5 - 0.5 * cos(a * i), 0.85);       // hann ** 0.85
-        if (cfg->window_type == MV_WINDOW_HANNING) w = 0.5 - 0.5 * cos(a * i);
-        if (cfg->window_type == MV_WINDOW_HAMMING) w = 0.54 - 0.46 * cos(a * i);
-        if (cfg->window_type == MV_WINDOW_BLACKMAN) w = cfg->blackman_coeff - 0.5 * cos(a * i) + (0.5 - cfg->blackman_coeff) * cos(2.0 * a * i);
-        window[i] = (float)w;
-        window_half[i] = 0.5f * window[i];  // exact: the halved spectrum squares to |X|^2 without a final scale
-    }
-    for (int m = 0; m < 256; ++m) {
-        const int k1 = m >> 4, n2 = m & 15;  // stage-1 -> stage-2 twiddle W256^(n2*k1), laid out [k1][n2]
-        tw256[2 * m] = (float)cos(2.0 * pi * ((n2 * k1) & 255) / 256.0);
-        tw256[2 * m + 1] = (float)sin(2.0 * pi * ((n2 * k1) & 255) / 256.0);
-        tw512[2 * m] = (float)cos(2.0 * pi * m / 512.0);
-        tw512[2 * m + 1] = (float)sin(2.0 * pi * m / 512.0);
-    }
-    // Windows that round up to an FFT of P < 512 points (8 kHz: 25 ms = 200 samples, P = 256): the kernels still transform the frame zero-padded to
-    // 512 points; bin k of the P-point transform of a zero-padded frame IS bin k * 512 / P of the 512-point one, so kaldi's filter weights (built
-    // for P) are placed on those bins and the bins in between carry zero weight.
-    std::vector<std::vector<float>> banks_p;
-    if (!kaldi_mel_banks(h->nbins, h->padded, cfg->sample_frequency, cfg->low_freq, cfg->high_freq, cfg->vtln_low, cfg->vtln_high, cfg->vtln_warp, &banks_p)) {
-        delete h;
+    std::vector<float> window, window_half, tw256, tw512, melb;
+    std::vector<std::vector<float>> banks;
+    kaldi_window(cfg, win, &window, &window_half);
+    fft_twiddles(&tw256, &tw512);
+    if (!banks_on_fft_grid(h.get(), &banks))
         return mv::fail(MV_ERR_INVALID_ARGUMENT, "mv_fbank_create: bad VTLN options (need low_freq < vtln_low < vtln_high < high_freq, and the warped cut-offs inside the band)");
-    }
-    std::vector<std::vector<float>> banks(h->nbins, std::vector<float>(mv::FB_NFFT / 2, 0.0f));
-    {
-        const int stride = mv::FB_NFFT / h->padded;
-        for (int m = 0; m < h->nbins; ++m)
-            for (int k = 0; k < h->padded / 2; ++k) banks[m][k * stride] = banks_p[m][k];
-    }
     // Mel stage tables (frontend_common.h::build_mel_plan): passes of 16 blocks x (4 frames x 4 adjacent filters), every block
     // walking only the bins its triangles cover, inside the 256 bins of a power row
     mv::FbankTables& tab = h->tab;
-    mv::MelPlan plan;
-    std::vector<float> melb;
-    if (!mv::build_mel_plan(banks, 256, &plan, &melb)) {
-        delete h;
-        return mv::fail(MV_ERR_UNSUPPORTED, "mv_fbank_create: num_mel_bins needs more than two MFMA passes");
-    }
-    tab.passes = plan.passes;
-    for (int p = 0; p < mv::FB_MAX_PASSES; ++p) {
-        tab.pass_steps[p] = plan.pass_steps[p];
-        tab.pass_split[p] = plan.pass_split[p];
-        tab.pass_gbase[p] = plan.pass_gbase[p];
-        for (int blk = 0; blk < 16; ++blk) tab.pass_start[p][blk] = plan.pass_start[p][blk];
-    }
+    if (!mv::build_mel_plan(banks, 256, &tab.plan, &melb)) return mv::fail(MV_ERR_UNSUPPORTED, "mv_fbank_create: num_mel_bins needs more than two MFMA passes");
     tab.melb_elems = (int)melb.size();
-    int rc;
-    if ((rc = upload(window, &h->d_window)) || (rc = upload(window_half, &h->d_window_half)) || (rc = upload(tw256, &h->d_tw256)) ||
-        (rc = upload(tw512, &h->d_tw512)) ||
-        (rc = upload(melb, &h->d_melb))) {
-        mv_fbank_destroy(h);
+    if ((rc = mv::upload_vec(window, &h->d_window)) || (rc = mv::upload_vec(window_half, &h->d_window_half)) || (rc = mv::upload_vec(tw256, &h->d_tw256)) ||
+        (rc = mv::upload_vec(tw512, &h->d_tw512)) || (rc = mv::upload_vec(melb, &h->d_melb)))
         return rc;
-    }
     tab.window = h->d_window;
     tab.window_half = h->d_window_half;
     tab.tw256 = h->d_tw256;
     tab.tw512 = h->d_tw512;
     tab.melb = h->d_melb;
-    auto lds_need = [&](int waves) { return ((size_t)waves * 4 * mv::FB_SLOT_FLOATS + 3 * 512 + melb.size()) * sizeof(float); };
-    if (lds_need(h->waves) > 160 * 1024 && h->waves > 12) h->waves = 12;  // a long mel table leaves room for fewer frame slots
-    if (lds_need(h->waves) > 160 * 1024) h->waves = 8;
-    h->smem_bytes = lds_need(h->waves);
-    if (h->smem_bytes > 160 * 1024) {
-        mv_fbank_destroy(h);
-        return mv::fail(MV_ERR_UNSUPPORTED, "mv_fbank_create: the mel table does not fit the LDS next to the frame slots");
-    }
-    if (fbank_set_smem(h->smem_bytes) != hipSuccess) {
-        mv_fbank_destroy(h);
-        return mv::fail(MV_ERR_HIP, "mv_fbank_create: cannot reserve dynamic LDS for fbank_kernel");
-    }
-    h->tile_kernel = fbank_tile_geometry_ok(h) && cfg->kernel != MV_FBANK_KERNEL_GENERIC;
-    if (cfg->kernel == MV_FBANK_KERNEL_TILE && !h->tile_kernel) {
-        mv_fbank_destroy(h);
+
+    h->waves = generic_waves(melb.size(), &h->smem_bytes);
+    if (h->waves == 0) return mv::fail(MV_ERR_UNSUPPORTED, "mv_fbank_create: the mel table does not fit the LDS next to the frame slots");
+    if (reserve_lds(GENERIC_KERNELS, h->smem_bytes) != hipSuccess) return mv::fail(MV_ERR_HIP, "mv_fbank_create: cannot reserve dynamic LDS for fbank_kernel");
+    h->tile_kernel = fbank_tile_geometry_ok(h.get()) && cfg->kernel != MV_FBANK_KERNEL_GENERIC;
+    if (cfg->kernel == MV_FBANK_KERNEL_TILE && !h->tile_kernel)
         return mv::fail(MV_ERR_UNSUPPORTED, "mv_fbank_create: fbank_tile_kernel is instantiated for log power spectra on the mel geometry of 80 bins / 16 kHz / "
                                             "512-point FFT (mel passes of 28 + 12 bins) with an even window; this configuration runs fbank_kernel");
-    }
-    if (h->tile_kernel && (fbank_tile_set_smem_ng<10>() != hipSuccess || fbank_tile_set_smem_ng<12>() != hipSuccess || fbank_tile_set_smem_ng<13>() != hipSuccess ||
-                           fbank_tile_set_smem_ng<15>() != hipSuccess || fbank_tile_set_smem_ng<16>() != hipSuccess)) {
-        mv_fbank_destroy(h);
+    if (h->tile_kernel && reserve_lds(TILE_KERNELS, 160 * 1024) != hipSuccess)
         return mv::fail(MV_ERR_HIP, "mv_fbank_create: cannot reserve dynamic LDS for fbank_tile_kernel");
-    }
-    *out = h;
+    for (int vec2 = 0; vec2 < 2; ++vec2)
+        h->kernel[vec2] = h->tile_kernel ? find_kernel(TILE_KERNELS, tile_ng(win), vec2 != 0, mv::FBT_WAVES) : find_kernel(GENERIC_KERNELS, generic_ng(win), vec2 != 0, h->waves);
+    *out = h.release();
     return MV_OK;
 }
 
@@ -1204,7 +1194,7 @@ int mv_fbank_num_frames(const MvFbank* h, int64_t num_samples, int64_t* num_fram
     if (num_samples < h->min_samples) {
         *num_frames = 0;
     } else if (h->cfg.snip_edges) {
-        *num_frames = num_samples < h->win ? 0 : 1 + (num_samples - h->win) / h->shift;
+        *num_frames = mv::fbank_num_frames(num_samples, h->win, h->win, h->shift);
     } else {
         *num_frames = (num_samples + h->shift / 2) / h->shift;
     }
@@ -1214,40 +1204,34 @@ int mv_fbank_num_frames(const MvFbank* h, int64_t num_samples, int64_t* num_fram
 int mv_fbank_info(const MvFbank* h, int32_t* tile_kernel, int32_t* pass_steps) {
     MV_REQUIRE(h != nullptr && tile_kernel != nullptr && pass_steps != nullptr, "mv_fbank_info: null argument");
     *tile_kernel = h->tile_kernel ? 1 : 0;
-    pass_steps[0] = h->tab.pass_steps[0];
-    pass_steps[1] = h->tab.pass_steps[1];
+    pass_steps[0] = h->tab.plan.pass_steps[0];
+    pass_steps[1] = h->tab.plan.pass_steps[1];
     return MV_OK;
 }
 
-// Geometry of one forward.  `fit` = feature rows that fit next to the wave slots in LDS (a multiple of 4).  The several-workgroups form
-// (chunk_form) is a matter of time only -- both forms sum an utterance's time mean in one order (FbankArgs) -- and pays whenever there are
-// fewer utterances than CUs: chunks of a multiple of 8 quads so that (utterance, chunk) workgroups about fill the chip.
+}  // extern "C"
+
+namespace {
+
+// ---- forward: the plan of one call, checks, optional mirror pass, mel launch, optional energy pass
+
+// Geometry of one forward and the sections of its workspace, in order, each at a multiple of 256 bytes: the mirrored rows [B][mirror_stride]
+// with their lengths [B] (snip_edges = 0), the chunks' per-quad column sums (chunk_form), the mel kernels' [B, T, nbins] rows (use_energy).
+// `fit` = feature rows that fit next to the wave slots in LDS (a multiple of 4).  The several-workgroups form (chunk_form) is a matter of time
+// only -- both forms sum an utterance's time mean in one order (FbankArgs) -- and pays whenever there are fewer utterances than CUs: chunks of
+// a multiple of 8 quads so that (utterance, chunk) workgroups about fill the chip.
 struct FbankPlan {
     int64_t T = 0, fit = 0, need = 0;
     int nch = 1, chunk_quads = 0;
     bool chunk_form = false;   // B * nch workgroups + the finish pass; needs the caller's workspace
-    // snip_edges = 0: the mirrored rows [B][mirror_stride] and their lengths [B] come first in the workspace (mirror_bytes, a multiple of 256)
     int64_t mirror_len = 0, mirror_stride = 0;
-    size_t mirror_bytes = 0;
-    size_t chunk_bytes = 0;
-    // use_energy: the mel kernels' [B, T, nbins] rows come last (mel_off, a multiple of 256)
+    size_t mirror_bytes = 0;                 // at offset 0
+    size_t chunk_off = 0, chunk_bytes = 0;
     size_t mel_off = 0, mel_bytes = 0;
     size_t workspace_bytes = 0;
 };
 
-static FbankPlan fbank_plan_mel(const MvFbank* h, int32_t B, int64_t L);
-
-static FbankPlan fbank_plan(const MvFbank* h, int32_t B, int64_t L) {
-    FbankPlan p = fbank_plan_mel(h, B, L);
-    if (h->cfg.use_energy && B > 0 && p.T > 0) {
-        p.mel_off = (size_t)mv::round_up((int64_t)p.workspace_bytes, (int64_t)256);
-        p.mel_bytes = (size_t)B * (size_t)p.T * (size_t)h->nbins * sizeof(float);
-        p.workspace_bytes = p.mel_off + p.mel_bytes;
-    }
-    return p;
-}
-
-static FbankPlan fbank_plan_mel(const MvFbank* h, int32_t B, int64_t L) {
+FbankPlan fbank_plan(const MvFbank* h, int32_t B, int64_t L) {
     FbankPlan p;
     mv_fbank_num_frames(h, L, &p.T);
     if (B <= 0 || p.T <= 0) return p;
@@ -1255,33 +1239,152 @@ static FbankPlan fbank_plan_mel(const MvFbank* h, int32_t B, int64_t L) {
         p.mirror_len = (p.T - 1) * h->shift + h->win;
         p.mirror_stride = mv::round_up(p.mirror_len, (int64_t)4);
         p.mirror_bytes = (size_t)mv::round_up((int64_t)B * p.mirror_stride * (int64_t)sizeof(float) + (int64_t)B * (int64_t)sizeof(int64_t), (int64_t)256);
-        p.workspace_bytes = p.mirror_bytes;
     }
-    if (!h->tile_kernel) return p;
-    p.fit = (int64_t)((160 * 1024 - fbank_tile_fixed_lds_bytes(h->win)) / ((size_t)h->nbins * sizeof(float))) & ~(int64_t)3;
-    p.need = (p.T + 3) & ~(int64_t)3;
-    const int cus = mv::device_cu_count();
-    const int nquads = (int)(p.need / 4);
-    if (B < cus && nquads >= 2 * mv::FBT_WAVES) {
-        const int want = (int)mv::ceil_div(cus, B);                                    // chunks per utterance that fill the chip once
-        const int most = nquads / mv::FBT_WAVES;                                       // (every wave of a chunk gets a quad)
-        const int nch0 = want < most ? want : most;
-        p.chunk_quads = (int)mv::round_up(mv::ceil_div(nquads, nch0), mv::FBT_WAVES);
-        p.nch = (int)mv::ceil_div(nquads, p.chunk_quads);
-        p.chunk_form = p.nch > 1;
+    p.chunk_off = p.mirror_bytes;
+    if (h->tile_kernel) {
+        p.fit = (int64_t)((160 * 1024 - fbank_tile_fixed_lds_bytes(h->win)) / ((size_t)h->nbins * sizeof(float))) & ~(int64_t)3;
+        p.need = (p.T + 3) & ~(int64_t)3;
+        const int cus = mv::device_cu_count();
+        const int nquads = (int)(p.need / 4);
+        if (B < cus && nquads >= 2 * mv::FBT_WAVES) {
+            const int want = (int)mv::ceil_div(cus, B);                                    // chunks per utterance that fill the chip once
+            const int most = nquads / mv::FBT_WAVES;                                       // (every wave of a chunk gets a quad)
+            const int nch0 = want < most ? want : most;
+            p.chunk_quads = (int)mv::round_up(mv::ceil_div(nquads, nch0), mv::FBT_WAVES);
+            p.nch = (int)mv::ceil_div(nquads, p.chunk_quads);
+            p.chunk_form = p.nch > 1;
+        }
+        if (p.chunk_form) p.chunk_bytes = (size_t)B * p.nch * p.chunk_quads * 128 * sizeof(float);
     }
-    if (p.chunk_form) p.chunk_bytes = (size_t)B * p.nch * p.chunk_quads * 128 * sizeof(float);
-    p.workspace_bytes += p.chunk_bytes;
+    p.workspace_bytes = p.chunk_off + p.chunk_bytes;
+    if (h->cfg.use_energy) {
+        p.mel_off = (size_t)mv::round_up((int64_t)p.workspace_bytes, (int64_t)256);
+        p.mel_bytes = (size_t)B * (size_t)p.T * (size_t)h->nbins * sizeof(float);
+        p.workspace_bytes = p.mel_off + p.mel_bytes;
+    }
     return p;
 }
 
-static int fbank_forward_impl(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
-                              const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream);
-
-int mv_fbank_forward(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
-                     const float* lens_ratio, float* out, mv_stream_t stream) {
-    return fbank_forward_impl(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, nullptr, 0, stream);
+// the caller's workspace is there, 16-byte aligned and holds the sections up to `bytes`
+bool workspace_holds(const void* workspace, size_t workspace_bytes, size_t bytes) {
+    return workspace != nullptr && workspace_bytes >= bytes && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
 }
+
+// the arguments of the mel kernels for the one-workgroup form on the caller's rows; the mirror pass and the chunk form change theirs
+mv::FbankArgs fbank_args(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, const int64_t* num_samples,
+                         float* out, int64_t T) {
+    mv::FbankArgs a;
+    a.wav = wav; a.wav_stride = wav_stride; a.L = L; a.lens_ratio = lens_ratio; a.num_samples = num_samples; a.out = out;
+    a.B = B; a.T = (int)T; a.win = h->win; a.shift = h->shift; a.nbins = h->nbins;
+    a.preemph = h->cfg.preemphasis_coefficient; a.inv_win = 1.0f / (float)h->win;
+    a.remove_dc = h->cfg.remove_dc_offset; a.use_power = h->cfg.use_power; a.use_log = h->cfg.use_log_fbank;
+    // kaldi.fbank's own subtract_mean (column means over the utterance's frames) followed by the wrapper's time mean over the same frames
+    // subtracts (a rounding of) zero the second time: one subtraction serves both
+    a.cmn = h->cfg.subtract_time_mean || h->cfg.subtract_mean;
+    a.min_len = h->min_samples > h->win ? h->min_samples : h->win;
+    a.tile_rows = 0; a.chunked = 0; a.nchunks = 1; a.chunk_quads = 0; a.part = nullptr;
+    a.tab = h->tab;
+    return a;
+}
+
+// snip_edges = False: fbank_mirror_kernel writes the mirrored rows (and, for the variable-length form, their lengths) to the first workspace
+// section; *a then describes those rows, whose frames are plain snip-edges frames
+int mirror_pass(const MvFbank* h, const FbankPlan& plan, int32_t B, int64_t L, void* workspace, size_t workspace_bytes, hipStream_t st, mv::FbankArgs* a) {
+    if (!workspace_holds(workspace, workspace_bytes, plan.mirror_bytes))
+        return mv::fail(MV_ERR_WORKSPACE, "mv_fbank_forward: snip_edges=False writes the mirrored signal to the caller workspace "
+                                        "(mv_fbank_workspace_bytes, 16-byte aligned; mv_fbank_forward_ws / mv_fbank_forward_varlen_ws)");
+    if (a->num_samples == nullptr) {   // (torchaudio concatenates the reversed signal once to either side: shorter signals make it raise)
+        const int64_t pad = h->win / 2 - h->shift / 2;
+        if (pad > L || (plan.T - 1) * h->shift - pad + h->win > 2 * L)
+            return mv::fail(MV_ERR_INVALID_ARGUMENT, "mv_fbank_forward: snip_edges=False: the signal is too short to be mirrored over its frames");
+    }
+    float* mw = static_cast<float*>(workspace);
+    int64_t* mlens = a->num_samples != nullptr ? reinterpret_cast<int64_t*>(mw + (int64_t)B * plan.mirror_stride) : nullptr;
+    MV_REQUIRE(B <= 65535, "mv_fbank_forward: snip_edges=False takes at most 65535 rows per call");
+    MV_LAUNCH(mv::fbank_mirror_kernel, ((unsigned)mv::ceil_div(plan.mirror_stride, (int64_t)1024), (unsigned)B, 1), (256, 1, 1), 0, st, a->wav, a->wav_stride,
+              a->num_samples, L, mw, plan.mirror_stride, plan.mirror_len, mlens, h->win, h->shift, h->min_samples);
+    a->wav = mw;
+    a->wav_stride = plan.mirror_stride;
+    a->L = plan.mirror_len;
+    a->min_len = h->win;
+    a->num_samples = mlens;
+    return MV_OK;
+}
+
+// use_energy: the mel kernels have written their rows `a.out` to the workspace; fbank_energy_kernel composes the caller's [B, T, nbins + 1] output
+void energy_pass(const MvFbank* h, const mv::FbankArgs& a, float* out, hipStream_t st) {
+    mv::FbankEnergyArgs e;
+    e.wav = a.wav; e.wav_stride = a.wav_stride; e.lens_ratio = a.lens_ratio; e.num_samples = a.num_samples; e.mel = a.out; e.out = out;
+    e.window = h->tab.window; e.T = a.T; e.win = h->win; e.shift = h->shift; e.nbins = h->nbins; e.min_len = a.min_len;
+    e.preemph = a.preemph; e.inv_win = a.inv_win; e.remove_dc = a.remove_dc; e.raw_energy = h->cfg.raw_energy; e.cmn = a.cmn;
+    e.energy_col = h->cfg.htk_compat ? h->nbins : 0;
+    e.mel_col = h->cfg.htk_compat ? 0 : 1;
+    e.has_floor = h->cfg.energy_floor != 0.0f;
+    e.log_floor = e.has_floor ? (float)log((double)h->cfg.energy_floor) : 0.0f;
+    MV_LAUNCH(mv::fbank_energy_kernel, ((unsigned)a.B, 1, 1), (256, 1, 1), 0, st, e);
+}
+
+// The forward behind the four entry points: lens_ratio (batch form, or neither) or num_samples (variable-length form).  Checks; the optional
+// mirror pass; the mel launch -- fbank_tile_kernel in chunks + the finish pass, fbank_tile_kernel on one workgroup per utterance, or
+// fbank_kernel --; the optional energy pass.
+int fbank_forward(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, const int64_t* num_samples,
+                  float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
+    MV_REQUIRE(h != nullptr, "mv_fbank_forward: null handle");
+    MV_REQUIRE(B >= 0 && L >= 0 && wav_stride >= L, "mv_fbank_forward: bad batch geometry");
+    const FbankPlan plan = fbank_plan(h, B, L);
+    const int64_t T = plan.T;
+    if (B == 0 || T == 0) return MV_OK;  // empty output, like kaldi.fbank on a too-short input
+    MV_REQUIRE(wav != nullptr && out != nullptr, "mv_fbank_forward: null buffer");
+    MV_REQUIRE(T * (h->nbins + 1) < (int64_t)1 << 31, "mv_fbank_forward: utterance too long for 32-bit row indexing");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float* mel_out = out;
+    if (h->cfg.use_energy) {   // the mel kernels write to the workspace, fbank_energy_kernel composes the [B, T, nbins + 1] output
+        if (!workspace_holds(workspace, workspace_bytes, plan.workspace_bytes))
+            return mv::fail(MV_ERR_WORKSPACE, "mv_fbank_forward: use_energy writes the mel columns to the caller workspace first "
+                                            "(mv_fbank_workspace_bytes, 16-byte aligned; mv_fbank_forward_ws / mv_fbank_forward_varlen_ws)");
+        mel_out = reinterpret_cast<float*>(static_cast<char*>(workspace) + plan.mel_off);
+    }
+    mv::FbankArgs a = fbank_args(h, wav, B, L, wav_stride, lens_ratio, num_samples, mel_out, T);
+    int rc;
+    if (!h->cfg.snip_edges && (rc = mirror_pass(h, plan, B, L, workspace, workspace_bytes, st, &a)) != MV_OK) return rc;
+    const bool vec2 = (reinterpret_cast<uintptr_t>(a.wav) & 7) == 0 && (a.wav_stride & 1) == 0 && (h->shift & 1) == 0 && (h->win & 1) == 0;
+    const FbankKernelRow& k = *h->kernel[vec2];
+    const int prof = mv::prof_begin(MV_PROF_FBANK, (double)B * (4.0 * (double)L + 4.0 * (double)T * h->nbins), st);
+    if (!h->tile_kernel) {
+        MV_LAUNCH(k.fn, (B, 1, 1), (k.waves * 64, 1, 1), h->smem_bytes, st, a);
+    } else if (plan.chunk_form && num_samples == nullptr && workspace_holds(workspace, workspace_bytes, plan.chunk_off + plan.chunk_bytes)) {
+        // The chunk form and the one-workgroup form give the same bits (FbankArgs), so taking it is a matter of time only.  It needs scratch for
+        // the chunks' per-wave sums, which belongs to the CALL, not to the handle: without the caller's workspace (mv_fbank_forward, the
+        // variable-length entry point) every utterance runs on one workgroup.
+        a.chunked = 1;
+        a.nchunks = plan.nch;
+        a.chunk_quads = plan.chunk_quads;
+        a.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + plan.chunk_off);
+        MV_LAUNCH(k.fn, (B * plan.nch, 1, 1), (k.waves * 64, 1, 1), fbank_tile_fixed_lds_bytes(h->win), st, a);
+        if (a.cmn || lens_ratio != nullptr) {
+            const int row_blocks = (int)mv::ceil_div(T, mv::FBF_ROWS);
+            MV_LAUNCH(mv::fbank_cmn_finish_kernel, (B * row_blocks, 1, 1), (256, 1, 1), 0, st, mel_out, a.part, lens_ratio, (int)T, h->nbins,
+                      plan.nch * plan.chunk_quads, row_blocks, a.cmn);
+        }
+    } else {
+        // the first `fit` feature rows stay in LDS next to the wave slots until the time mean is known (292 of the 298 frames of a 3 s
+        // utterance at 80 bins); the rest take the write / re-read / rewrite route through global memory
+        a.tile_rows = (int)(plan.fit < plan.need ? plan.fit : plan.need);
+        MV_LAUNCH(k.fn, (B, 1, 1), (k.waves * 64, 1, 1), fbank_tile_fixed_lds_bytes(h->win) + (size_t)a.tile_rows * h->nbins * sizeof(float), st, a);
+    }
+    const char* launched = h->tile_kernel ? "fbank_tile_kernel" : "fbank_kernel";
+    if (h->cfg.use_energy) {
+        if ((rc = mv::check_launch(launched)) != MV_OK) return rc;
+        energy_pass(h, a, out, st);
+        launched = "fbank_energy_kernel";
+    }
+    mv::prof_end(prof, st);
+    return mv::check_launch(launched);
+}
+
+}  // namespace
+
+extern "C" {
 
 int mv_fbank_workspace_bytes(const MvFbank* h, int32_t B, int64_t L, size_t* bytes) {
     MV_REQUIRE(h != nullptr && bytes != nullptr, "mv_fbank_workspace_bytes: null argument");
@@ -1289,152 +1392,26 @@ int mv_fbank_workspace_bytes(const MvFbank* h, int32_t B, int64_t L, size_t* byt
     return MV_OK;
 }
 
+int mv_fbank_forward(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
+                     const float* lens_ratio, float* out, mv_stream_t stream) {
+    return fbank_forward(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, nullptr, 0, stream);
+}
+
 int mv_fbank_forward_ws(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
                         float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
-    return fbank_forward_impl(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, workspace, workspace_bytes, stream);
+    return fbank_forward(h, wav, B, L, wav_stride, lens_ratio, nullptr, out, workspace, workspace_bytes, stream);
 }
 
 int mv_fbank_forward_varlen(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride,
                             const int64_t* num_samples, float* out, mv_stream_t stream) {
     MV_REQUIRE(num_samples != nullptr, "mv_fbank_forward_varlen: null length array");
-    return fbank_forward_impl(h, wav, B, L, wav_stride, nullptr, num_samples, out, nullptr, 0, stream);
+    return fbank_forward(h, wav, B, L, wav_stride, nullptr, num_samples, out, nullptr, 0, stream);
 }
 
 int mv_fbank_forward_varlen_ws(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples,
                                float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
     MV_REQUIRE(num_samples != nullptr, "mv_fbank_forward_varlen_ws: null length array");
-    return fbank_forward_impl(h, wav, B, L, wav_stride, nullptr, num_samples, out, workspace, workspace_bytes, stream);
-}
-
-static int fbank_forward_impl(const MvFbank* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
-                              const int64_t* num_samples, float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream) {
-    MV_REQUIRE(h != nullptr, "mv_fbank_forward: null handle");
-    MV_REQUIRE(B >= 0 && L >= 0 && wav_stride >= L, "mv_fbank_forward: bad batch geometry");
-    const FbankPlan plan = fbank_plan(h, B, L);
-    int64_t T = 0;
-    mv_fbank_num_frames(h, L, &T);
-    if (B == 0 || T == 0) return MV_OK;  // empty output, like kaldi.fbank on a too-short input
-    MV_REQUIRE(wav != nullptr && out != nullptr, "mv_fbank_forward: null buffer");
-    MV_REQUIRE(T * (h->nbins + 1) < (int64_t)1 << 31, "mv_fbank_forward: utterance too long for 32-bit row indexing");
-    float* const final_out = out;
-    if (h->cfg.use_energy) {   // the mel kernels write to the workspace, fbank_energy_kernel composes the [B, T, nbins + 1] output
-        if (workspace == nullptr || workspace_bytes < plan.workspace_bytes || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-            return mv::fail(MV_ERR_WORKSPACE, "mv_fbank_forward: use_energy writes the mel columns to the caller workspace first "
-                                            "(mv_fbank_workspace_bytes, 16-byte aligned; mv_fbank_forward_ws / mv_fbank_forward_varlen_ws)");
-        out = reinterpret_cast<float*>(static_cast<char*>(workspace) + plan.mel_off);
-        workspace_bytes = plan.mel_off;   // what the other sections may use
-    }
-    mv::FbankArgs a;
-    a.wav = wav;
-    a.wav_stride = wav_stride;
-    a.lens_ratio = lens_ratio;
-    a.num_samples = num_samples;
-    a.out = out;
-    a.B = B;
-    a.T = (int)T;
-    a.win = h->win;
-    a.shift = h->shift;
-    a.nbins = h->nbins;
-    a.preemph = h->cfg.preemphasis_coefficient;
-    a.inv_win = 1.0f / (float)h->win;
-    a.remove_dc = h->cfg.remove_dc_offset;
-    a.use_power = h->cfg.use_power;
-    a.use_log = h->cfg.use_log_fbank;
-    // kaldi.fbank's own subtract_mean (column means over the utterance's frames) followed by the wrapper's time mean over the same frames
-    // subtracts (a rounding of) zero the second time: one subtraction serves both
-    a.cmn = h->cfg.subtract_time_mean || h->cfg.subtract_mean;
-    a.L = L;
-    a.min_len = h->min_samples > h->win ? h->min_samples : h->win;
-    a.tile_rows = 0;
-    a.chunked = 0;
-    a.nchunks = 1;
-    a.chunk_quads = 0;
-    a.part = nullptr;
-    a.tab = h->tab;
-    void* chunk_ws = workspace;
-    size_t chunk_ws_bytes = workspace_bytes;
-    if (!h->cfg.snip_edges) {
-        if (workspace == nullptr || workspace_bytes < plan.mirror_bytes || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0)
-            return mv::fail(MV_ERR_WORKSPACE, "mv_fbank_forward: snip_edges=False writes the mirrored signal to the caller workspace "
-                                            "(mv_fbank_workspace_bytes, 16-byte aligned; mv_fbank_forward_ws / mv_fbank_forward_varlen_ws)");
-        if (num_samples == nullptr) {   // (torchaudio concatenates the reversed signal once to either side: shorter signals make it raise)
-            const int64_t pad = h->win / 2 - h->shift / 2;
-            if (pad > L || (T - 1) * h->shift - pad + h->win > 2 * L)
-                return mv::fail(MV_ERR_INVALID_ARGUMENT, "mv_fbank_forward: snip_edges=False: the signal is too short to be mirrored over its frames");
-        }
-        float* mw = static_cast<float*>(workspace);
-        int64_t* mlens = reinterpret_cast<int64_t*>(mw + (int64_t)B * plan.mirror_stride);
-        const int64_t xb = mv::ceil_div(plan.mirror_stride, (int64_t)1024);
-        MV_REQUIRE(B <= 65535, "mv_fbank_forward: snip_edges=False takes at most 65535 rows per call");
-        MV_LAUNCH(mv::fbank_mirror_kernel, ((unsigned)xb, (unsigned)B, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), wav, wav_stride, num_samples, L, mw,
-                  plan.mirror_stride, plan.mirror_len, num_samples != nullptr ? mlens : nullptr, h->win, h->shift, h->min_samples);
-        a.wav = wav = mw;
-        a.wav_stride = wav_stride = plan.mirror_stride;
-        a.L = plan.mirror_len;
-        a.min_len = h->win;
-        if (num_samples != nullptr) a.num_samples = num_samples = mlens;
-        chunk_ws = static_cast<char*>(workspace) + plan.mirror_bytes;
-        chunk_ws_bytes = workspace_bytes - plan.mirror_bytes;
-    }
-    const bool vec2 = (reinterpret_cast<uintptr_t>(wav) & 7) == 0 && (wav_stride & 1) == 0 && (h->shift & 1) == 0 && (h->win & 1) == 0;
-    const int prof = mv::prof_begin(MV_PROF_FBANK, (double)B * (4.0 * (double)L + 4.0 * (double)T * h->nbins), static_cast<hipStream_t>(stream));
-    if (h->tile_kernel) {
-        const size_t fixed = fbank_tile_fixed_lds_bytes(h->win);
-        // The chunk form and the one-workgroup form give the same bits (FbankArgs), so taking it is a matter of time only.  It needs scratch for
-        // the chunks' per-wave sums, which belongs to the CALL, not to the handle: without the caller's workspace (mv_fbank_forward, the
-        // variable-length entry point) every utterance runs on one workgroup.
-        if (plan.chunk_form && num_samples == nullptr && chunk_ws != nullptr && chunk_ws_bytes >= plan.chunk_bytes &&
-            (reinterpret_cast<uintptr_t>(chunk_ws) & 15) == 0) {
-            a.chunked = 1;
-            a.nchunks = plan.nch;
-            a.chunk_quads = plan.chunk_quads;
-            a.part = static_cast<float*>(chunk_ws);
-            fbank_tile_launch(B * plan.nch, fixed, static_cast<hipStream_t>(stream), a, vec2);
-            if (a.cmn || lens_ratio != nullptr) {
-                const int row_blocks = (int)mv::ceil_div(T, mv::FBF_ROWS);
-                MV_LAUNCH(mv::fbank_cmn_finish_kernel, (B * row_blocks, 1, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), out, a.part, lens_ratio,
-                          (int)T, h->nbins, plan.nch * plan.chunk_quads, row_blocks, a.cmn);
-            }
-        } else {
-            // the first `fit` feature rows stay in LDS next to the wave slots until the time mean is known (292 of the 298 frames of a 3 s
-            // utterance at 80 bins); the rest take the write / re-read / rewrite route through global memory
-            a.tile_rows = (int)(plan.fit < plan.need ? plan.fit : plan.need);
-            fbank_tile_launch(B, fixed + (size_t)a.tile_rows * h->nbins * sizeof(float), static_cast<hipStream_t>(stream), a, vec2);
-        }
-    } else {
-        fbank_launch(B, h->smem_bytes, static_cast<hipStream_t>(stream), a, h->waves, vec2);
-    }
-    if (h->cfg.use_energy) {
-        int rc = mv::check_launch(h->tile_kernel ? "fbank_tile_kernel" : "fbank_kernel");
-        if (rc != MV_OK) return rc;
-        mv::FbankEnergyArgs e;
-        e.wav = a.wav;
-        e.wav_stride = a.wav_stride;
-        e.lens_ratio = lens_ratio;
-        e.num_samples = a.num_samples;
-        e.mel = out;
-        e.out = final_out;
-        e.window = h->tab.window;
-        e.T = (int)T;
-        e.win = h->win;
-        e.shift = h->shift;
-        e.nbins = h->nbins;
-        e.preemph = a.preemph;
-        e.inv_win = a.inv_win;
-        e.remove_dc = a.remove_dc;
-        e.raw_energy = h->cfg.raw_energy;
-        e.cmn = a.cmn;
-        e.energy_col = h->cfg.htk_compat ? h->nbins : 0;
-        e.mel_col = h->cfg.htk_compat ? 0 : 1;
-        e.has_floor = h->cfg.energy_floor != 0.0f;
-        e.log_floor = e.has_floor ? (float)log((double)h->cfg.energy_floor) : 0.0f;
-        e.min_len = a.min_len;
-        MV_LAUNCH(mv::fbank_energy_kernel, ((unsigned)B, 1, 1), (256, 1, 1), 0, static_cast<hipStream_t>(stream), e);
-        mv::prof_end(prof, static_cast<hipStream_t>(stream));
-        return mv::check_launch("fbank_energy_kernel");
-    }
-    mv::prof_end(prof, static_cast<hipStream_t>(stream));
-    return mv::check_launch(h->tile_kernel ? "fbank_tile_kernel" : "fbank_kernel");
+    return fbank_forward(h, wav, B, L, wav_stride, nullptr, num_samples, out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

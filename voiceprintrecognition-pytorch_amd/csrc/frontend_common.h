@@ -1,5 +1,5 @@
 // Shared pieces of the two front-end kernels (fbank.hip, melspec.hip): complex helpers on float2 vectors, the in-register
-// 16-point FFT, the matrix-pipe mel stage primitives and the host-side planner of the banded mel walk.
+// 16-point FFT, the matrix-pipe mel stage primitives, the frame rules, the host-side planner of the banded mel walk and the table upload.
 #pragma once
 #include "common.h"
 
@@ -128,6 +128,12 @@ __host__ __device__ inline int64_t stft_num_frames(int64_t n, int cfg_pad, int c
     return lp < n_fft ? 0 : 1 + (lp - n_fft) / hop;
 }
 
+// The frame rule of the Kaldi front-end under snip_edges, host and device: a row of n samples has no frames below min_len (the window, or
+// min_duration when that is longer), else one per shift that leaves a whole window.
+__host__ __device__ inline int64_t fbank_num_frames(int64_t n, int64_t min_len, int win, int shift) {
+    return n < min_len ? 0 : 1 + (n - win) / shift;
+}
+
 __device__ __forceinline__ int64_t row_samples(const RowLens& v, int b) {
     const int64_t n = v.num_samples[b];
     return n < 0 ? 0 : (n > v.L ? v.L : n);
@@ -237,6 +243,14 @@ inline bool build_mel_plan(const std::vector<std::vector<float>>& banks, int row
         }
     }
     return true;
+}
+
+// a host table to a device buffer of its own, which the handle's destroy call frees
+template <typename T>
+int upload_vec(const std::vector<T>& v, T** dptr) {
+    MV_HIP_OK(hipMalloc(reinterpret_cast<void**>(dptr), v.size() * sizeof(T)));
+    MV_HIP_OK(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return MV_OK;
 }
 
 }  // namespace mv

@@ -634,12 +634,7 @@ constexpr int MST_G0 = 3, MST_G1 = 5;
 
 namespace {
 
-template <typename T>
-int upload_vec(const std::vector<T>& v, T** dptr) {
-    MV_HIP_OK(hipMalloc(reinterpret_cast<void**>(dptr), v.size() * sizeof(T)));
-    MV_HIP_OK(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MV_OK;
-}
+using mv::upload_vec;
 
 constexpr double PI = 3.14159265358979323846;
 

@@ -419,16 +419,10 @@ class Fbank(_FrontEnd):
         need = ctypes.c_size_t()
         check(self._cdll.mv_fbank_workspace_bytes(self._h, B, L, ctypes.byref(need)), self._cdll)
         ws = torch.empty(need.value, dtype=torch.uint8, device=wav.device) if need.value and (workspace or self._needs_ws) else None
-        if num_samples is not None:
-            if ws is None:
-                check(self._cdll.mv_fbank_forward_varlen(self._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
-                                                         current_stream(wav)), self._cdll)
-            else:
-                check(self._cdll.mv_fbank_forward_varlen_ws(self._h, wav.data_ptr(), B, L, wav.stride(0), num_samples.data_ptr(), out.data_ptr(),
-                                                            _ptr(ws), need.value, current_stream(wav)), self._cdll)
-            return out
-        check(self._cdll.mv_fbank_forward_ws(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(), _ptr(ws),
-                                             need.value if ws is not None else 0, current_stream(wav)), self._cdll)
+        # the _ws entry points with a null workspace are the plain ones
+        form, lens = ('forward_ws', lens_ratio) if num_samples is None else ('forward_varlen_ws', num_samples)
+        check(self._fn(form)(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens), out.data_ptr(), _ptr(ws),
+                             need.value if ws is not None else 0, current_stream(wav)), self._cdll)
         return out
 
 
