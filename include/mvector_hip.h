@@ -452,6 +452,27 @@ typedef struct MvEres2Cfg {
 } MvEres2Cfg;
 int mv_eres2net_create(const MvEres2Cfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
 
+/* ResNetSE.forward (mvector/models/resnet_se.py:65-145): conv3x3 stem, four stages of SE bottleneck blocks (1x1 -> 3x3 (stride) -> 1x1 -> squeeze /
+ * excitation gate -> + residual -> ReLU) on S16 maps, x.reshape(B, -1, T') -> the pooling head `pooling_type` (MV_POOL_*, prefix `pooling.`) ->
+ * bn2 -> linear -> bn3 folded into one exact-fp32 layer.  Entry point added under ABI 5.
+ * Refused with a message: input_size not a multiple of 8; a num_filters entry that is not a multiple of 16 or is above 512; a stage without
+ * blocks; a reduction that leaves no hidden unit; a pooling_type outside MV_POOL_ASP .. MV_POOL_TSP; a missing tensor.  The forward needs at least 9
+ * frames (two time steps behind three stride-2 stages).
+ * The network's ReLU has no upper bound and S16 maps saturate at |value| = 1023.5: every launch that stores a map reports the largest value it
+ * wanted to store to one device word of the handle, read through mv_model_info (MV_INFO_RESNETSE_*; never on the forward path).
+ * MV_RESNETSE_NO_PEAK or-ed into pooling_type builds the handle WITHOUT that word (the conv launches then run the instantiation without the
+ * tracking code; the two keys report -1): for tools that measure what the tracking costs, not for serving. */
+#define MV_RESNETSE_NO_PEAK 0x100
+typedef struct MvResNetSeCfg {
+    int32_t input_size;     /* F (80); must be a multiple of 8 */
+    int32_t layers[4];      /* {3,4,6,3} */
+    int32_t num_filters[4]; /* {32,64,128,256}: multiples of 16, at most 512 */
+    int32_t embd_dim;       /* 192 */
+    int32_t pooling_type;   /* MV_POOL_* */
+    int32_t reduction;      /* 8 */
+} MvResNetSeCfg;
+int mv_resnetse_create(const MvResNetSeCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
+
 int mv_model_destroy(MvModel* m);
 int mv_model_embd_dim(const MvModel* m, int32_t* embd_dim);
 /* Model-specific facts (tests, logs).  Keys:
@@ -491,6 +512,11 @@ int mv_model_embd_dim(const MvModel* m, int32_t* embd_dim);
 #define MV_INFO_ECAPA_GROUPED_EXPANDED 21
 #define MV_INFO_ECAPA_EXPANDED_1X1 22
 #define MV_INFO_ECAPA_BLOCKS 23
+/* ResNetSE handles (mv_resnetse_create): the range of their S16 maps on the caller's inputs since create (both WAIT FOR THE DEVICE: diagnostics)
+ *   MV_INFO_RESNETSE_PEAK        largest |map value| a launch wanted to store (real units; -1 on a MV_RESNETSE_NO_PEAK handle)
+ *   MV_INFO_RESNETSE_SATURATED   1.0 when it exceeded 1023.5 and was clamped (the embeddings of that call are not to be trusted) */
+#define MV_INFO_RESNETSE_PEAK 30
+#define MV_INFO_RESNETSE_SATURATED 31
 int mv_model_info(const MvModel* m, int32_t key, float* value);
 int mv_model_workspace_bytes(const MvModel* m, int32_t B, int32_t T, size_t* bytes);
 /* feats: [B, T, F] fp32 (the AudioFeaturizer output layout); emb: [B, embd_dim] fp32. */
@@ -590,6 +616,29 @@ int mv_conv2ds_forward(const MvConv2dsDesc* d, mv_stream_t stream);
 int mv_conv2d_first_s16(const float* feats, void* out, const float* w, const float* bias, int32_t B, int32_t T, int32_t F,
                         int32_t C, mv_stream_t stream);
 int mv_tstp_s16(const void* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t C, float* stats, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The SE layer of ResNetSE on S16 maps [B, H, W, ld] with C real channels (csrc/se2d.hip; resnet_se.py:47-62, 36-42), and the hand-over of a map
+ * to the pooling heads.  Added under ABI 5.  Every entry point refuses null pointers, non-positive sizes, ld < C and ld % 16 != 0 with a message.
+ *   mv_se2d_squeeze_s16        s[b, c] = mean over the H * W pixels, fp32 [B, C].  Partial sums over MV_SE2D_SQUEEZE_CHUNK consecutive pixels
+ *                              (in fp64) into the caller's workspace of mv_se2d_squeeze_workspace_floats(B, H, W, C) floats (8-byte aligned), then
+ *                              a finish pass in chunk order: no atomics, the bits of a row do not depend on B.
+ *   mv_se2d_excite_f32         g = sigmoid(W2 . relu(W1 . s + b1) + b2): s [B, C], w1 [R, C], b1 [R], w2 [C, R], b2 [C], g [B, C] fp32
+ *                              (products summed in fp64 in one fixed order); C <= 1024, 1 <= R <= 1024.
+ *   mv_se2d_gate_res_relu_s16  y = relu(x * g[b, c] + res), x / res / y S16 with their own leading dimensions (y may be x or res); channels C ..
+ *                              of a padded unit stay exact zeros; peak (optional device word) as MvConv2dsDesc.peak.
+ *   mv_s16_map_to_rows_f16     fp16 y[b, w, c * H + h] = x[b, h, w, c] (x.reshape(B, -1, W), channel-last), row pitch ldy >= C * H, a multiple
+ *                              of 8; columns C * H .. ldy - 1 zero.  H <= 256.
+ * ------------------------------------------------------------------------------------------------ */
+#define MV_SE2D_SQUEEZE_CHUNK 256
+size_t mv_se2d_squeeze_workspace_floats(int32_t B, int32_t H, int32_t W, int32_t C);
+int mv_se2d_squeeze_s16(const void* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t C, float* s, float* workspace, size_t workspace_floats,
+                        mv_stream_t stream);
+int mv_se2d_excite_f32(const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* g, int32_t B, int32_t C, int32_t R,
+                       mv_stream_t stream);
+int mv_se2d_gate_res_relu_s16(const void* x, int64_t ldx, const float* g, const void* res, int64_t ldres, void* y, int64_t ldy, int32_t B, int32_t H,
+                              int32_t W, int32_t C, uint32_t* peak, mv_stream_t stream);
+int mv_s16_map_to_rows_f16(const void* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t C, void* y, int64_t ldy, mv_stream_t stream);
 
 /* pack [Cout][Cin][k] fp32 (nn.Conv1d layout) -> fp16 [Cout_pad][k][Cin_pad]; returns element count */
 int64_t mv_conv1d_packed_elems(int32_t cout, int32_t cin, int32_t k);

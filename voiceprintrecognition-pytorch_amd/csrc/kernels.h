@@ -36,6 +36,13 @@ int map_merge_launch(const void* x, float* y, int64_t n, hipStream_t stream);
 // peak (optional device word): largest |64 * value| stored, as float bits (s16map.h)
 int conv2d_first_s16_launch(const float* feats, half_t* out, const float* w, const float* bias, int B, int T, int F, int C, hipStream_t stream, unsigned* peak = nullptr);
 int tstp_s16_launch(const half_t* x, int64_t ld, int B, int H, int W, int C, float* stats, hipStream_t stream);
+// the SE layer of ResNetSE on S16 maps and the map -> pooling rows hand-over (se2d.hip); peak as above
+size_t se2d_squeeze_ws_floats(int B, int H, int W, int C);
+int se2d_squeeze_launch(const half_t* x, int64_t ld, int B, int H, int W, int C, float* s, float* ws, size_t ws_floats, hipStream_t stream);
+int se2d_excite_launch(const float* s, const float* w1, const float* b1, const float* w2, const float* b2, float* g, int B, int C, int R, hipStream_t stream);
+int se2d_gate_res_relu_launch(const half_t* x, int64_t ldx, const float* g, const half_t* res, int64_t ldr, half_t* y, int64_t ldy, int B, int H, int W,
+                              int C, hipStream_t stream, unsigned* peak = nullptr);
+int s16_map_to_rows_launch(const half_t* x, int64_t ld, int B, int H, int W, int C, half_t* y, int64_t ldy, hipStream_t stream);
 
 // splitk_ws (optional, linear_f32_splitk_floats(B, K, O) floats; 0 = the direct kernel is what runs): long reductions over many rows as K slices + a
 // slice-ordered sum (linear.hip)
