@@ -473,6 +473,28 @@ typedef struct MvResNetSeCfg {
 } MvResNetSeCfg;
 int mv_resnetse_create(const MvResNetSeCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
 
+/* Res2Net.forward (mvector/models/res2net.py:89-174): conv7x7 stride-3 stem + MaxPool2d(3, 2, 1), four stages of Bottle2neck blocks (1x1 into `scale`
+ * slices of `width` channels -> a 3x3 conv (stride) per slice but the last, hierarchical sums in the 'normal' blocks -> the last slice passed on
+ * ('normal') or AvgPool2d(3, stride, 1)-ed ('stage') -> 1x1 + residual -> ReLU) on S16 maps, x.reshape(B, -1, T') -> the pooling head
+ * `pooling_type` (MV_POOL_*, prefix `pooling.`) -> bn2 -> linear -> bn3 folded into one exact-fp32 layer.  Entry point added under ABI 5.
+ * Refused with a message: scale outside 1..8; m_channels not a multiple of 8 or above 256 (the stem's limits); a stage without
+ * blocks; a block width floor(planes * base_width / 64) below 4; an input_size whose frequency size behind the four stages
+ * (h1 = (F - 5) / 3 + 1, h2 = (h1 - 1) / 2 + 1, then three times (h - 1) / 2 + 1) differs from input_size / base_width (the reference's own
+ * forward fails on such a model); a pooling_type outside MV_POOL_ASP .. MV_POOL_TSP; a missing tensor.  The forward needs at least 5 frames.
+ * Saturation: as ResNetSE -- one device word per handle, MV_INFO_S16_PEAK / MV_INFO_S16_SATURATED; MV_RES2NET_NO_PEAK or-ed into pooling_type
+ * builds the handle without it. */
+#define MV_RES2NET_NO_PEAK 0x100
+typedef struct MvRes2NetCfg {
+    int32_t input_size;   /* F (80) */
+    int32_t m_channels;   /* 32: a multiple of 8, at most 256 */
+    int32_t layers[4];    /* {3,4,6,3} */
+    int32_t base_width;   /* 32 */
+    int32_t scale;        /* 2: 1..8 */
+    int32_t embd_dim;     /* 192 */
+    int32_t pooling_type; /* MV_POOL_* */
+} MvRes2NetCfg;
+int mv_res2net_create(const MvRes2NetCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out);
+
 int mv_model_destroy(MvModel* m);
 int mv_model_embd_dim(const MvModel* m, int32_t* embd_dim);
 /* Model-specific facts (tests, logs).  Keys:
@@ -512,11 +534,15 @@ int mv_model_embd_dim(const MvModel* m, int32_t* embd_dim);
 #define MV_INFO_ECAPA_GROUPED_EXPANDED 21
 #define MV_INFO_ECAPA_EXPANDED_1X1 22
 #define MV_INFO_ECAPA_BLOCKS 23
-/* ResNetSE handles (mv_resnetse_create): the range of their S16 maps on the caller's inputs since create (both WAIT FOR THE DEVICE: diagnostics)
- *   MV_INFO_RESNETSE_PEAK        largest |map value| a launch wanted to store (real units; -1 on a MV_RESNETSE_NO_PEAK handle)
- *   MV_INFO_RESNETSE_SATURATED   1.0 when it exceeded 1023.5 and was clamped (the embeddings of that call are not to be trusted) */
-#define MV_INFO_RESNETSE_PEAK 30
-#define MV_INFO_RESNETSE_SATURATED 31
+/* ResNetSE and Res2Net handles (mv_resnetse_create, mv_res2net_create): the range of their S16 maps on the caller's inputs since create (both WAIT
+ * FOR THE DEVICE: diagnostics)
+ *   MV_INFO_S16_PEAK        largest |map value| a launch wanted to store (real units; -1 on a handle built with MV_*_NO_PEAK)
+ *   MV_INFO_S16_SATURATED   1.0 when it exceeded 1023.5 and was clamped (the embeddings of that call are not to be trusted)
+ * The MV_INFO_RESNETSE_* names are the same keys. */
+#define MV_INFO_S16_PEAK 30
+#define MV_INFO_S16_SATURATED 31
+#define MV_INFO_RESNETSE_PEAK MV_INFO_S16_PEAK
+#define MV_INFO_RESNETSE_SATURATED MV_INFO_S16_SATURATED
 int mv_model_info(const MvModel* m, int32_t key, float* value);
 int mv_model_workspace_bytes(const MvModel* m, int32_t B, int32_t T, size_t* bytes);
 /* feats: [B, T, F] fp32 (the AudioFeaturizer output layout); emb: [B, embd_dim] fp32. */
@@ -639,6 +665,29 @@ int mv_se2d_excite_f32(const float* s, const float* w1, const float* b1, const f
 int mv_se2d_gate_res_relu_s16(const void* x, int64_t ldx, const float* g, const void* res, int64_t ldres, void* y, int64_t ldy, int32_t B, int32_t H,
                               int32_t W, int32_t C, uint32_t* peak, mv_stream_t stream);
 int mv_s16_map_to_rows_f16(const void* x, int64_t ld, int32_t B, int32_t H, int32_t W, int32_t C, void* y, int64_t ldy, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The layers only Res2Net has, on S16 maps (csrc/res2net2d.hip; res2net.py:98-101, 35, 75).  Added under ABI 5.  Every entry point refuses null
+ * pointers, non-positive sizes, ld < C, ld % 16 != 0 and a stride other than 1 or 2 with a message.
+ *   mv_conv2d_stem7_s16       features fp32 [B, T, F] -> S16 [B, Ho, Wo, round_up(C, 16)] = relu(conv7x7(stride 3, zero padding 1) + bias), H =
+ *                             frequency, W = time, Ho = (F + 2 - 7) / 3 + 1, Wo likewise from T; w fp32 [C][49] (BatchNorm folded), products
+ *                             accumulated in fp32 in one fixed tap order; channels C .. of the last unit are exact zeros.  F >= 5, T >= 5 (where
+ *                             torch's Conv2d refuses too), C a multiple of 8, at most 256.
+ *   mv_conv2d_stem7_peak_s16  the same with the optional device word `peak` of MvConv2dsDesc.peak (largest |64 * value| before the clamp).
+ *   mv_maxpool3s2_s16         MaxPool2d(3, stride 2, padding 1): Ho = (H - 1) / 2 + 1, Wo likewise; taps outside the map take no part; the output
+ *                             pixel is the (hi, lo) pair of the window's largest merged value, copied as it is; padded channels of the last unit
+ *                             are zero bits.
+ *   mv_avgpool3_s16           AvgPool2d(3, stride 1 | 2, padding 1, count_include_pad): the merged values of the taps inside the map summed in fp32
+ *                             in a fixed order, divided by 9 and split again.
+ * x and y may be channel slices of wider maps: a pointer at a 16-channel unit with the map's leading dimension.
+ * ------------------------------------------------------------------------------------------------ */
+int mv_conv2d_stem7_s16(const float* feats, void* out, const float* w, const float* bias, int32_t B, int32_t T, int32_t F, int32_t C,
+                        mv_stream_t stream);
+int mv_conv2d_stem7_peak_s16(const float* feats, void* out, const float* w, const float* bias, int32_t B, int32_t T, int32_t F, int32_t C,
+                             uint32_t* peak, mv_stream_t stream);
+int mv_maxpool3s2_s16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t B, int32_t H, int32_t W, int32_t C, mv_stream_t stream);
+int mv_avgpool3_s16(const void* x, int64_t ldx, void* y, int64_t ldy, int32_t B, int32_t H, int32_t W, int32_t C, int32_t stride,
+                    mv_stream_t stream);
 
 /* pack [Cout][Cin][k] fp32 (nn.Conv1d layout) -> fp16 [Cout_pad][k][Cin_pad]; returns element count */
 int64_t mv_conv1d_packed_elems(int32_t cout, int32_t cin, int32_t k);

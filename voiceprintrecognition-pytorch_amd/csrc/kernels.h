@@ -43,6 +43,11 @@ int se2d_excite_launch(const float* s, const float* w1, const float* b1, const f
 int se2d_gate_res_relu_launch(const half_t* x, int64_t ldx, const float* g, const half_t* res, int64_t ldr, half_t* y, int64_t ldy, int B, int H, int W,
                               int C, hipStream_t stream, unsigned* peak = nullptr);
 int s16_map_to_rows_launch(const half_t* x, int64_t ld, int B, int H, int W, int C, half_t* y, int64_t ldy, hipStream_t stream);
+// the layers only Res2Net has (res2net2d.hip): the 7x7 stride-3 stem (C a multiple of 8, at most 256: channels C .. round_up(C, 16) are zeros; peak as above),
+// MaxPool2d(3, 2, 1) and AvgPool2d(3, stride, 1) on S16 maps or 16-channel-aligned slices of them
+int conv2d_stem7_s16_launch(const float* feats, half_t* out, const float* w, const float* bias, int B, int T, int F, int C, hipStream_t stream, unsigned* peak = nullptr);
+int maxpool3s2_s16_launch(const half_t* x, int64_t ldx, half_t* y, int64_t ldy, int B, int H, int W, int C, hipStream_t stream);
+int avgpool3_s16_launch(const half_t* x, int64_t ldx, half_t* y, int64_t ldy, int B, int H, int W, int C, int stride, hipStream_t stream);
 
 // splitk_ws (optional, linear_f32_splitk_floats(B, K, O) floats; 0 = the direct kernel is what runs): long reductions over many rows as K slices + a
 // slice-ordered sum (linear.hip)

@@ -93,13 +93,20 @@ class MvEres2Cfg(ctypes.Structure):
 
 
 MV_RESNETSE_NO_PEAK = 0x100   # or-ed into MvResNetSeCfg.pooling_type: a handle without the saturation word (tools that time what it costs)
-MV_INFO_RESNETSE_PEAK, MV_INFO_RESNETSE_SATURATED = 30, 31
+MV_INFO_S16_PEAK, MV_INFO_S16_SATURATED = 30, 31   # ResNetSE and Res2Net handles: the range of their S16 maps since create
+MV_INFO_RESNETSE_PEAK, MV_INFO_RESNETSE_SATURATED = MV_INFO_S16_PEAK, MV_INFO_S16_SATURATED   # (the names the keys were introduced under)
+MV_RES2NET_NO_PEAK = 0x100    # or-ed into MvRes2NetCfg.pooling_type, as MV_RESNETSE_NO_PEAK
 MV_SE2D_SQUEEZE_CHUNK = 256   # pixels per partial sum of mv_se2d_squeeze_s16
 
 
 class MvResNetSeCfg(ctypes.Structure):
     _fields_ = [('input_size', c_i32), ('layers', c_i32 * 4), ('num_filters', c_i32 * 4), ('embd_dim', c_i32), ('pooling_type', c_i32),
                 ('reduction', c_i32)]
+
+
+class MvRes2NetCfg(ctypes.Structure):
+    _fields_ = [('input_size', c_i32), ('m_channels', c_i32), ('layers', c_i32 * 4), ('base_width', c_i32), ('scale', c_i32), ('embd_dim', c_i32),
+                ('pooling_type', c_i32)]
 
 
 class MvConv2dsDesc(ctypes.Structure):
@@ -160,6 +167,11 @@ _SIGNATURES = {
     'mv_se2d_excite_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     'mv_se2d_gate_res_relu_s16': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'mv_s16_map_to_rows_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
+    'mv_res2net_create': (c_i32, [ctypes.POINTER(MvRes2NetCfg), ctypes.POINTER(MvTensorRef), c_i32, ctypes.POINTER(c_vp)]),
+    'mv_conv2d_stem7_s16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    'mv_conv2d_stem7_peak_s16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    'mv_maxpool3s2_s16': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    'mv_avgpool3_s16': (c_i32, [c_vp, c_i64, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'mv_conv2d_first': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     'mv_tstp_f32': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'mv_conv2ds_packed_elems': (c_i64, [c_i32, c_i32, c_i32]),
@@ -694,8 +706,8 @@ class Model:
     """Handle of a native backbone (mv_*_create / mv_model_forward) built from a reference-layout state_dict.
 
     ``pooling_type`` ('ASP' | 'SAP' | 'TAP' | 'TSP', or an MV_POOL_* code): the head of an 'ecapa' or 'tdnn' backbone
-    (mv_*_create_pooled); other kinds have one head and take 'ASP' only, which stands for "the model's own" ('resnet_se': the head its
-    MvResNetSeCfg.pooling_type names)."""
+    (mv_*_create_pooled); other kinds have one head and take 'ASP' only, which stands for "the model's own" ('resnet_se', 'res2net': the
+    head their config's pooling_type names)."""
 
     def __init__(self, kind, cfg, state_dict, cdll=None, pooling_type='ASP'):
         self._cdll = cdll or lib()
@@ -716,7 +728,7 @@ class Model:
         elif pool == MV_POOL_ASP:   # (the plain create calls: the handles every ASP model has always built)
             create = {'ecapa': self._cdll.mv_ecapa_create, 'campp': self._cdll.mv_campp_create,
                       'tdnn': self._cdll.mv_tdnn_create, 'eres2net': self._cdll.mv_eres2net_create,
-                      'resnet_se': self._cdll.mv_resnetse_create}[kind]
+                      'resnet_se': self._cdll.mv_resnetse_create, 'res2net': self._cdll.mv_res2net_create}[kind]
         else:
             pooled = {'ecapa': self._cdll.mv_ecapa_create_pooled, 'tdnn': self._cdll.mv_tdnn_create_pooled}[kind]
             create = lambda c, r, n, out: pooled(c, pool, r, n, out)   # noqa: E731
@@ -736,15 +748,18 @@ class Model:
     def info(self, key):
         """mv_model_info: 1 = CAM++ head on fp32 maps (1.0 / 0.0), 2 = its creation-time calibration 1 - cos, 3 + p = probe p's figure;
         EcapaTdnn: MV_INFO_ECAPA_* (20 grouped layers on the grouped GEMM, 21 expanded, 22 expanded 1x1 ones, 23 SE-Res2Net blocks);
-        ResNetSE: MV_INFO_RESNETSE_* (30 largest map value since create, 31 saturated; both wait for the device)"""
+        ResNetSE, Res2Net: MV_INFO_S16_* (30 largest map value since create, 31 saturated; both wait for the device)"""
         v = c_f32()
         check(self._cdll.mv_model_info(self._h, key, ctypes.byref(v)), self._cdll)
         return v.value
 
-    def resnet_se_range(self):
-        """ResNetSE handles: {'peak': largest |map value| a launch wanted to store since create, 'saturated': it exceeded the S16 range 1023.5
-        (the embeddings of that call are not to be trusted)}.  WAITS FOR THE DEVICE, like campp_head(range=True): a diagnostic, never on a hot path."""
-        return {'peak': self.info(MV_INFO_RESNETSE_PEAK), 'saturated': self.info(MV_INFO_RESNETSE_SATURATED) == 1.0}
+    def s16_range(self):
+        """ResNetSE and Res2Net handles: {'peak': largest |map value| a launch wanted to store since create, 'saturated': it exceeded the S16 range
+        1023.5 (the embeddings of that call are not to be trusted)}.  WAITS FOR THE DEVICE, like campp_head(range=True): a diagnostic, never on a
+        hot path."""
+        return {'peak': self.info(MV_INFO_S16_PEAK), 'saturated': self.info(MV_INFO_S16_SATURATED) == 1.0}
+
+    resnet_se_range = s16_range   # (the name it was introduced under)
 
     XVEC_WARN = 2.5e-5   # MV_CAMPP_XVEC_WARN (include/mvector_hip.h)
 
