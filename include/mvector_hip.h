@@ -39,6 +39,7 @@ extern "C" {
 #define MV_ERR_UNSUPPORTED (-3)
 #define MV_ERR_WORKSPACE (-4)
 #define MV_ERR_MISSING_TENSOR (-5)
+#define MV_ERR_NOT_CONVERGED (-6) /* mv_laplacian_eig_lowest ran out of iterations; MvEigInfo carries the residual */
 
 #define MV_ABI_VERSION 5
 
@@ -847,6 +848,58 @@ int mv_profile_read(int32_t kernel_class, int32_t* calls, double* total_ms, doub
  * (device int32 array, may be NULL). */
 int mv_wave_prepare_i16(const int16_t* pcm, int64_t pcm_stride, const int64_t* num_samples, int32_t B, int64_t L, int32_t normalize,
                         float target_db, float max_gain_db, float* wav, int64_t wav_stride, int32_t* too_quiet, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Speaker diarization behind the embeddings (mvector/infer_utils/speaker_diarization.py; added within ABI 5).
+ * Every sum runs in one fixed order: results are bit-identical from run to run and on any stream.
+ * ------------------------------------------------------------------------------------------------ */
+/* Chunk rows out of ONE resident waveform wav[L] (fp32): rows[i] = wav[start[i] : start[i] + len[i]] followed by zeros up to chunk_len
+ * (start / len: device int64 arrays of n entries, clamped to the waveform and to chunk_len).  normalize != 0: the dB normalisation of
+ * the int16 entry point above with the same gain formula, max_gain_db and too_quiet flags, the mean square (an fp64 sum) taken over all
+ * chunk_len samples, zeros included -- the reference's predict_batch normalises the already padded chunk. */
+int mv_wave_chunks_f32(const float* wav, int64_t L, const int64_t* start, const int64_t* len, int32_t n, int64_t chunk_len, int32_t normalize,
+                       float target_db, float max_gain_db, float* rows, int64_t rows_stride, int32_t* too_quiet, mv_stream_t stream);
+
+/* Cosine matrix S [N, N] fp32 -> M [N, N] fp32 and degree [N] fp64 (SpectralCluster.p_pruning, the symmetrisation and get_laplacian):
+ * per row the n_prune smallest entries are dropped (n_prune = the reference's int((1 - pval) * N), computed by the caller); among equal
+ * values the LOWER column index is dropped first (numpy's default argsort leaves the order of ties open: this rule is the library's);
+ * M_ij = 0.5f * (kept_ij ? S_ij : 0 + kept_ji ? S_ji : 0) in fp32, M_ii = 0; degree_i = sum_j |M_ij| in fp64.
+ * 1 <= N <= 16384 (a row of keys is 64 KiB of LDS there and M is 1 GiB), 0 <= n_prune < N; M must not alias S.  workspace: device
+ * memory of the size the companion function reports (0 for an N it refuses). */
+size_t mv_affinity_laplacian_workspace_bytes(int32_t N);
+int mv_affinity_laplacian_f32(const float* S, int32_t N, int32_t n_prune, float* M, double* degree, void* workspace, size_t workspace_bytes,
+                              mv_stream_t stream);
+
+/* The m lowest eigenpairs of L = diag(degree) - M (M fp32 [N, N] symmetric with a zero diagonal, degree fp64 [N], both on the device) by
+ * Chebyshev-filtered subspace iteration in fp64 on a block of vectors: seeded fixed start block, then per iteration a scaled Chebyshev filter
+ * of the given degree that damps [largest Ritz value, ub], ub = 2 max degree; Cholesky-QR twice on column-scaled vectors; Rayleigh-Ritz;
+ * stop when the largest residual |L v_i - lambda_i v_i|_2 of the m wanted columns is <= tol * ub.  On a non-positive Cholesky pivot the
+ * iteration is repeated from the last Ritz vectors with half the filter degree (counted in MvEigInfo.retries).
+ * lambdas [m] (ascending) and info are HOST memory; vecs [N, m] fp64 row-major is device memory.  The b x b problems are solved on the
+ * host between launches: THIS CALL SYNCHRONISES ITS STREAM (several times) and has returned its results when it returns.
+ * 2 <= N <= 16384, 1 <= m <= min(16, N), block 0 (= min(32, N)) or m .. min(32, N).  Out of iterations: MV_ERR_NOT_CONVERGED, with lambdas,
+ * vecs and info holding the last Ritz pairs.  workspace: device memory, 16-byte aligned, of the size the companion reports (0 for a cfg it
+ * refuses); nothing is allocated on the device per call. */
+typedef struct MvEigCfg {
+    int32_t m;         /* wanted eigenpairs */
+    int32_t block;     /* vectors iterated; 0 = min(32, N) */
+    int32_t degree;    /* Chebyshev filter degree = products with L per iteration besides the Rayleigh-Ritz one */
+    int32_t max_iters;
+    double tol;        /* relative to ub */
+    uint64_t seed;     /* of the start block */
+} MvEigCfg;
+typedef struct MvEigInfo {
+    int32_t iterations;
+    int32_t products;  /* block products with L */
+    int32_t retries;   /* iterations repeated with half the filter degree */
+    int32_t converged;
+    double residual;   /* largest of the m wanted columns, absolute */
+    double ub;         /* 2 max degree */
+} MvEigInfo;
+void mv_laplacian_eig_default_cfg(MvEigCfg* cfg); /* m 16, block 0, degree 16, max_iters 60, tol 1e-6 */
+size_t mv_laplacian_eig_lowest_workspace_bytes(int32_t N, const MvEigCfg* cfg);
+int mv_laplacian_eig_lowest(const float* M, const double* degree, int32_t N, const MvEigCfg* cfg, double* lambdas, double* vecs, MvEigInfo* info,
+                            void* workspace, size_t workspace_bytes, mv_stream_t stream);
 
 /* Attentive-statistics pooling tail (mvector/models/pooling.py:117-125): attention logits = W2 . h (the bias of the
  * projection is constant over time and cancels in the softmax over time), softmax over time, weighted mean / std.

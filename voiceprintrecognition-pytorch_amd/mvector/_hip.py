@@ -133,6 +133,15 @@ class MvConv1dDesc(ctypes.Structure):
                 ('persist_blocks_hint', c_i32), ('clock_probe', c_vp)]
 
 
+class MvEigCfg(ctypes.Structure):
+    _fields_ = [('m', c_i32), ('block', c_i32), ('degree', c_i32), ('max_iters', c_i32), ('tol', ctypes.c_double), ('seed', ctypes.c_uint64)]
+
+
+class MvEigInfo(ctypes.Structure):
+    _fields_ = [('iterations', c_i32), ('products', c_i32), ('retries', c_i32), ('converged', c_i32), ('residual', ctypes.c_double),
+                ('ub', ctypes.c_double)]
+
+
 _SIGNATURES = {
     'mv_last_error': (ctypes.c_char_p, []),
     'mv_abi_version': (c_i32, []),
@@ -251,6 +260,13 @@ _SIGNATURES = {
     'mv_cam_dense_block_workspace_bytes': (c_i32, [c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
     'mv_cam_dense_block_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_i32] + [ctypes.POINTER(c_vp)] * 10 +
                                [c_i32, c_i32, c_i32, ctypes.POINTER(c_i32), c_vp, c_sz, c_vp]),
+    'mv_wave_chunks_f32': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_i32, c_i64, c_i32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
+    'mv_affinity_laplacian_workspace_bytes': (c_sz, [c_i32]),
+    'mv_affinity_laplacian_f32': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_laplacian_eig_default_cfg': (None, [ctypes.POINTER(MvEigCfg)]),
+    'mv_laplacian_eig_lowest_workspace_bytes': (c_sz, [c_i32, ctypes.POINTER(MvEigCfg)]),
+    'mv_laplacian_eig_lowest': (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(MvEigCfg), ctypes.POINTER(ctypes.c_double), c_vp,
+                                        ctypes.POINTER(MvEigInfo), c_vp, c_sz, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -835,6 +851,71 @@ def cosine(a, b, cdll=None):
         check(cdll.mv_cosine_f32(a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], out.data_ptr(),
                                  current_stream(a)), cdll)
     return out
+
+
+def wave_chunks(wav, start, length, chunk_len, target_db=None, max_gain_db=300.0, cdll=None):
+    """One resident fp32 waveform [L] and the chunk table (int64 tensors start / length, [n]) -> (rows [n, chunk_len] fp32, too_quiet int32
+    [n]): row i = wav[start_i : start_i + length_i] followed by zeros, dB-normalised over the padded row unless ``target_db`` is None."""
+    cdll = cdll or lib()
+    assert wav.dim() == 1 and wav.dtype == torch.float32 and start.shape == length.shape and start.dim() == 1
+    wav = wav.contiguous()
+    start = start.to(device=wav.device, dtype=torch.int64).contiguous()
+    length = length.to(device=wav.device, dtype=torch.int64).contiguous()
+    n, chunk_len = start.shape[0], int(chunk_len)
+    rows = torch.empty((n, chunk_len), dtype=torch.float32, device=wav.device)
+    flags = torch.zeros((n,), dtype=torch.int32, device=wav.device)
+    check(cdll.mv_wave_chunks_f32(wav.data_ptr(), wav.shape[0], start.data_ptr(), length.data_ptr(), n, chunk_len, 0 if target_db is None else 1,
+                                  float(target_db or 0.0), float(max_gain_db), rows.data_ptr(), chunk_len, flags.data_ptr(), current_stream(wav)),
+          cdll)
+    return rows, flags
+
+
+def affinity_laplacian(sim, n_prune, cdll=None):
+    """Cosine matrix [N, N] fp32 -> (M [N, N] fp32, degree [N] fp64): per row the ``n_prune`` smallest entries dropped (ties: the lower column
+    first), M = 0.5 * (pruned + pruned^T) with a zero diagonal, degree_i = sum_j |M_ij|.  The Laplacian is diag(degree) - M."""
+    cdll = cdll or lib()
+    assert sim.dim() == 2 and sim.shape[0] == sim.shape[1] and sim.dtype == torch.float32
+    sim = sim.contiguous()
+    N = sim.shape[0]
+    M = torch.empty_like(sim)
+    degree = torch.empty((N,), dtype=torch.float64, device=sim.device)
+    ws = torch.empty((max(int(cdll.mv_affinity_laplacian_workspace_bytes(N)), 16),), dtype=torch.uint8, device=sim.device)
+    check(cdll.mv_affinity_laplacian_f32(sim.data_ptr(), N, int(n_prune), M.data_ptr(), degree.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         current_stream(sim)), cdll)
+    return M, degree
+
+
+MV_ERR_NOT_CONVERGED = -6
+
+
+def laplacian_eig_lowest(M, degree, m=16, block=0, filter_degree=None, max_iters=None, tol=None, seed=None, cdll=None):
+    """The ``m`` lowest eigenpairs of diag(degree) - M (mv_laplacian_eig_lowest) -> (eigenvalues float64 numpy [m] ascending, eigenvectors
+    [N, m] float64 on the device of ``M``, info dict).  Synchronises the current stream.  Raises RuntimeError carrying the residual when the
+    iteration does not converge: there is no other path."""
+    cdll = cdll or lib()
+    assert M.dim() == 2 and M.shape[0] == M.shape[1] and M.dtype == torch.float32 and degree.dtype == torch.float64
+    M, degree = M.contiguous(), degree.to(M.device).contiguous()
+    N = M.shape[0]
+    cfg = MvEigCfg()
+    cdll.mv_laplacian_eig_default_cfg(ctypes.byref(cfg))
+    cfg.m, cfg.block = int(m), int(block)
+    for field, value in (('degree', filter_degree), ('max_iters', max_iters), ('tol', tol), ('seed', seed)):
+        if value is not None:
+            setattr(cfg, field, value)
+    nbytes = int(cdll.mv_laplacian_eig_lowest_workspace_bytes(N, ctypes.byref(cfg)))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=M.device)
+    lambdas = (ctypes.c_double * max(cfg.m, 1))()
+    vecs = torch.empty((N, max(cfg.m, 0)), dtype=torch.float64, device=M.device)
+    info = MvEigInfo()
+    rc = cdll.mv_laplacian_eig_lowest(M.data_ptr(), degree.data_ptr(), N, ctypes.byref(cfg), lambdas, vecs.data_ptr(), ctypes.byref(info),
+                                      ws.data_ptr(), nbytes, current_stream(M))
+    out = {f: getattr(info, f) for f, _ in MvEigInfo._fields_}
+    if rc == MV_ERR_NOT_CONVERGED:
+        raise RuntimeError(f'libmvector_hip: {cdll.mv_last_error().decode(errors="replace")} (code {rc}; residual {info.residual:.3e}, '
+                           f'ub {info.ub:.3e}, {info.iterations} iterations, {info.products} products)')
+    check(rc, cdll)
+    import numpy as np
+    return np.array(lambdas[:cfg.m], dtype=np.float64), vecs, out
 
 
 MV_ERR_UNSUPPORTED = -3

@@ -251,8 +251,56 @@ class MVectorPredictor:
             self._device_gallery.remove(user_name)
         return ok
 
-    def speaker_diarization(self, audio_data, sample_rate=16000, speaker_num=None, search_audio_db=False):
-        """说话人日志: VAD segmentation and spectral clustering are host post-processing of the reference
-        (mvector/infer_utils/speaker_diarization.py) and are not part of the accelerated embedding path."""
-        raise NotImplementedError('speaker diarization (VAD + spectral clustering around predict_batch) is outside '
-                                  'the MI355X embedding path of this package; use predict_batch for the embeddings')
+    @torch.no_grad()
+    def _embed_chunks_device(self, samples, starts, lens, chunk_len, batch_size=256):
+        """GPU path of speaker_diarization: the recording goes up ONCE, mv_wave_chunks_f32 cuts (and dB-normalises) the chunk rows there, the
+        front-end and the backbone run in steps of at least 256 rows -> embeddings [n, embd_dim] that stay on the device."""
+        from mvector import _hip
+        dataset = self.configs.dataset_conf.dataset
+        wav = torch.from_numpy(np.ascontiguousarray(samples, dtype=np.float32)).to(self.device)
+        rows, too_quiet = _hip.wave_chunks(wav, torch.from_numpy(starts), torch.from_numpy(lens), chunk_len,
+                                           dataset.target_dB if dataset.use_dB_normalization else None)
+        step = max(int(batch_size), 256)
+        features = []
+        for i in range(0, rows.shape[0], step):
+            part = rows[i:i + step]
+            ratio = torch.ones((part.shape[0],), dtype=torch.float32, device=self.device)   # every row is chunk_len long, as in predict_batch
+            features.append(self.predictor(self._audio_featurizer(part, ratio)).data)
+        if bool(too_quiet.any().item()):
+            raise ValueError(f'无法将段规范化到{dataset.target_dB}dB，音频增益已经超过max_gain_db (300.0dB)')
+        return torch.cat(features, dim=0)
+
+    def speaker_diarization(self, audio_data, sample_rate=16000, speaker_num=None, search_audio_db=False, vad_segments=None):
+        """说话人日志识别 -> [{'speaker', 'start', 'end'}]
+
+        :param audio_data: 需要识别的数据，支持文件路径，文件对象，字节，numpy，AudioSegment对象
+        :param sample_rate: 如果传入的是numpy数据，需要指定采样率
+        :param speaker_num: 预期的说话人数量，提供说话人数量可以提高准确率 (at most 16 on the GPU predictor)
+        :param search_audio_db: 是否在声纹库中搜索说话人的名字
+        :param vad_segments: speech regions [{'start': seconds, 'end': seconds}, ...] (the shape yeaudio's VAD returns); needed unless
+                             ``audio_data`` is a segment object with a ``vad`` method -- this package ships no VAD
+
+        GPU predictor: one upload of the recording, chunk rows / front-end / backbone / cosine / pruned Laplacian / lowest eigenpairs on
+        the device (mvector/infer_utils/speaker_diarization.py), k_means and the merging on the host.  ``use_gpu=False``: predict_batch
+        and the host classes, as the reference."""
+        from mvector.infer_utils.speaker_diarization import SpeakerDiarization
+        if getattr(self, 'speaker_diarize', None) is None:
+            self.speaker_diarize = SpeakerDiarization()
+        input_data = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+        if self.device.type == 'cuda':
+            dataset = self.configs.dataset_conf.dataset
+            segments, starts, lens, chunk_len = self.speaker_diarize.chunk_table(input_data, vad_segments=vad_segments)
+            duration = chunk_len / float(input_data.sample_rate)   # the reference loads every (padded) chunk through _load_audio
+            assert duration >= dataset.min_duration, f'音频太短，最小应该为{dataset.min_duration}s，当前音频为{duration}s'
+            features = self._embed_chunks_device(input_data.samples, starts, lens, chunk_len)
+        else:
+            segments = self.speaker_diarize.segments_audio(input_data, vad_segments=vad_segments)
+            features = self.predict_batch([segment[2] for segment in segments], sample_rate=input_data.sample_rate)
+        labels, spk_center_embeddings = self.speaker_diarize.clustering(features, speaker_num=speaker_num)
+        outputs = self.speaker_diarize.postprocess(segments, labels)
+        if search_audio_db:
+            assert self._gallery is not None and len(self._gallery.names) > 0, "数据库中没有音频数据，请先指定说话人特征数据库或者注册说话人"
+            names = self._best_matches(spk_center_embeddings)
+            outputs = [{'speaker': names[o['speaker']][0] if names[o['speaker']][0] else f"陌生人{o['speaker']}", 'start': o['start'],
+                        'end': o['end']} for o in outputs]
+        return outputs
