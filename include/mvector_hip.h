@@ -901,6 +901,54 @@ size_t mv_laplacian_eig_lowest_workspace_bytes(int32_t N, const MvEigCfg* cfg);
 int mv_laplacian_eig_lowest(const float* M, const double* degree, int32_t N, const MvEigCfg* cfg, double* lambdas, double* vecs, MvEigInfo* info,
                             void* workspace, size_t workspace_bytes, mv_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Verification metrics of an evaluation (mvector/metric/metrics.py behind MVectorTrainer.evaluate; added within ABI 5).
+ * Integer counts and single fp64 operations only: results are bit-identical from run to run and on any stream.  Every step is a chain
+ * of ordinary launches ordered by the stream; no workgroup waits for another one.
+ * ------------------------------------------------------------------------------------------------ */
+/* Ascending stable sort of N fp32 scores with their flat indices: sorted_scores[i] = scores[sorted_index[i]], in the order of
+ * numpy.argsort(scores, kind='stable') -- equal scores (-0 == +0 among them) keep their index order, NaNs of either sign come last in
+ * index order.  A -0 comes out as +0 and a NaN as the quiet NaN 0x7FFFFFFF; every other value keeps its bits.
+ * LSD radix sort over four 8-bit digits of the order-preserving key, tiles of mv_sort_scores_tile() keys.  1 <= N <= 2^31 - 1.
+ * scores, sorted_scores [N] and sorted_index [N] are distinct device buffers; workspace: device memory, 16-byte aligned, of the size the
+ * companion reports (0 for an N it refuses). */
+int32_t mv_sort_scores_tile(void);
+size_t mv_sort_scores_workspace_bytes(int64_t N);
+int mv_sort_scores_f32(const float* scores, int64_t N, float* sorted_scores, uint32_t* sorted_index, void* workspace, size_t workspace_bytes,
+                       mv_stream_t stream);
+
+/* EER, minDCF and threshold ingredients of the score matrix scores [n_trials, n_enroll] (fp32, row-major, device), trial (i, j) being a
+ * target when trial_labels[i] == enroll_labels[j] (device int32 arrays).  With the N = n_trials * n_enroll scores in stable ascending order,
+ * T_i = targets among positions 0 .. i, I_i = i + 1 - T_i, and in fp64, each operation rounded once (no contraction):
+ *   fnr_i = T_i / NT,  fpr_i = 1 - I_i / NI,  c_i = (c_miss * fnr_i) * p_target + (c_fa * fpr_i) * (1 - p_target)
+ * the result holds i1 = the first i with fnr_i - fpr_i >= 0 (-1: none), i2 = the last i with fnr_i - fpr_i < 0 (-1: none), T at both,
+ * min_i c_i and the score at sorted position i1.  The interpolation of the EER and the division by the default cost are the caller's
+ * (metrics.verification_metrics).  No target or no impostor trial is reported (n_target / n_impostor = 0; the other fields then mean
+ * nothing), not refused.  sorted_scores [N] fp32 and tgt_cum [N] uint32 (= T) are optional device outputs (NULL: not written).
+ * result is HOST memory: THIS CALL SYNCHRONISES ITS STREAM and has returned its result when it returns.  1 <= N <= 2^31 - 1,
+ * 0 < p_target < 1, c_miss >= 0, c_fa >= 0.  workspace: device memory, 16-byte aligned, of the size the companion reports (0 for a shape
+ * it refuses); nothing is allocated per call. */
+typedef struct MvVerifCfg {
+    double p_target;
+    double c_miss;
+    double c_fa;
+} MvVerifCfg;
+typedef struct MvVerifResult {
+    int64_t n_target;    /* NT */
+    int64_t n_impostor;  /* NI */
+    int64_t i1;
+    int64_t i2;
+    int64_t tgt_i1;      /* T at i1 */
+    int64_t tgt_i2;      /* T at i2 */
+    double min_cost;     /* min_i c_i, not yet divided by the default cost */
+    float score_i1;      /* the threshold */
+    int32_t reserved;
+} MvVerifResult;
+size_t mv_verif_metrics_workspace_bytes(int64_t n_trials, int64_t n_enroll);
+int mv_verif_metrics_f32(const float* scores, int64_t n_trials, int64_t n_enroll, const int32_t* trial_labels, const int32_t* enroll_labels,
+                         const MvVerifCfg* cfg, MvVerifResult* result, float* sorted_scores, uint32_t* tgt_cum, void* workspace,
+                         size_t workspace_bytes, mv_stream_t stream);
+
 /* Attentive-statistics pooling tail (mvector/models/pooling.py:117-125): attention logits = W2 . h (the bias of the
  * projection is constant over time and cancels in the softmax over time), softmax over time, weighted mean / std.
  *   h  fp16 [B, T, A] (tanh output, |h| <= 1),  w2_packed = mv_conv1d_pack_weight of  W2[C, A, 1] * log2(e),

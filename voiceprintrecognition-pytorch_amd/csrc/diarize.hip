@@ -19,6 +19,7 @@
 // The b x b problems (Cholesky, triangular inverse, cyclic Jacobi) are solved on the host between launches:
 // mv_laplacian_eig_lowest synchronises its stream.
 #include "common.h"
+#include "order_key.h"
 
 #include <vector>
 
@@ -79,13 +80,7 @@ __global__ __launch_bounds__(256) void wave_chunks_kernel(const float* wav, int6
 }
 
 // ------------------------------------------------------------------------------------------------ affinity
-// unsigned key with the order of the floats (-0 and +0 share one key, as they compare equal)
-__device__ __forceinline__ uint32_t order_key(float x) {
-    uint32_t u = __builtin_bit_cast(uint32_t, x);
-    if (u == 0x80000000u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
+// (keys: order_key of order_key.h, an unsigned image with the order of the floats)
 // entry (row, col) survives the pruning of its row: above the cut, or equal to it from column tie_col on
 __device__ __forceinline__ bool kept(uint32_t key, int col, uint32_t cut_key, uint32_t tie_col) {
     return key > cut_key || (key == cut_key && (uint32_t)col >= tie_col);

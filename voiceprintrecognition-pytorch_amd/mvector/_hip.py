@@ -142,6 +142,15 @@ class MvEigInfo(ctypes.Structure):
                 ('ub', ctypes.c_double)]
 
 
+class MvVerifCfg(ctypes.Structure):
+    _fields_ = [('p_target', ctypes.c_double), ('c_miss', ctypes.c_double), ('c_fa', ctypes.c_double)]
+
+
+class MvVerifResult(ctypes.Structure):
+    _fields_ = [('n_target', c_i64), ('n_impostor', c_i64), ('i1', c_i64), ('i2', c_i64), ('tgt_i1', c_i64), ('tgt_i2', c_i64),
+                ('min_cost', ctypes.c_double), ('score_i1', c_f32), ('reserved', c_i32)]
+
+
 _SIGNATURES = {
     'mv_last_error': (ctypes.c_char_p, []),
     'mv_abi_version': (c_i32, []),
@@ -267,6 +276,12 @@ _SIGNATURES = {
     'mv_laplacian_eig_lowest_workspace_bytes': (c_sz, [c_i32, ctypes.POINTER(MvEigCfg)]),
     'mv_laplacian_eig_lowest': (c_i32, [c_vp, c_vp, c_i32, ctypes.POINTER(MvEigCfg), ctypes.POINTER(ctypes.c_double), c_vp,
                                         ctypes.POINTER(MvEigInfo), c_vp, c_sz, c_vp]),
+    'mv_sort_scores_tile': (c_i32, []),
+    'mv_sort_scores_workspace_bytes': (c_sz, [c_i64]),
+    'mv_sort_scores_f32': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_verif_metrics_workspace_bytes': (c_sz, [c_i64, c_i64]),
+    'mv_verif_metrics_f32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(MvVerifCfg), ctypes.POINTER(MvVerifResult), c_vp, c_vp,
+                                     c_vp, c_sz, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -916,6 +931,48 @@ def laplacian_eig_lowest(M, degree, m=16, block=0, filter_degree=None, max_iters
     check(rc, cdll)
     import numpy as np
     return np.array(lambdas[:cfg.m], dtype=np.float64), vecs, out
+
+
+def sort_scores(scores, cdll=None):
+    """fp32 scores of any shape -> (sorted [N] fp32 ascending, index [N] int32) with sorted[i] = scores.reshape(-1)[index[i]], in the order
+    of ``numpy.argsort(scores, kind='stable')``: equal scores keep their flat-index order, NaNs come last (mv_sort_scores_f32)."""
+    cdll = cdll or lib()
+    assert scores.dtype == torch.float32
+    flat = scores.contiguous().reshape(-1)
+    N = flat.shape[0]
+    out = torch.empty((N,), dtype=torch.float32, device=flat.device)
+    index = torch.empty((N,), dtype=torch.int32, device=flat.device)   # N <= 2^31 - 1: every index is a non-negative int32
+    nbytes = int(cdll.mv_sort_scores_workspace_bytes(N))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=flat.device)
+    check(cdll.mv_sort_scores_f32(flat.data_ptr(), N, out.data_ptr(), index.data_ptr(), ws.data_ptr(), nbytes, current_stream(flat)), cdll)
+    return out, index
+
+
+def verification_metrics(scores, trial_labels, enroll_labels, p_target=0.01, c_miss=1, c_fa=1, curve=False, cdll=None):
+    """Score matrix [n_trials, n_enroll] fp32 and the two int32 label vectors, all on one device -> dict of the counts EER, minDCF and the
+    threshold are made of (the fields of MvVerifResult: n_target, n_impostor, i1, i2, tgt_i1, tgt_i2, min_cost, score_i1); with ``curve`` also
+    'sorted_scores' [N] fp32 and 'tgt_cum' [N] int32 (targets among the sorted positions 0 .. i) on the device.  Equal scores are ordered by
+    their flat index.  Synchronises the current stream (mv_verif_metrics_f32)."""
+    cdll = cdll or lib()
+    assert scores.dim() == 2 and scores.dtype == torch.float32
+    scores = scores.contiguous()
+    n_trials, n_enroll = scores.shape
+    trial_labels = trial_labels.to(device=scores.device, dtype=torch.int32).contiguous()
+    enroll_labels = enroll_labels.to(device=scores.device, dtype=torch.int32).contiguous()
+    assert trial_labels.shape == (n_trials,) and enroll_labels.shape == (n_enroll,)
+    N = n_trials * n_enroll
+    cfg = MvVerifCfg(float(p_target), float(c_miss), float(c_fa))
+    res = MvVerifResult()
+    sorted_scores = torch.empty((N,), dtype=torch.float32, device=scores.device) if curve else None
+    tgt_cum = torch.empty((N,), dtype=torch.int32, device=scores.device) if curve else None
+    nbytes = int(cdll.mv_verif_metrics_workspace_bytes(n_trials, n_enroll))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=scores.device)
+    check(cdll.mv_verif_metrics_f32(scores.data_ptr(), n_trials, n_enroll, trial_labels.data_ptr(), enroll_labels.data_ptr(), ctypes.byref(cfg),
+                                    ctypes.byref(res), _ptr(sorted_scores), _ptr(tgt_cum), ws.data_ptr(), nbytes, current_stream(scores)), cdll)
+    out = {f: getattr(res, f) for f, _ in MvVerifResult._fields_ if f != 'reserved'}
+    if curve:
+        out['sorted_scores'], out['tgt_cum'] = sorted_scores, tgt_cum
+    return out
 
 
 MV_ERR_UNSUPPORTED = -3

@@ -10,7 +10,11 @@ raise.  What changed underneath ``evaluate`` (not in its contract):
   (trainer.py:452-461).
 * CPU (``use_gpu=False``): the reference's flow -- per-item featurisation in the dataset, padded feature batches, torch
   graphs.
-The metrics (EER, minDCF, threshold) are computed on the host from the same flattened score / label arrays.
+* GPU: the metrics (EER, minDCF, threshold) come from the device score matrix and the two label vectors
+  (``metrics.verification_metrics``: a radix sort and one scan in the native library); the scores are not downloaded and no
+  N-sized label matrix is built.  Equal scores are ordered by their flat (trial-major) index; numpy's default argsort on the
+  CPU path leaves that order open, so the two paths return the same floats whenever no target score equals an impostor score.
+* CPU: the metrics are computed on the host from the flattened score / label arrays.
 """
 import os
 
@@ -22,7 +26,7 @@ from torch.utils.data import DataLoader
 from mvector.data_utils.collate_fn import collate_fn, collate_waveforms
 from mvector.data_utils.featurizer import AudioFeaturizer
 from mvector.data_utils.reader import MVectorDataset
-from mvector.metric.metrics import compute_fnr_fpr, compute_eer, compute_dcf
+from mvector.metric.metrics import compute_fnr_fpr, compute_eer, compute_dcf, verification_metrics
 from mvector.models import build_model
 from mvector.utils.checkpoint import load_pretrained
 from mvector.utils.logger import logger
@@ -103,7 +107,8 @@ class MVectorTrainer(object):
         return torch.cat(feats), torch.cat(labels).numpy().astype(np.int32)
 
     def evaluate(self, resume_model=None, save_image_path=None):
-        """:return: (eer, min_dcf, threshold) -- floats, as the reference"""
+        """:return: (eer, min_dcf, threshold) -- floats, as the reference.  With ``use_gpu`` they are computed on the device, equal scores
+        ordered by their flat index: identical to the host path unless a target score equals an impostor score (module docstring)."""
         use_wave = self._loaders()
         if self.model is None:
             backbone = build_model(input_size=self.audio_featurizer.feature_dim, configs=self.configs)
@@ -123,19 +128,24 @@ class MVectorTrainer(object):
             return -1, -1, -1
         logger.info('开始对比音频特征...')
         if self.use_gpu:
+            # the score matrix stays on the device; the labels go up as two vectors (flat index = trial-major, the order of the reference's loop)
             from mvector import _hip
-            scores = _hip.cosine(trials_features, enroll_features).cpu().numpy()
+            scores = _hip.cosine(trials_features, enroll_features)
+            out = verification_metrics(scores, torch.from_numpy(trials_labels), torch.from_numpy(enroll_labels),
+                                       return_curve=bool(save_image_path))
+            eer, min_dcf, threshold = out[:3]
+            fnr, fpr, thresholds = out[3:] if save_image_path else (None, None, None)
         else:
             a = torch.nn.functional.normalize(trials_features, dim=1)
             b = torch.nn.functional.normalize(enroll_features, dim=1)
             scores = (a @ b.t()).numpy()
-        # flattened trial-major, exactly the order of the reference's loop (trainer.py:452-461)
-        all_score = scores.astype(np.float32).reshape(-1)
-        all_labels = (trials_labels[:, None] == enroll_labels[None, :]).astype(np.int32).reshape(-1)
-        fnr, fpr, thresholds = compute_fnr_fpr(all_score, all_labels)
-        eer, threshold = compute_eer(fnr, fpr, all_score)
-        min_dcf = compute_dcf(fnr, fpr)
-        eer, min_dcf, threshold = float(eer), float(min_dcf), float(threshold)
+            # flattened trial-major, exactly the order of the reference's loop (trainer.py:452-461)
+            all_score = scores.astype(np.float32).reshape(-1)
+            all_labels = (trials_labels[:, None] == enroll_labels[None, :]).astype(np.int32).reshape(-1)
+            fnr, fpr, thresholds = compute_fnr_fpr(all_score, all_labels)
+            eer, threshold = compute_eer(fnr, fpr, all_score)
+            min_dcf = compute_dcf(fnr, fpr)
+            eer, min_dcf, threshold = float(eer), float(min_dcf), float(threshold)
         if save_image_path:
             self._save_curve(save_image_path, thresholds, fnr, fpr, eer, threshold)
         return eer, min_dcf, threshold
