@@ -850,6 +850,44 @@ int mv_wave_prepare_i16(const int16_t* pcm, int64_t pcm_stride, const int64_t* n
                         float target_db, float max_gain_db, float* wav, int64_t wav_stride, int32_t* too_quiet, mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 16-bit PCM of another rate and channel count -> mono float32 waveforms at the target rate (added within ABI 5): the channel mean, the
+ * resampling and the dB normalisation that mvector/predict.py:185-212 does per file on the host (AudioSegment.from_file, resample, normalize).
+ *   x[i] = (float)(sum_c pcm[i, c]) * (1 / 32768) / channels -- the bits of (pcm.astype(float32) / 32768).mean(axis=1);
+ *   g = gcd(dst, src), up = dst / g, down = src / g, half = 10 max(up, down),
+ *   h = scipy.signal.firwin(2 half + 1, 1 / max(up, down), window=('kaiser', 5.0)) * up, designed in fp64 and rounded to fp32 -- the filter of
+ *   scipy.signal.resample_poly(x, up, down) with its defaults;
+ *   y[m] = sum_j x[j] h[m down + half - j up] for 0 <= m < n_out = ceil(n_in up / down): zero padding at both ends, the group delay removed.
+ * Every output is ONE fp32 fmaf chain over its K = ceil((2 half + 1) / up) taps, in the order j = (m down + half) / up downwards: a row's
+ * bits depend on its own samples only -- not on the batch, the stream or the call.  up = down = 1 (a pure down-mix) copies x.
+ * The handle owns the table and no mutable state: one handle may drive several streams at once.
+ * ------------------------------------------------------------------------------------------------ */
+#define MV_RESAMPLER_MAX_RATE 1024 /* largest max(up, down) mv_resampler_create takes */
+typedef struct MvResampler MvResampler;
+typedef struct MvResamplerInfo {
+    int32_t up, down, half, K; /* as defined above */
+    int32_t tile;              /* outputs of a row one workgroup computes (tile edges are row-relative) */
+    int32_t table_in_lds;      /* 0: the ratio's table and source span do not fit into LDS together, the table is read from global memory */
+} MvResamplerInfo;
+/* refused by name: a rate <= 0; max(up, down) > MV_RESAMPLER_MAX_RATE */
+int mv_resampler_create(int32_t src_rate, int32_t dst_rate, MvResampler** out);
+int mv_resampler_destroy(MvResampler* h);
+int mv_resampler_info(const MvResampler* h, MvResamplerInfo* info);
+/* the 2 half + 1 fp32 coefficients in filter order into HOST memory (n must be 2 half + 1; for up = down = 1 the unit impulse) */
+int mv_resampler_taps(const MvResampler* h, float* taps_host, int32_t n);
+int64_t mv_resampler_out_len(const MvResampler* h, int64_t n_in); /* ceil(n_in up / down) */
+size_t mv_resampler_workspace_bytes(const MvResampler* h, int32_t B, int64_t L_in);
+/* pcm: interleaved int16 frames [B, L_in, channels], rows pcm_stride ELEMENTS apart (no alignment beyond int16's is assumed), channels 1 .. 8;
+ * num_frames: device int64 [B] or NULL (= L_in), clamped to [0, L_in].  wav: [B, L_out] fp32 rows wav_stride apart, L_out >=
+ * mv_resampler_out_len(L_in); row b holds its n_out = out_len(num_frames[b]) samples and zeros behind them.  num_out (device int64 [B], may be
+ * NULL) receives n_out.  normalize / target_db / max_gain_db / too_quiet: the dB normalisation of mv_wave_prepare_i16 (same gain formula, same
+ * flags), the mean square taken over the row's n_out resampled samples: per-tile partial sums (fp32 over a thread's <= 4 outputs, fp64 across)
+ * go to the workspace, a second launch adds them in a fixed order and scales the row.  workspace: device memory, 8-byte aligned, of the size the
+ * companion reports; nothing is allocated per call and no workgroup waits for another. */
+int mv_resampler_forward_i16(const MvResampler* h, const int16_t* pcm, int64_t pcm_stride, int32_t channels, const int64_t* num_frames, int32_t B,
+                             int64_t L_in, int32_t normalize, float target_db, float max_gain_db, float* wav, int64_t wav_stride, int64_t L_out,
+                             int64_t* num_out, int32_t* too_quiet, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Speaker diarization behind the embeddings (mvector/infer_utils/speaker_diarization.py; added within ABI 5).
  * Every sum runs in one fixed order: results are bit-identical from run to run and on any stream.
  * ------------------------------------------------------------------------------------------------ */

@@ -142,6 +142,10 @@ class MvEigInfo(ctypes.Structure):
                 ('ub', ctypes.c_double)]
 
 
+class MvResamplerInfo(ctypes.Structure):
+    _fields_ = [('up', c_i32), ('down', c_i32), ('half', c_i32), ('K', c_i32), ('tile', c_i32), ('table_in_lds', c_i32)]
+
+
 class MvVerifCfg(ctypes.Structure):
     _fields_ = [('p_target', ctypes.c_double), ('c_miss', ctypes.c_double), ('c_fa', ctypes.c_double)]
 
@@ -225,6 +229,14 @@ _SIGNATURES = {
     'mv_profile_enable': (c_i32, [c_i32]),
     'mv_profile_read': (c_i32, [c_i32, ctypes.POINTER(c_i32), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), c_i32]),
     'mv_wave_prepare_i16': (c_i32, [c_vp, c_i64, c_vp, c_i32, c_i64, c_i32, c_f32, c_f32, c_vp, c_i64, c_vp, c_vp]),
+    'mv_resampler_create': (c_i32, [c_i32, c_i32, ctypes.POINTER(c_vp)]),
+    'mv_resampler_destroy': (c_i32, [c_vp]),
+    'mv_resampler_info': (c_i32, [c_vp, ctypes.POINTER(MvResamplerInfo)]),
+    'mv_resampler_taps': (c_i32, [c_vp, ctypes.POINTER(c_f32), c_i32]),
+    'mv_resampler_out_len': (c_i64, [c_vp, c_i64]),
+    'mv_resampler_workspace_bytes': (c_sz, [c_vp, c_i32, c_i64]),
+    'mv_resampler_forward_i16': (c_i32, [c_vp, c_vp, c_i64, c_i32, c_vp, c_i32, c_i64, c_i32, c_f32, c_f32, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz,
+                                         c_vp]),
     'mv_asp_pool_f16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
     'mv_sap_pool_f16': (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp]),
     'mv_time_mean_var_f16': (c_i32, [c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
@@ -853,6 +865,63 @@ def wave_prepare(pcm, num_samples=None, target_db=None, max_gain_db=300.0, cdll=
                                    float(target_db or 0.0), float(max_gain_db), wav.data_ptr(), L, flags.data_ptr(), current_stream(pcm)),
           cdll)
     return wav, flags
+
+
+class Resampler:
+    """Handle of the down-mix + polyphase resampler (mv_resampler_*): interleaved int16 PCM at ``src_rate`` -> mono fp32 at ``dst_rate`` with the
+    filter of scipy.signal.resample_poly(x, up, down).  Refused (RuntimeError naming the limit): a rate <= 0, max(up, down) > 1024."""
+
+    def __init__(self, src_rate, dst_rate, cdll=None):
+        self._cdll = cdll or lib()
+        self._h = c_vp()
+        check(self._cdll.mv_resampler_create(int(src_rate), int(dst_rate), ctypes.byref(self._h)), self._cdll)
+        info = MvResamplerInfo()
+        check(self._cdll.mv_resampler_info(self._h, ctypes.byref(info)), self._cdll)
+        self.src_rate, self.dst_rate = int(src_rate), int(dst_rate)
+        self.up, self.down, self.half, self.K, self.tile, self.table_in_lds = (info.up, info.down, info.half, info.K, info.tile,
+                                                                               bool(info.table_in_lds))
+
+    def taps(self):
+        """the 2 * half + 1 fp32 coefficients in filter order (numpy)"""
+        import numpy as np
+        n = 2 * self.half + 1
+        buf = (c_f32 * n)()
+        check(self._cdll.mv_resampler_taps(self._h, buf, n), self._cdll)
+        return np.frombuffer(buf, dtype=np.float32).copy()
+
+    def out_len(self, n):
+        return int(self._cdll.mv_resampler_out_len(self._h, int(n)))
+
+    def __call__(self, pcm, num_frames=None, target_db=None, max_gain_db=300.0):
+        """int16 [B, L] or [B, L, C] (interleaved frames, any row stride) -> (wav [B, out_len(L)] fp32, num_out int64 [B], too_quiet int32 [B])
+        on the caller's stream; ``num_frames`` int64 [B] = the rows' own frame counts, ``target_db`` None = no dB normalisation."""
+        assert pcm.dtype == torch.int16 and pcm.dim() in (2, 3)
+        if pcm.dim() == 2:
+            pcm = pcm.unsqueeze(-1)
+        B, L, C = pcm.shape
+        if B and L and (pcm.stride(2) != 1 or pcm.stride(1) != C or pcm.stride(0) < L * C):
+            pcm = pcm.contiguous()
+        L_out = self.out_len(L)
+        wav = torch.empty((B, L_out), dtype=torch.float32, device=pcm.device)
+        num_out = torch.zeros((B,), dtype=torch.int64, device=pcm.device)
+        flags = torch.zeros((B,), dtype=torch.int32, device=pcm.device)
+        if num_frames is not None:
+            num_frames = num_frames.to(device=pcm.device, dtype=torch.int64).contiguous()
+            if num_frames.shape != (B,):
+                raise ValueError(f'num_frames must have shape ({B},), got {tuple(num_frames.shape)}')
+        nbytes = int(self._cdll.mv_resampler_workspace_bytes(self._h, B, L))
+        ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=pcm.device)   # per call: streams never share it
+        check(self._cdll.mv_resampler_forward_i16(self._h, pcm.data_ptr(), pcm.stride(0) if B and L else L * C, C, _ptr(num_frames), B, L,
+                                                  0 if target_db is None else 1, float(target_db or 0.0), float(max_gain_db), wav.data_ptr(), L_out,
+                                                  L_out, num_out.data_ptr(), flags.data_ptr(), ws.data_ptr(), nbytes, current_stream(pcm)), self._cdll)
+        return wav, num_out, flags
+
+    def __del__(self):
+        try:
+            if getattr(self, '_h', None):
+                self._cdll.mv_resampler_destroy(self._h)
+        except Exception:
+            pass
 
 
 def cosine(a, b, cdll=None):

@@ -97,3 +97,17 @@ def read_pcm16(file):
     if data.dtype != np.int16 or data.ndim != 1:
         return None
     return data, int(sr)
+
+
+def read_pcm16_frames(file):
+    """(int16 frames [frames, channels], sample rate) of ANY 16-bit PCM WAV given by path / file object / bytes -- whatever its rate and channel
+    count --, else None.  The GPU predictor uploads such audio as interleaved int16 and down-mixes, resamples and normalises it on the device
+    (mv_resampler_forward_i16)."""
+    from scipy.io import wavfile as _wavfile
+    try:
+        sr, data = _wavfile.read(io.BytesIO(file) if isinstance(file, (bytes, bytearray)) else file)
+    except Exception:
+        return None
+    if data.dtype != np.int16 or data.ndim not in (1, 2):
+        return None
+    return data.reshape(data.shape[0], -1), int(sr)

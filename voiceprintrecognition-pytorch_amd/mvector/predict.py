@@ -5,6 +5,7 @@ does (predict.py:244-255), moved to the GPU once, featurised there by the fused 
 (``AudioFeaturizer`` no longer runs on the CPU), embedded by the native backbone, and scored by the HIP cosine
 kernel.  With ``use_gpu=False`` everything runs through the torch CPU graphs, as in the reference.
 """
+import math
 import os
 from io import BufferedReader
 
@@ -73,7 +74,10 @@ class MVectorPredictor:
             step = self.configs.dataset_conf.eval_conf.batch_size
             for lo in range(0, len(todo), step):
                 chunk = todo[lo:lo + step]
-                rows = self.predict_batch([self._load_audio(p).samples for p in chunk])
+                if self.device.type == 'cuda' and self._pcm16_frames_batch(chunk) is not None:
+                    rows = self.predict_batch(chunk)   # 16-bit files of another rate / channel count: resampled on the device
+                else:
+                    rows = self.predict_batch([self._load_audio(p).samples for p in chunk])
                 for path, row in zip(chunk, rows):
                     self._gallery.add(os.path.basename(os.path.dirname(path)), path, row)
             self._gallery.save()
@@ -193,6 +197,91 @@ class MVectorPredictor:
             raise ValueError(f'无法将段规范化到{dataset.target_dB}dB，音频增益已经超过max_gain_db (300.0dB)')
         return out
 
+    # ---- 16-bit PCM of other rates / channel counts: down-mix, resampling and normalisation on the device (mv_resampler_*)
+    def _resample_ratio(self, rate):
+        dataset = self.configs.dataset_conf.dataset
+        g = math.gcd(int(dataset.sample_rate), int(rate))
+        return int(dataset.sample_rate) // g, int(rate) // g
+
+    def _pcm16_frames_batch(self, audios_data):
+        """[(int16 frames [n, channels], rate)] for EVERY item when all are paths / bytes of 16-bit PCM WAVs the device resampler takes (1 .. 8
+        channels, max(up, down) <= 1024) and at least one is not mono at the configured rate, else None."""
+        from mvector.data_utils.audio import read_pcm16_frames
+        dataset = self.configs.dataset_conf.dataset
+        out, foreign = [], False
+        for a in audios_data:
+            if not isinstance(a, (str, bytes)):
+                return None
+            got = read_pcm16_frames(a)
+            if got is None or got[1] <= 0 or not 1 <= got[0].shape[1] <= 8 or max(self._resample_ratio(got[1])) > 1024:
+                return None
+            duration = got[0].shape[0] / float(got[1])   # of the source, as _load_audio asserts it before it resamples
+            assert duration >= dataset.min_duration, f'音频太短，最小应该为{dataset.min_duration}s，当前音频为{duration}s'
+            foreign = foreign or got[1] != dataset.sample_rate or got[0].shape[1] != 1
+            out.append(got)
+        return out if foreign else None
+
+    @staticmethod
+    def _resample_groups(frames):
+        """{(rate, channels): [(batch index, frames), ...]} in first-seen order"""
+        groups = {}
+        for i, (f, rate) in enumerate(frames):
+            groups.setdefault((rate, f.shape[1]), []).append((i, f))
+        return groups
+
+    def _resampled_lengths(self, frames):
+        """samples of every item at the configured rate: ceil(n * up / down), from the frame counts alone"""
+        out = []
+        for f, rate in frames:
+            up, down = self._resample_ratio(rate)
+            out.append(-(-f.shape[0] * up // down))
+        return out
+
+    def _resampler(self, rate):
+        from mvector import _hip
+        cache = self.__dict__.setdefault('_resamplers', {})
+        if rate not in cache:
+            cache[rate] = _hip.Resampler(rate, self.configs.dataset_conf.dataset.sample_rate)
+        return cache[rate]
+
+    @torch.no_grad()
+    def _predict_batch_resampled(self, frames, batch_size):
+        """GPU path of predict_batch for 16-bit files that are not all mono at the configured rate: per (rate, channels) group one pinned int16
+        staging buffer, one upload and one call of the group's Resampler (target-rate mono rows: wave_prepare, as the pcm16 path), written into
+        one [B, max n_out] batch; the length ratios come from the frame counts on the host -- nothing waits for the device."""
+        from mvector import _hip
+        dataset = self.configs.dataset_conf.dataset
+        target_db = dataset.target_dB if dataset.use_dB_normalization else None
+        lens = self._resampled_lengths(frames)
+        max_len = max(lens)
+        wav = torch.zeros((len(frames), max_len), dtype=torch.float32, device=self.device)
+        flags = []
+        for (rate, channels), members in self._resample_groups(frames).items():
+            n_in = [f.shape[0] for _, f in members]
+            staging = torch.zeros((len(members), max(n_in), channels), dtype=torch.int16)
+            if torch.cuda.is_available():
+                staging = staging.pin_memory()
+            host = staging.numpy()   # (a view of the pinned buffer: the decoded frames may be read-only arrays)
+            for r, (_, f) in enumerate(members):
+                host[r, :n_in[r]] = f
+            pcm = staging.to(self.device, non_blocking=True)
+            n = torch.tensor(n_in, dtype=torch.int64, device=self.device)
+            if rate == dataset.sample_rate and channels == 1:
+                rows, quiet = _hip.wave_prepare(pcm[:, :, 0], n, target_db)
+            else:
+                rows, _, quiet = self._resampler(rate)(pcm, n, target_db)
+            index = torch.tensor([i for i, _ in members], dtype=torch.int64, device=self.device)
+            wav[index, :rows.shape[1]] = rows
+            flags.append(quiet)
+        ratio = torch.tensor([l / max_len for l in lens], dtype=torch.float32, device=self.device)
+        audio_feature = self._audio_featurizer(wav, ratio)
+        step = max(int(batch_size), 256)
+        features = [self.predictor(audio_feature[i:i + step]).data for i in range(0, len(frames), step)]
+        out = torch.cat(features, dim=0).cpu().numpy()
+        if bool(torch.cat(flags).any().item()):
+            raise ValueError(f'无法将段规范化到{dataset.target_dB}dB，音频增益已经超过max_gain_db (300.0dB)')
+        return out
+
     @torch.no_grad()
     def predict_batch(self, audios_data, sample_rate=16000, batch_size=32):
         """预测一批音频的特征 -> np.ndarray [B, embd_dim] (row order = input order)"""
@@ -202,6 +291,10 @@ class MVectorPredictor:
             if pcms is not None:
                 self._last_batch_path = 'pcm16'
                 return self._predict_batch_pcm16(pcms, batch_size)
+            frames = self._pcm16_frames_batch(audios_data)
+            if frames is not None:
+                self._last_batch_path = 'pcm16_resampled'
+                return self._predict_batch_resampled(frames, batch_size)
         samples = [self._load_audio(audio_data=a, sample_rate=sample_rate).samples for a in audios_data]
         max_len = max(s.shape[0] for s in samples)
         inputs = np.zeros((len(samples), max_len), dtype=np.float32)
