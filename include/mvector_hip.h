@@ -560,6 +560,28 @@ int mv_cosine_f32(const float* a, int32_t n, const float* b, int32_t m, int32_t 
 int mv_l2_normalize_f32(float* x, int32_t n, int32_t dim, mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Speaker search (added within ABI 5): per query the k best gallery rows by cosine similarity, without the [n, m] score matrix.
+ * Replaces the score matrix + np.argmax per query of mvector/predict.py:169-183 (__retrieval).
+ *   q [n, dim], g [m, dim] fp32 rows of any alignment -> scores [n, k] fp32, index [n, k] int32, best candidate in slot 0.
+ * Arithmetic: the score of (query i, row j) is the value mv_cosine_f32(q, n, g, m, dim, ...) writes for that pair -- it compares == as a
+ *   float, or both are NaN (a -0 comes out as +0, a NaN as the quiet NaN 0x7FFFFFFF).  dim is limited to 1 .. 2047, the range in which
+ *   mv_cosine_f32 runs its four-wave kernel; a larger dim is refused with MV_ERR_UNSUPPORTED.
+ * Order: descending by the order-preserving key of the score, in which -0 and +0 are one value and every NaN ranks above +inf (as np.argmax
+ *   and torch.topk treat it); equal keys by the LOWER row index first.  For k > m the slots behind m hold index -1 and score -inf (all of
+ *   them for m == 0).  n == 0 returns MV_OK and touches nothing.  1 <= k <= 64.
+ * The gallery is walked by S slices: slice s takes the rows [16 floor(s T / S), 16 floor((s + 1) T / S)), T = ceil(m / 16); slices_hint > 0
+ *   pins S (tests; at most T and 4096), 0 lets the library choose from the chip.  The result does not depend on S, on the batch a query sits
+ *   in, or on the stream.  Two ordinary launches (slices, then a merge per query); no workgroup waits for another.
+ * workspace: device memory, 8-byte aligned, of the size the companion reports for the same arguments (S * n * k * 8 bytes, independent of m;
+ *   0 for arguments the call refuses).  Neither the workspace nor the outputs need initialising.
+ * Refused with MV_ERR_INVALID_ARGUMENT and a message: a null pointer, negative n or m, k outside 1 .. 64, dim below 1; MV_ERR_WORKSPACE: a
+ *   workspace smaller than reported.
+ * ------------------------------------------------------------------------------------------------ */
+size_t mv_cosine_topk_workspace_bytes(int32_t n, int32_t m, int32_t dim, int32_t k, int32_t slices_hint);
+int mv_cosine_topk_f32(const float* q, int32_t n, const float* g, int32_t m, int32_t dim, int32_t k, float* scores, int32_t* index,
+                       int32_t slices_hint, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Layer-level entry points (same kernels the model forwards launch; exported so that the parity
  * tests can pin each kernel against the oracle layer by layer).
  * ------------------------------------------------------------------------------------------------ */

@@ -17,7 +17,7 @@
 // that x passes through one L2 instead of eight) changes nothing -- 24.3 / 24.7 us warm and 28 us behind a cache flush in both forms, and
 // [2048, 6144] x [192, 6144] takes 8 x the time of 256 rows: the launch is bound by the workgroup's own chain (three dependent load trips + 96
 // fp32 MFMAs per wave, four waves per SIMD), not by operand delivery through the fabric.
-#include "kernels.h"
+#include "cosine_tile.h"
 
 namespace mv {
 
@@ -25,14 +25,6 @@ __device__ __forceinline__ float lin_act(float v, int act) {
     if (act == MV_ACT_RELU) return fmaxf(v, 0.0f);
     if (act == MV_ACT_TANH) return tanhf(v);
     if (act == MV_ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
-    return v;
-}
-
-__device__ __forceinline__ float4v load4_guard(const float* row, int k, int K, bool vec_ok) {
-    if (vec_ok && k + 3 < K) return *reinterpret_cast<const float4v*>(row + k);
-    float4v v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = (k + e < K) ? row[k + e] : 0.0f;
     return v;
 }
 
@@ -73,45 +65,16 @@ __global__ __launch_bounds__(64 * NW) void linear_f32_kernel(const float* x, int
             wb[u] = *reinterpret_cast<const float4v*>(wrow + k0 + u * 16 * NW + 4 * g);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[u][e], wb[u][e], acc, 0, 0, 0);
-            if (cosine) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    sqx += xa[u][e] * xa[u][e];
-                    sqw += wb[u][e] * wb[u][e];
-                }
-            }
-        }
+        for (int u = 0; u < U; ++u) tile_block_step(xa[u], wb[u], acc, sqx, sqw, cosine);
     }
     for (; k0 < K; k0 += 16 * NW) {
-        const int k = k0 + 4 * g;
         float4v xa, wb;
-        // (the choice between the 16-byte load and the guarded one is made per WAVE: decided per lane, both forms run one after the other under
-        //  complementary masks into the same registers, and the second waits -- s_waitcnt vmcnt(0) -- for the first: two round trips per block)
-        if (xvec && wvec && k0 + 16 <= K) {
-            xa = *MV_GLOBAL_PTR(float4v, xrow + k);
-            wb = *MV_GLOBAL_PTR(float4v, wrow + k);
-        } else {
-            xa = load4_guard(xrow, k, K, false);
-            wb = load4_guard(wrow, k, K, false);
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[e], wb[e], acc, 0, 0, 0);
-        if (cosine) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                sqx += xa[e] * xa[e];
-                sqw += wb[e] * wb[e];
-            }
-        }
+        tile_load_block(xrow, wrow, k0, g, K, xvec && wvec, xa, wb);
+        tile_block_step(xa, wb, acc, sqx, sqw, cosine);
     }
     if (cosine) {
-        sqx += __shfl_xor(sqx, 16);
-        sqx += __shfl_xor(sqx, 32);
-        sqw += __shfl_xor(sqw, 16);
-        sqw += __shfl_xor(sqw, 32);
+        sqx = tile_norm_fold(sqx);
+        sqw = tile_norm_fold(sqw);
         if (g == 0) {
             nrm[0][wave][i] = sqx;
             nrm[1][wave][i] = sqw;
@@ -125,18 +88,7 @@ __global__ __launch_bounds__(64 * NW) void linear_f32_kernel(const float* x, int
         const int r = tid >> 4, c = tid & 15;
         const int b = b0 + r, o = o0 + c;
         if (b < B && o < O) {
-            float v = 0.0f, sx = 0.0f, sw = 0.0f;
-#pragma unroll
-            for (int q = 0; q < NW; ++q) {
-                v += red[q][r][c];
-                sx += nrm[0][q][r];
-                sw += nrm[1][q][c];
-            }
-            if (cosine) {
-                const float nx = sqrtf(sx);
-                const float nw = sqrtf(sw);
-                v = v / (fmaxf(nx, 1.17549435e-38f) * fmaxf(nw, 1.17549435e-38f));
-            }
+            float v = tile_finish<NW>(red, nrm, r, c, cosine);
             if (bias != nullptr) v += bias[o];
             y[(int64_t)b * ldy + o] = lin_act(v, act);
         }

@@ -210,6 +210,8 @@ _SIGNATURES = {
     'mv_model_forward': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_sz, c_vp]),
     'mv_cosine_f32': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_vp, c_vp]),
     'mv_l2_normalize_f32': (c_i32, [c_vp, c_i32, c_i32, c_vp]),
+    'mv_cosine_topk_workspace_bytes': (c_sz, [c_i32, c_i32, c_i32, c_i32, c_i32]),
+    'mv_cosine_topk_f32': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
     'mv_conv1d_packed_elems': (c_i64, [c_i32, c_i32, c_i32]),
     'mv_conv1d_pack_weight': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'mv_conv1d_forward': (c_i32, [ctypes.POINTER(MvConv1dDesc), c_vp]),
@@ -935,6 +937,28 @@ def cosine(a, b, cdll=None):
         check(cdll.mv_cosine_f32(a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], out.data_ptr(),
                                  current_stream(a)), cdll)
     return out
+
+
+def cosine_topk(q, g, k, slices_hint=0, cdll=None, to_host=False):
+    """[N, D] queries x [M, D] gallery -> (scores fp32 [N, k], index int32 [N, k]) on the device of ``q``: per query the ``k`` best rows of
+    ``cosine(q, g)`` -- the same score bits -- best first, equal scores by the lower row first, NaN above +inf; slots behind M hold
+    (-inf, -1).  The [N, M] matrix is never built (mv_cosine_topk_f32).  ``slices_hint`` pins the number of gallery slices (tests).
+    ``to_host``: the two as numpy arrays -- they share one device buffer, so both come down in one transfer."""
+    cdll = cdll or lib()
+    q = q.to(torch.float32).contiguous()
+    g = g.to(device=q.device, dtype=torch.float32).contiguous()
+    assert q.dim() == 2 and g.dim() == 2 and q.shape[1] == g.shape[1]
+    n, m, dim, k = q.shape[0], g.shape[0], q.shape[1], int(k)
+    out = torch.empty((2, n, max(k, 0)), dtype=torch.int32, device=q.device)
+    scores, index = out[0].view(torch.float32), out[1]
+    nbytes = int(cdll.mv_cosine_topk_workspace_bytes(n, m, dim, k, int(slices_hint)))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=q.device)
+    check(cdll.mv_cosine_topk_f32(q.data_ptr(), n, g.data_ptr(), m, dim, k, scores.data_ptr(), index.data_ptr(), int(slices_hint), ws.data_ptr(),
+                                  nbytes, current_stream(q)), cdll)
+    if to_host:
+        host = out.cpu().numpy()
+        return host[0].view('float32'), host[1]
+    return scores, index
 
 
 def wave_chunks(wav, start, length, chunk_len, target_db=None, max_gain_db=300.0, cdll=None):

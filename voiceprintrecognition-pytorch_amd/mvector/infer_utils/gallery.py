@@ -20,6 +20,32 @@ import shutil
 import numpy as np
 
 INDEX_NAME = 'audio_indexes.bin'
+MAX_TOP_K = 64   # of mv_cosine_topk_f32
+
+
+def sort_keys(scores):
+    """float32 array -> uint32 keys in the order of the scores: -0 and +0 share a key, every NaN sits above +inf (csrc/order_key.h: sort_key)"""
+    u = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32)
+    u = np.where(u == 0x80000000, np.uint32(0), u)
+    key = np.where(u & 0x80000000 != 0, ~u, u | np.uint32(0x80000000))
+    return np.where((u & 0x7FFFFFFF) > 0x7F800000, np.uint32(0xFFFFFFFF), key).astype(np.uint32)
+
+
+def top_k_of_scores(scores, k):
+    """[n, m] float32 score matrix -> (scores [n, k] float32, index [n, k] int32), the order rule of mv_cosine_topk_f32 on the host: best
+    first by key (sort_keys), equal keys by the lower column first, slots behind m hold (-inf, -1)."""
+    scores = np.ascontiguousarray(scores, dtype=np.float32)
+    n, m = scores.shape
+    out_s = np.full((n, k), -np.inf, dtype=np.float32)
+    out_i = np.full((n, k), -1, dtype=np.int32)
+    if n and m:
+        col = np.arange(m, dtype=np.uint64)
+        word = (sort_keys(scores).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - col)[None, :]   # one unsigned order for both
+        take = min(k, m)
+        best = np.argsort(word, axis=1)[:, ::-1][:, :take]
+        out_i[:, :take] = best
+        out_s[:, :take] = np.take_along_axis(scores, best, axis=1)
+    return out_s, out_i
 
 
 class SpeakerGallery:
@@ -163,3 +189,24 @@ class DeviceGallery:
 
     def matrix(self):
         return self.sums[:len(self.users)]
+
+    def search(self, queries, k, to_host=False):
+        """queries [N, D] (or [D]) on the gallery's device -> (scores fp32 [N, k], index int32 [N, k]): per query the k best users by
+        cosine similarity, best first, equal scores by the lower row first, NaN above +inf, (-inf, -1) behind the number of users;
+        ``users[index]`` names them.  Device tensors: mv_cosine_topk_f32, no [N, users] matrix.  CPU tensors: the same rule restated in numpy.
+        ``to_host``: numpy arrays instead of tensors (from the device: one transfer for both)."""
+        import torch
+        assert 1 <= int(k) <= MAX_TOP_K, f'k outside 1 .. {MAX_TOP_K}'
+        q = queries.reshape(-1, queries.shape[-1]).to(torch.float32)
+        if q.is_cuda:
+            from mvector import _hip
+            return _hip.cosine_topk(q, self.matrix(), int(k), to_host=to_host)
+        qn, gn = q.numpy(), self.matrix().numpy()
+        tiny = np.float32(1.17549435e-38)
+        with np.errstate(invalid='ignore', over='ignore'):
+            # (row by row, not one matrix product: a BLAS call sums different columns in different orders, and a score must depend on its
+            #  own pair of rows alone -- equal rows tie exactly, one query alone gets the answer it gets in a batch)
+            dots = np.stack([(gn * row).sum(axis=1) for row in qn]) if len(qn) else np.zeros((0, len(gn)), dtype=np.float32)
+            norms = np.maximum(np.linalg.norm(qn, axis=1), tiny)[:, None] * np.maximum(np.linalg.norm(gn, axis=1), tiny)[None, :]
+            scores, index = top_k_of_scores(dots / norms, int(k))
+        return (scores, index) if to_host else (torch.from_numpy(scores), torch.from_numpy(index))

@@ -106,20 +106,40 @@ class MVectorPredictor:
 
     def _best_matches(self, embeddings):
         """[name, score] of the best enrolled user per query row, or [None, None] below the threshold.  ``embeddings``: array
-        or (GPU predictor) a device tensor, which is scored against the device-resident gallery through mv_cosine_f32."""
+        or (GPU predictor) a device tensor, which is searched against the device-resident gallery by mv_cosine_topk_f32: the scores are
+        those of mv_cosine_f32 and the first maximum wins, as np.argmax picks it, but only one score and one index per query come down."""
         if getattr(self, '_device_gallery', None) is not None:
-            from mvector import _hip
             users = self._device_gallery.users
             q = embeddings if torch.is_tensor(embeddings) else torch.as_tensor(np.atleast_2d(np.asarray(embeddings, dtype=np.float32)))
-            scores = _hip.cosine(q.to(self.device).reshape(-1, q.shape[-1]), self._device_gallery.matrix()).cpu().numpy()
-        else:
-            users, means = self._gallery.user_means()
-            scores = self._cosine(np.atleast_2d(np.asarray(embeddings, dtype=np.float32)), means)
+            scores, index = self._device_gallery.search(q.to(self.device), 1, to_host=True)
+            return [[users[i], round(float(s), 5)] if i >= 0 and s >= self.threshold else [None, None] for s, i in zip(scores[:, 0], index[:, 0])]
+        users, means = self._gallery.user_means()
+        scores = self._cosine(np.atleast_2d(np.asarray(embeddings, dtype=np.float32)), means)
         out = []
         for row in scores:
             best = int(np.argmax(row))
             out.append([users[best], round(float(row[best]), 5)] if row[best] >= self.threshold else [None, None])
         return out
+
+    def _top_matches(self, embeddings, top_k):
+        """per query row [[name, score], ...] of the min(top_k, users) best enrolled users, best first (equal scores: the user enrolled first),
+        scores rounded as ``_best_matches`` rounds them, no threshold"""
+        if getattr(self, '_device_gallery', None) is not None:
+            users = self._device_gallery.users
+            k = min(int(top_k), len(users))
+            if k < 1:
+                return [[] for _ in range(embeddings.reshape(-1, embeddings.shape[-1]).shape[0])]
+            q = embeddings if torch.is_tensor(embeddings) else torch.as_tensor(np.atleast_2d(np.asarray(embeddings, dtype=np.float32)))
+            scores, index = self._device_gallery.search(q.to(self.device), k, to_host=True)
+        else:
+            from mvector.infer_utils.gallery import top_k_of_scores
+            users, means = self._gallery.user_means()
+            queries = np.atleast_2d(np.asarray(embeddings, dtype=np.float32))
+            k = min(int(top_k), len(users))
+            if k < 1:
+                return [[] for _ in range(queries.shape[0])]
+            scores, index = top_k_of_scores(self._cosine(queries, means), k)
+        return [[[users[i], round(float(s), 5)] for s, i in zip(srow, irow)] for srow, irow in zip(scores, index)]
 
     # ------------------------------------------------------------------ audio in
     def _load_audio(self, audio_data, sample_rate=16000):
@@ -333,6 +353,24 @@ class MVectorPredictor:
         if threshold:
             self.threshold = threshold
         return self._best_matches(self._embed(audio_data, sample_rate=sample_rate))[0]
+
+    def recognition_batch(self, audios_data, threshold=None, sample_rate=16000, batch_size=32):
+        """一批音频的声纹识别 -> one [user name or None, score or None] per item, exactly what ``recognition`` answers for each.
+        Every item is embedded as ``recognition`` embeds it (one at a time: the padded batches of ``predict_batch`` prepare the audio by other
+        arithmetic -- on the device from int16, with length ratios -- and their scores differ from ``recognition``'s in the last rounded digit,
+        which near the threshold is another answer); the embeddings stay on the predictor's device, where one search takes them all, so a
+        batch costs one synchronisation and one download of B scores and indices instead of one of each per item.  ``batch_size`` is accepted
+        for the call shape of ``predict_batch`` and not used."""
+        if threshold:
+            self.threshold = threshold
+        if len(audios_data) == 0:
+            return []
+        return self._best_matches(torch.cat([self._embed(a, sample_rate=sample_rate) for a in audios_data], dim=0))
+
+    def search(self, audio_data, top_k=5, sample_rate=16000):
+        """声纹检索 -> [[user name, score], ...]: the min(top_k, users) most similar enrolled users, best first, no threshold applied
+        (GPU predictor: top_k <= 64, the limit of mv_cosine_topk_f32)"""
+        return self._top_matches(self._embed(audio_data, sample_rate=sample_rate), top_k)[0]
 
     def get_users(self):
         """One entry per enrolled audio, as the reference returns its ``users_name`` list."""
