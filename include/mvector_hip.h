@@ -582,6 +582,49 @@ int mv_cosine_topk_f32(const float* q, int32_t n, const float* g, int32_t m, int
                        int32_t slices_hint, void* workspace, size_t workspace_bytes, mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cohort score normalisation (added within ABI 5): Z-, T-, S-norm and adaptive S-norm of a trials x enrolments score matrix.
+ *
+ * mv_cohort_stats_f32: x [n, dim], cohort [m, dim] fp32 rows -> mean [n], std [n] fp32 of each row's top_n cohort scores.
+ *   Cohort scores: the score of (x_i, cohort_j) is the float mv_cosine_f32(x, n, cohort, m, dim, ...) writes for that pair, bit for bit
+ *     (the same launcher writes them, chunk by chunk, into the workspace).
+ *   Selection: the N' = min(top_n, m) largest of the row by the order-preserving key of the score, in which -0 and +0 are one value and
+ *     every NaN ranks above +inf; equal keys by the LOWER cohort index first (equal keys are equal values: the rule only fixes which
+ *     entries are summed, the statistics do not depend on it).
+ *   Statistics: mean = sum x / N', std = sqrt(sum (x - mean)^2 / N') (population form, two passes), accumulated in fp64 in one fixed order
+ *     -- every thread of the row's workgroup adds the kept entries of its own contiguous index segment in ascending order, the partial sums
+ *     are folded by a halving tree -- and rounded once to fp32.  No floating-point atomics.  The order depends on m alone (through the
+ *     workgroup size of its tier), never on n, on the chunking or on the stream.  A NaN among the selected scores gives NaN / NaN for that row
+ *     only; N' equal values v give mean == v and std == 0 exactly.
+ *   The n rows are walked in chunks of R rows: R = rows_hint when positive (tests), else the library's choice, which keeps the chunk's
+ *     R * m scores well inside the Infinity Cache.  The result does not depend on R.  Two ordinary launches per chunk; no workgroup waits for
+ *     another, nothing is allocated, the call does not synchronise.
+ *   workspace: device memory, 4-byte aligned, of the size the companion reports for the same arguments: R * m * 4 bytes, at most 64 MiB
+ *     whatever n is unless rows_hint asks for more (0 for arguments the call refuses).  It needs no initialising.
+ *   Refused with MV_ERR_INVALID_ARGUMENT and a message: a null pointer, negative n, m < 1, top_n < 1, dim < 1; MV_ERR_UNSUPPORTED:
+ *     m > MV_COHORT_MAX_ROWS; MV_ERR_WORKSPACE: a workspace smaller than reported.  n == 0 returns MV_OK and touches nothing.
+ *
+ * mv_score_norm_f32: scores [n_trials, n_enroll] fp32 (contiguous) -> out of the same shape; out == scores is allowed.  For trial t,
+ *   enrolment e and raw score s, each operation one correctly rounded fp32 operation in this order (no contraction, no reciprocal), so the
+ *   result equals the same expression in numpy.float32 bit for bit; std == 0 is not guarded:
+ *     MV_SNORM_Z: (s - enroll_mean[e]) / enroll_std[e]
+ *     MV_SNORM_T: (s - trial_mean[t]) / trial_std[t]
+ *     MV_SNORM_S: 0.5f * ((s - trial_mean[t]) / trial_std[t] + (s - enroll_mean[e]) / enroll_std[e])
+ *   With statistics of top_n < m this is the adaptive form (AS-norm), with top_n >= m plain S-norm.  The statistics of the side a mode does
+ *   not use may be null.  n_trials * n_enroll <= 2^31 - 1.  One launch; an empty matrix touches nothing.
+ *   Refused with MV_ERR_INVALID_ARGUMENT and a message: a null pointer for a required argument, negative sizes, more than 2^31 - 1
+ *   elements, an unknown mode.
+ * ------------------------------------------------------------------------------------------------ */
+#define MV_SNORM_S 0
+#define MV_SNORM_Z 1
+#define MV_SNORM_T 2
+#define MV_COHORT_MAX_ROWS 32768
+size_t mv_cohort_stats_workspace_bytes(int32_t n, int32_t m, int32_t dim, int32_t rows_hint);
+int mv_cohort_stats_f32(const float* x, int32_t n, const float* cohort, int32_t m, int32_t dim, int32_t top_n, float* mean, float* std,
+                        int32_t rows_hint, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+int mv_score_norm_f32(const float* scores, int64_t n_trials, int64_t n_enroll, const float* trial_mean, const float* trial_std,
+                      const float* enroll_mean, const float* enroll_std, int32_t mode, float* out, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Layer-level entry points (same kernels the model forwards launch; exported so that the parity
  * tests can pin each kernel against the oracle layer by layer).
  * ------------------------------------------------------------------------------------------------ */

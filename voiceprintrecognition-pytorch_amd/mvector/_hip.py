@@ -296,6 +296,9 @@ _SIGNATURES = {
     'mv_verif_metrics_workspace_bytes': (c_sz, [c_i64, c_i64]),
     'mv_verif_metrics_f32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, ctypes.POINTER(MvVerifCfg), ctypes.POINTER(MvVerifResult), c_vp, c_vp,
                                      c_vp, c_sz, c_vp]),
+    'mv_cohort_stats_workspace_bytes': (c_sz, [c_i32, c_i32, c_i32, c_i32]),
+    'mv_cohort_stats_f32': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
+    'mv_score_norm_f32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -959,6 +962,54 @@ def cosine_topk(q, g, k, slices_hint=0, cdll=None, to_host=False):
         host = out.cpu().numpy()
         return host[0].view('float32'), host[1]
     return scores, index
+
+
+MV_SNORM_S, MV_SNORM_Z, MV_SNORM_T = 0, 1, 2
+MV_COHORT_MAX_ROWS = 32768
+SCORE_NORM_MODES = {'s': MV_SNORM_S, 'z': MV_SNORM_Z, 't': MV_SNORM_T}
+
+
+def cohort_stats(x, cohort, top_n, rows_hint=0, cdll=None):
+    """[N, D] embeddings x [M, D] cohort -> (mean, std), both fp32 [N], on the device of ``x``: the statistics of each row's
+    min(top_n, M) largest cohort scores -- the scores are those of ``cosine(x, cohort)`` bit for bit, the sums run in fp64 in one fixed order
+    (mv_cohort_stats_f32).  The [N, M] matrix is never built: the rows go through a workspace of R rows.  ``rows_hint`` pins R (tests)."""
+    cdll = cdll or lib()
+    x = x.to(torch.float32).contiguous()
+    cohort = cohort.to(device=x.device, dtype=torch.float32).contiguous()
+    assert x.dim() == 2 and cohort.dim() == 2 and x.shape[1] == cohort.shape[1]
+    n, m, dim = x.shape[0], cohort.shape[0], x.shape[1]
+    out = torch.empty((2, n), dtype=torch.float32, device=x.device)
+    nbytes = int(cdll.mv_cohort_stats_workspace_bytes(n, m, dim, int(rows_hint)))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=x.device)
+    check(cdll.mv_cohort_stats_f32(x.data_ptr(), n, cohort.data_ptr(), m, dim, int(top_n), out[0].data_ptr(), out[1].data_ptr(), int(rows_hint),
+                                   ws.data_ptr(), nbytes, current_stream(x)), cdll)
+    return out[0], out[1]
+
+
+def score_norm(scores, trial_stats, enroll_stats, mode='s', out=None, cdll=None):
+    """scores [T, E] fp32 with ``trial_stats`` = (mean [T], std [T]) and ``enroll_stats`` = (mean [E], std [E]) -> the normalised matrix
+    (mv_score_norm_f32): mode 'z' (s - mean_e) / std_e, 't' (s - mean_t) / std_t, 's' half their sum -- the numpy.float32 expression bit for
+    bit.  The statistics of the side a mode does not use may be None.  ``out`` may be ``scores`` itself (in place)."""
+    cdll = cdll or lib()
+    if mode not in SCORE_NORM_MODES:
+        raise ValueError(f"score_norm: mode {mode!r} is not one of 's', 'z', 't'")
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.is_contiguous()
+    n_t, n_e = scores.shape
+
+    def side(stats, count, what):
+        if stats is None:
+            return None, None
+        mean, std = (s.to(device=scores.device, dtype=torch.float32).contiguous() for s in stats)
+        assert mean.shape == (count,) and std.shape == (count,), f'score_norm: {what} statistics are not [{count}]'
+        return mean, std
+    tm, ts = side(trial_stats, n_t, 'trial')
+    em, es = side(enroll_stats, n_e, 'enrolment')
+    if out is None:
+        out = torch.empty_like(scores)
+    assert out.shape == scores.shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == scores.device
+    check(cdll.mv_score_norm_f32(scores.data_ptr(), n_t, n_e, _ptr(tm), _ptr(ts), _ptr(em), _ptr(es), SCORE_NORM_MODES[mode], out.data_ptr(),
+                                 current_stream(scores)), cdll)
+    return out
 
 
 def wave_chunks(wav, start, length, chunk_len, target_db=None, max_gain_db=300.0, cdll=None):

@@ -336,6 +336,17 @@ class MVectorPredictor:
         feature2 = self.predict(audio_data2)
         return np.dot(feature1, feature2) / (np.linalg.norm(feature1) * np.linalg.norm(feature2))
 
+    def contrast_normalized(self, audio_data1, audio_data2, normalizer):
+        """``contrast`` with cohort score normalisation -> float: the cosine of the two embeddings, normalised by ``normalizer`` (a
+        ``metric.score_norm.ScoreNormalizer``; mode 's' with the first audio as the trial, the second as the enrolment).  On the GPU predictor
+        the embeddings stay on the device: mv_cosine_f32, mv_cohort_stats_f32 per side and mv_score_norm_f32, one float comes down."""
+        from mvector.metric.score_norm import cosine_scores
+        e1, e2 = self._embed(audio_data1), self._embed(audio_data2)
+        if self.device.type != 'cuda':
+            e1, e2 = e1.numpy(), e2.numpy()
+        score = normalizer.normalize(cosine_scores(e1, e2), trial_embeddings=e1, enroll_embeddings=e2)
+        return float(score[0, 0])
+
     def register(self, audio_data, user_name: str, sample_rate=16000):
         """声纹注册"""
         audio_segment = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)

@@ -150,6 +150,59 @@ class MVectorTrainer(object):
             self._save_curve(save_image_path, thresholds, fnr, fpr, eer, threshold)
         return eer, min_dcf, threshold
 
+    def evaluate_normalized(self, cohort_list, top_n=300, mode='s', resume_model=None, save_image_path=None, per_speaker=True):
+        """``evaluate`` with cohort score normalisation (``metric.score_norm``: Z-, T-, S-norm, adaptive with ``top_n`` below the cohort size)
+        in front of the metrics -> (eer, min_dcf, threshold).  ``cohort_list`` is a data list in the format of ``enroll_list``; its utterances
+        are embedded as the other two lists are and, with ``per_speaker``, reduced to one mean embedding per speaker.  With ``use_gpu`` the
+        cohort stays on the device, the raw score matrix of ``evaluate`` is normalised in place there (``mv_cohort_stats_f32`` per side, then
+        ``mv_score_norm_f32``) and goes to ``verification_metrics`` as it is; on the CPU the same definition runs in numpy."""
+        from mvector.metric.score_norm import ScoreNormalizer, cohort_means, cosine_scores
+        ds_conf = self.configs.dataset_conf
+        use_wave = self._loaders()
+        if use_wave and self._has_npy(cohort_list):
+            raise ValueError('evaluate_normalized: the cohort list holds .npy features while the enrolment and trial lists hold audio')
+        args = dict(ds_conf.get('dataset', {}))
+        args['max_duration'] = ds_conf.eval_conf.max_duration
+        cohort_set = MVectorDataset(data_list_path=cohort_list, audio_featurizer=self.audio_featurizer, mode='eval', return_waveform=use_wave, **args)
+        cohort_loader = DataLoader(dataset=cohort_set, collate_fn=collate_waveforms if use_wave else collate_fn, shuffle=False,
+                                   batch_size=ds_conf.eval_conf.batch_size, **dict(ds_conf.get('dataLoader', {})))
+        eval_model = self._eval_model(resume_model)
+        enroll_features, enroll_labels = self._embed(self.enroll_loader, eval_model, use_wave)
+        trials_features, trials_labels = self._embed(self.trials_loader, eval_model, use_wave)
+        cohort_features, cohort_labels = self._embed(cohort_loader, eval_model, use_wave)
+        if self.stop_eval:
+            return -1, -1, -1
+        if per_speaker:
+            cohort_features = torch.from_numpy(cohort_means(cohort_features, cohort_labels)).to(self.device)
+        normalizer = ScoreNormalizer(cohort_features if self.use_gpu else cohort_features.numpy(), top_n=top_n, mode=mode)
+        if self.use_gpu:
+            scores = cosine_scores(trials_features, enroll_features)
+            scores = normalizer.normalize(scores, trial_embeddings=trials_features, enroll_embeddings=enroll_features, out=scores)
+        else:
+            a = torch.nn.functional.normalize(trials_features, dim=1)
+            b = torch.nn.functional.normalize(enroll_features, dim=1)
+            scores = normalizer.normalize((a @ b.t()).numpy().astype(np.float32), trial_embeddings=trials_features, enroll_embeddings=enroll_features)
+        out = verification_metrics(scores, trials_labels, enroll_labels, return_curve=bool(save_image_path))
+        eer, min_dcf, threshold = out[:3]
+        if save_image_path:
+            self._save_curve(save_image_path, out[5], out[3], out[4], eer, threshold)
+        return eer, min_dcf, threshold
+
+    def _eval_model(self, resume_model):
+        """the backbone in eval mode on the trainer's device, weights from ``resume_model`` (a file or a folder with model.pth), as
+        ``evaluate`` prepares it"""
+        if self.model is None:
+            backbone = build_model(input_size=self.audio_featurizer.feature_dim, configs=self.configs)
+            self.model = torch.nn.Sequential(backbone)
+        self.model.to(self.device)
+        if resume_model is not None:
+            if os.path.isdir(resume_model):
+                resume_model = os.path.join(resume_model, 'model.pth')
+            assert os.path.exists(resume_model), f'{resume_model} 模型不存在！'
+            self.model = load_pretrained(self.model, resume_model, use_gpu=self.use_gpu)
+        self.model.eval()
+        return self.model if len(self.model) == 1 else self.model[0]
+
     @staticmethod
     def _save_curve(save_image_path, thresholds, fnr, fpr, eer, threshold):
         """the reference plots FNR / FPR over the threshold (trainer.py:470-481); matplotlib is optional here"""
