@@ -821,6 +821,20 @@ int32_t mv_conv1d_grouped_native(int32_t cout, int32_t cin, int32_t k, int32_t g
 int64_t mv_conv1d_grouped_packed_elems(int32_t cout, int32_t cin, int32_t k, int32_t groups);
 int mv_conv1d_pack_weight_grouped(const float* w, int32_t cout, int32_t cin, int32_t k, int32_t groups, void* packed_f16, mv_stream_t stream);
 int mv_conv1d_forward_grouped(const MvConv1dDesc* d, int32_t groups, mv_stream_t stream);
+/* Which kernels mv_conv1d_forward / mv_conv1d_forward_grouped (groups as passed there) would launch for `d`, without launching (additive since
+ * ABI 5).  cus = 0 plans for the current device; any other value for a chip of that many compute units.  The descriptor goes through the same checks
+ * and the same plan as a forward call, so a refused descriptor returns that call's error code and message.  The names are the rows of csrc/conv1d.hip's
+ * kernel table as spelled there ("CK_GLDS_128", ...), static strings owned by the library; in_stats_kernel is "CK_IN_STATS" when the input statistics
+ * run as a launch of their own in front of the conv, tail_kernel the kernel of the ring walk's last partial round (tail_nv tiles, each cut
+ * tail_split x tail_split); both are "" when there is no such launch.  n_tiles x co_tiles: the main kernel's tiles over rows and output channels;
+ * grid: its workgroups. */
+typedef struct MvConv1dPlanInfo {
+    const char* kernel;
+    const char* in_stats_kernel;
+    const char* tail_kernel;
+    int32_t n_tiles, co_tiles, grid, tail_nv, tail_split;
+} MvConv1dPlanInfo;
+int mv_conv1d_plan_info(const MvConv1dDesc* d, int32_t groups, int32_t cus, MvConv1dPlanInfo* out);
 /* floats in one partial-statistics buffer, and the reduction of the partial rows to per-utterance mean[b, c] (and
  * std[b, c] = sqrt(max(E[(y - mean)^2], clamp_eps)) when stat_sq / std are given).  `shift` = the BatchNorm shift passed to the
  * conv (the moments are taken about it), NULL if the conv had none. */

@@ -44,10 +44,14 @@ def desc(x, ldx, packed, bias, scale, shift, y, ldy, B, T, cin, cout, k=1, dil=1
     return d
 
 
-def grouped_conv_case(cdll, device, B, T, cin, cout, groups, k=1, dil=1, tile=0, persist_blocks=0, seed=0, extra_ld=8):
+def grouped_conv_case(cdll, device, B, T, cin, cout, groups, k=1, dil=1, tile=0, persist_blocks=0, seed=0, extra_ld=8, bound=False,
+                      expect_kernel=None, plan_cus=None, log=None):
     """A grouped TDNNBlock layer through mv_conv1d_forward_grouped against F.conv1d(groups=g) on the fp16-rounded operands.  A native layer
     must also give, bit for bit, the g dense layers over the groups' slices of x (every output element: bias + the same K sum in the same
-    order).  Returns whether the layer ran native."""
+    order).  Returns whether the layer ran native.
+    expect_kernel: the row of conv1d's kernel table the layer must plan to on this device (mv_conv1d_plan_info), asserted before the launch.
+    bound: also hold every element to the per-element bound of tests/conv1d_cases.py against fp64 (k = 1).
+    plan_cus: launch nothing; return the plan info of the layer's descriptor on a chip of that many compute units."""
     g = torch.Generator().manual_seed(seed)
     cin_g, cout_g = cin // groups, cout // groups
     ldx, ldy = cin + extra_ld, cout + extra_ld
@@ -61,6 +65,11 @@ def grouped_conv_case(cdll, device, B, T, cin, cout, groups, k=1, dil=1, tile=0,
     native = bool(cdll.mv_conv1d_grouped_native(cout, cin, k, groups))
     packed = pack_grouped(cdll, wd, groups)
     d = desc(xd, ldx, packed, bd, sd, td, y, ldy, B, T, cin, cout, k, dil, tile, persist_blocks)
+    if plan_cus is not None:
+        return _hip.conv1d_plan_info(d, groups, plan_cus, cdll)
+    plan = _hip.conv1d_plan_info(d, groups, 0, cdll)
+    if expect_kernel is not None:
+        assert plan['kernel'] == expect_kernel, plan
     _hip.check(cdll.mv_conv1d_forward_grouped(ctypes.byref(d), groups, _stream(xd)), cdll)
     _sync(device)
     got = y.cpu()
@@ -69,7 +78,14 @@ def grouped_conv_case(cdll, device, B, T, cin, cout, groups, k=1, dil=1, tile=0,
         xg = xd[..., :cin].double().reshape(B * T, groups, cin_g).transpose(0, 1)                # [g, rows, cin_g]
         ref = torch.bmm(xg, wd.half().double().reshape(groups, cout_g, cin_g).transpose(1, 2))   # [g, rows, cout_g]
         ref = ref.transpose(0, 1).reshape(B, T, cout).cpu() + bias.double()
+        if bound:   # S = sum |x| |w| + |bias| by the same product on absolute values; the epilogue and the bound are conv1d_cases.bound's
+            import conv1d_cases
+            S = torch.bmm(xg.abs(), wd.half().double().abs().reshape(groups, cout_g, cin_g).transpose(1, 2))
+            S = S.transpose(0, 1).reshape(B, T, cout).cpu() + bias.double().abs()
+            ref64, bnd = conv1d_cases.bound(ref, S, cin_g * k, _hip.MV_ACT_RELU, scale, shift, _hip.MV_ACT_NONE, None, False)
+            conv1d_cases.assert_ratio(got[..., :cout], ref64, bnd, plan['kernel'], f'grouped g={groups} {cin}->{cout}', log)
     else:
+        assert not bound, 'the per-element bound is wired for k = 1'
         pad = dil * (k - 1) // 2
         xin = F.pad(x[..., :cin].double().transpose(1, 2), (pad, pad), mode='reflect')
         ref = F.conv1d(xin, w.half().double(), bias.double(), dilation=dil, groups=groups).transpose(1, 2)

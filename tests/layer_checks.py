@@ -25,33 +25,88 @@ def pack_weight(cdll, w):
     return packed
 
 
-def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, pad_mode='reflect', valid=False,
-                x_f32=False, y_f32=False, with_x2=False, in_affine=False, pre_act=1, affine=True, post_act=0,
-                row_bias=False, gate_seg=0, extra_ld=8, second_out=False, tile=0, stats=0, in_stats=False, seed=0, persist_blocks=0, clock_probe=False, return_y=False, out_gain=1.0):
+def conv1d_operands(B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, pad_mode='reflect', valid=False, x_f32=False, y_f32=False, with_x2=False,
+                    in_affine=False, pre_act=1, affine=True, post_act=0, row_bias=False, gate_seg=0, extra_ld=8, second_out=False, seed=0, out_gain=1.0,
+                    **launch_only):
+    """The seeded fp32 operands of a conv1d_case on the CPU, by the case's keywords (tile, stats, ... only shape the launch): what conv1d_case
+    uploads, and what the CPU self-checks of tests/conv1d_cases.py evaluate without a launch."""
+    from types import SimpleNamespace
     g = torch.Generator().manual_seed(seed)
     rn = lambda *s: torch.randn(*s, generator=g)
-    ldx = cin + extra_ld
-    xfull = rn(B, T, ldx)
-    x2full = rn(B, T, ldx) if with_x2 else None
-    w = rn(cout, cin, k) * (2.0 / (cin * k)) ** 0.5
-    bias = rn(cout) * 0.1
-    scale = (torch.rand(cout, generator=g) + 0.5) * out_gain if affine else None   # out_gain: drives the outputs beyond the fp16 range (saturation at +-65504)
-    shift = rn(cout) * 0.1 if affine else None
-    in_s = torch.rand(cin, generator=g) + 0.5 if in_affine else None
-    in_t = rn(cin) * 0.2 if in_affine else None
-    pad = 0 if valid else dil * (k - 1) // 2
-    T_out = (T + 2 * pad - dil * (k - 1) - 1) // stride + 1
-    rb = rn(B, cout) * 0.3 if row_bias else None
-    nseg = -(-T_out // gate_seg) if gate_seg else 0
-    gate = torch.rand(B, nseg, cout, generator=g) if gate_seg else None
-
+    o = SimpleNamespace(B=B, T=T, cin=cin, cout=cout, k=k, dil=dil, stride=stride, pad_mode=pad_mode, x_f32=x_f32, y_f32=y_f32, with_x2=with_x2,
+                        in_affine=in_affine, pre_act=pre_act, affine=affine, post_act=post_act, row_bias=row_bias, gate_seg=gate_seg)
+    o.ldx = cin + extra_ld
+    o.xfull = rn(B, T, o.ldx)
+    o.x2full = rn(B, T, o.ldx) if with_x2 else None
+    o.w = rn(cout, cin, k) * (2.0 / (cin * k)) ** 0.5
+    o.bias = rn(cout) * 0.1
+    o.scale = (torch.rand(cout, generator=g) + 0.5) * out_gain if affine else None   # out_gain: drives the outputs beyond the fp16 range (saturation at +-65504)
+    o.shift = rn(cout) * 0.1 if affine else None
+    o.in_s = torch.rand(cin, generator=g) + 0.5 if in_affine else None
+    o.in_t = rn(cin) * 0.2 if in_affine else None
+    o.pad = 0 if valid else dil * (k - 1) // 2
+    o.T_out = (T + 2 * o.pad - dil * (k - 1) - 1) // stride + 1
+    o.rb = rn(B, cout) * 0.3 if row_bias else None
+    o.nseg = -(-o.T_out // gate_seg) if gate_seg else 0
+    o.gate = torch.rand(B, o.nseg, cout, generator=g) if gate_seg else None
+    o.ldy = cout + extra_ld
+    o.addsrc = rn(B, o.T_out, o.ldy).half() if second_out else None
     xdt = torch.float32 if x_f32 else torch.float16
-    xd = xfull.to(xdt).to(device)
-    x2d = x2full.to(xdt).to(device) if with_x2 else None
-    ldy = cout + extra_ld
+    o.x, o.x2 = o.xfull.to(xdt), (o.x2full.to(xdt) if with_x2 else None)   # as stored on the device
+    return o
+
+
+def conv1d_rounded_input(o):
+    """[B, cin, T + 2 pad] fp32 holding the fp16 values the MFMAs consume: x (+ x2 in fp32) (through the in-affine fma + ReLU), rounded once, padded"""
+    xin = o.x.float()[..., :o.cin]
+    if o.with_x2:
+        xin = xin + o.x2.float()[..., :o.cin]
+    if o.in_affine:   # one rounding, like the kernel's fma (mul + add in fp32 lands on the other side of an fp16 rounding boundary for ~1 element in 30 000:
+        #              a 1e-3 difference behind the conv -- found by the device fuzz of round 5, r14x)
+        xin = torch.relu((xin.double() * o.in_s.double() + o.in_t.double()).float())
+    xin = xin.half().float().transpose(1, 2)
+    if o.pad:
+        xin = F.pad(xin, (o.pad, o.pad), mode='reflect' if o.pad_mode == 'reflect' else 'constant')
+    return xin
+
+
+def conv1d_ref32(o):
+    """torch fp32 reference [B, T_out, cout] on the values the kernel actually consumes (before the fp16 output's clamp)"""
+    ref = F.conv1d(conv1d_rounded_input(o), o.w.half().float(), o.bias, stride=o.stride, dilation=o.dil)
+    if o.row_bias:
+        ref = ref + o.rb.unsqueeze(2)
+    ref = ACT[o.pre_act](ref)
+    if o.affine:
+        ref = ref * o.scale.view(1, -1, 1) + o.shift.view(1, -1, 1)
+    ref = ACT[o.post_act](ref).transpose(1, 2)
+    if o.gate_seg:
+        seg = torch.arange(o.T_out) // o.gate_seg
+        ref = ref * o.gate[:, seg, :]
+    return ref
+
+
+# conv1d_case applies the per-element fp64 bound of tests/conv1d_cases.py up to this cin * k (above it the bound is as loose as the global tolerance)
+CONV_BOUND_MAX_K = 1024
+
+
+def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, pad_mode='reflect', valid=False,
+                x_f32=False, y_f32=False, with_x2=False, in_affine=False, pre_act=1, affine=True, post_act=0,
+                row_bias=False, gate_seg=0, extra_ld=8, second_out=False, tile=0, stats=0, in_stats=False, seed=0, persist_blocks=0, clock_probe=False, return_y=False, out_gain=1.0,
+                expect=None, plan_cus=None, log=None, tag=''):
+    """expect: {'kernel': ..., ...} -- fields of mv_conv1d_plan_info the descriptor must plan to on this device, asserted before the launch.
+    plan_cus: launch nothing; return {cus: plan info} of the case's descriptor for these compute-unit counts (the weights stay unpacked).
+    log: receives the per-element bound's line (tests/conv1d_cases.py) where the bound applies."""
+    o = conv1d_operands(B=B, T=T, cin=cin, cout=cout, k=k, dil=dil, stride=stride, pad_mode=pad_mode, valid=valid, x_f32=x_f32, y_f32=y_f32,
+                        with_x2=with_x2, in_affine=in_affine, pre_act=pre_act, affine=affine, post_act=post_act, row_bias=row_bias,
+                        gate_seg=gate_seg, extra_ld=extra_ld, second_out=second_out, seed=seed, out_gain=out_gain)
+    ldx, w, bias, scale, shift, in_s, in_t, pad, T_out, rb, gate = o.ldx, o.w, o.bias, o.scale, o.shift, o.in_s, o.in_t, o.pad, o.T_out, o.rb, o.gate
+
+    xd = o.x.to(device)
+    x2d = o.x2.to(device) if with_x2 else None
+    ldy = o.ldy
     y = torch.full((B, T_out, ldy), 7.0, dtype=torch.float32 if y_f32 else torch.float16, device=device)
     wd = w.to(device)
-    packed = pack_weight(cdll, wd)
+    packed = pack_weight(cdll, wd) if plan_cus is None else torch.zeros(cdll.mv_conv1d_packed_elems(cout, cin, k), dtype=torch.float16, device=device)
     dev = lambda t: None if t is None else t.to(device).contiguous()
     biasd, scaled, shiftd, in_sd, in_td, rbd, gated = map(dev, (bias, scale, shift, in_s, in_t, rb, gate))
     d = _hip.MvConv1dDesc()
@@ -66,7 +121,7 @@ def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, 
     d.gate, d.gate_seg_len = (gated.data_ptr(), gate_seg) if gate_seg else (None, 0)
     d.y, d.y_dtype, d.ldy = y.data_ptr(), (_hip.MV_DT_F32 if y_f32 else _hip.MV_DT_F16), ldy
     if second_out:
-        addsrc = (rn(B, T_out, ldy)).half().to(device)
+        addsrc = o.addsrc.to(device)
         sumdst = torch.full((B, T_out, ldy), 5.0, dtype=torch.float16, device=device)
         d.add_src, d.sum_dst, d.ld_add, d.ld_sum = addsrc.data_ptr(), sumdst.data_ptr(), ldy, ldy
     d.B, d.T_in, d.T_out, d.cin, d.cout, d.k = B, T, T_out, cin, cout, k
@@ -87,6 +142,11 @@ def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, 
     if clock_probe:   # MvConv1dDesc.clock_probe (ABI 5): the ring kernel's workgroups leave their entry / exit clocks
         probe = torch.zeros(4 * 264, dtype=torch.int64, device=device)
         d.clock_probe = probe.data_ptr()
+    if plan_cus is not None:
+        return {cus: _hip.conv1d_plan_info(d, 1, cus, cdll) for cus in plan_cus}
+    plan = _hip.conv1d_plan_info(d, 1, 0, cdll)
+    for name, want in (expect or {}).items():
+        assert plan[name] == want, f'{tag}: the plan has {name} = {plan[name]!r}, the case is pinned to {want!r} ({plan})'
     _hip.check(cdll.mv_conv1d_forward(ctypes.byref(d), _stream(xd)), cdll)
     if device != 'cpu':
         torch.cuda.synchronize()
@@ -109,25 +169,7 @@ def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, 
         assert e1 < 2e-6 * max(1.0, rm.abs().max().item()) and e2 < 2e-5 * max(1.0, rs.abs().max().item()), f'input statistics {e1} {e2}'
 
     # ---- torch fp32 reference on the values the kernel actually consumes ----
-    xin = xd.cpu().float()[..., :cin]
-    if with_x2:
-        xin = xin + x2d.cpu().float()[..., :cin]
-    if in_affine:   # one rounding, like the kernel's fma (mul + add in fp32 lands on the other side of an fp16 rounding boundary for ~1 element in 30 000:
-        #              a 1e-3 difference behind the conv -- found by the device fuzz of round 5, r14x)
-        xin = torch.relu((xin.double() * in_s.double() + in_t.double()).float())
-    xin = xin.half().float().transpose(1, 2)
-    if pad:
-        xin = F.pad(xin, (pad, pad), mode='reflect' if pad_mode == 'reflect' else 'constant')
-    ref = F.conv1d(xin, w.half().float(), bias, stride=stride, dilation=dil)
-    if row_bias:
-        ref = ref + rb.unsqueeze(2)
-    ref = ACT[pre_act](ref)
-    if affine:
-        ref = ref * scale.view(1, -1, 1) + shift.view(1, -1, 1)
-    ref = ACT[post_act](ref).transpose(1, 2)
-    if gate_seg:
-        seg = torch.arange(T_out) // gate_seg
-        ref = ref * gate[:, seg, :]
+    ref = conv1d_ref32(o)
     got = y.cpu().float()
     assert torch.all(got[..., cout:] == 7.0), 'kernel wrote outside its channel slice'
     if not y_f32:   # fp16 outputs saturate instead of overflowing (v_med3 / MODE.FP16_OVFL)
@@ -138,6 +180,10 @@ def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, 
     err = (got[..., :cout] - ref).abs().max().item()
     tol = 2e-4 if y_f32 else 4e-3 * max(1.0, ref.abs().max().item())
     assert err < tol, f'conv1d mismatch {err} (tol {tol})'
+    if cin * k <= CONV_BOUND_MAX_K:   # the per-element bound against fp64
+        import conv1d_cases
+        launched = '+'.join(name for name in (plan['in_stats_kernel'], plan['kernel'], plan['tail_kernel']) if name)
+        conv1d_cases.assert_within_bound(o, got[..., :cout], kernel=launched, tag=tag, log=log)
     if stats:
         mean = torch.empty(B, cout, device=device)
         std = torch.empty(B, cout, device=device) if stats == 2 else None
@@ -482,8 +528,8 @@ CONV_CASES = [
     dict(k=3, dil=3, cin=32, cout=512, T=90, B=3, tile=256, gate_seg=25, pre_act=0, affine=False, pad_mode='zero'),
     dict(k=1, dil=1, cin=136, cout=128, T=170, B=3, tile=160, row_bias=True, post_act=2),  # 128 x 160 tile (ASP hidden layer shape)
     dict(k=3, dil=2, cin=64, cout=200, T=100, B=2, tile=160),            # 160-row tile, taps, ragged channels
-    dict(k=1, dil=1, cin=128, cout=768, T=300, B=4, tile=256),           # persistent kernel: 15 tiles, workgroups walk 3 of them
-    dict(k=1, dil=1, cin=64, cout=512, T=150, B=7, tile=256),            # persistent, single K stage per tile (first == last stage)
+    dict(k=1, dil=1, cin=128, cout=768, T=300, B=4, tile=256),           # ring kernel (CK_RING): 15 tiles; eight resident workgroups walk two of them, a full chip has one workgroup per tile
+    dict(k=1, dil=1, cin=64, cout=512, T=150, B=7, tile=256),            # a single K stage: below the persistent kernels' two stages, so the one-shot 256 x 256 kernel (CK_GLDS_256), 10 tiles
     dict(k=1, dil=1, cin=128, cout=256, T=90, B=5, tile=256, stats=1),   # fused time mean: utterance boundaries inside 64-row blocks
     dict(k=1, dil=1, cin=192, cout=512, T=298, B=3, tile=256, stats=2),  # fused mean + std (ASP global statistics), ragged last tile
     dict(k=1, dil=1, cin=128, cout=256, T=64, B=4, tile=256, stats=2, affine=False, extra_ld=0),  # boundaries on block edges, no BN

@@ -1754,15 +1754,16 @@ struct ConvKernelRow {
     int threads, lds_bytes;
     int tile_rows, tile_ch;   // time steps x output channels of one workgroup's tile
     const char* name;
+    const char* id_name;      // the enumerator as spelled: what mv_conv1d_plan_info reports
 };
 
 // a conv1d_glds_kernel row: threads and tile follow from the template parameters as they do inside the kernel
 template <int WC, int WN, int MI, int NI, bool INSTATS = false, int NS = 2>
-constexpr ConvKernelRow glds_row(ConvKernel id, int lds_bytes, const char* name) {
-    return {id, conv1d_glds_kernel<WC, WN, MI, NI, INSTATS, NS>, 64 * WC * WN, lds_bytes, WN * NI * 16, WC * MI * 16, name};
+constexpr ConvKernelRow glds_row(ConvKernel id, int lds_bytes, const char* name, const char* id_name) {
+    return {id, conv1d_glds_kernel<WC, WN, MI, NI, INSTATS, NS>, 64 * WC * WN, lds_bytes, WN * NI * 16, WC * MI * 16, name, id_name};
 }
-#define MV_GLDS_ROW(id, lds_bytes, ...) glds_row<__VA_ARGS__>(id, lds_bytes, "conv1d_glds_kernel<" #__VA_ARGS__ ">")
-#define MV_CONV_ROW(id, threads, lds_bytes, tile_rows, tile_ch, ...) {id, __VA_ARGS__, threads, lds_bytes, tile_rows, tile_ch, #__VA_ARGS__}
+#define MV_GLDS_ROW(id, lds_bytes, ...) glds_row<__VA_ARGS__>(id, lds_bytes, "conv1d_glds_kernel<" #__VA_ARGS__ ">", #id)
+#define MV_CONV_ROW(id, threads, lds_bytes, tile_rows, tile_ch, ...) {id, __VA_ARGS__, threads, lds_bytes, tile_rows, tile_ch, #__VA_ARGS__, #id}
 constexpr ConvKernelRow CONV_KERNELS[CK_COUNT] = {
     MV_GLDS_ROW(CK_GLDS_128, CV_LDS_BYTES, 2, 2, 4, 4),
     MV_GLDS_ROW(CK_GLDS_64, CV_LDS_BYTES_SMALL, 2, 2, 2, 2, false, CV_SMALL_NS),
@@ -2075,6 +2076,26 @@ static void launch_conv_kernel(ConvKernel k, int grid_x, int grid_y, const ConvA
     MV_LAUNCH(row.fn, (grid_x, grid_y, 1), (row.threads, 1, 1), row.lds_bytes, stream, a);
 }
 
+// The plan of a descriptor as conv1d_launch would make it, for a chip of `cus` compute units (0: this device's), and nothing launched: the same
+// conv1d_check and conv1d_plan, so the same refusals.  (mv_conv1d_plan_info: tests name the table row a case has to run.)
+int conv1d_plan_info(const MvConv1dDesc& d_in, int groups, int cus, MvConv1dPlanInfo* out) {
+    int rc = conv1d_check(d_in, groups);
+    if (rc != MV_OK) return rc;
+    const MvConv1dDesc d = one_group(d_in, groups);
+    if (cus == 0) cus = device_cu_count();
+    ConvPlan p;
+    if ((rc = conv1d_plan(d, groups, cus, persistent_blocks(d, cus), &p))) return rc;
+    out->kernel = CONV_KERNELS[p.kernel].id_name;
+    out->in_stats_kernel = p.in_stats_first ? CONV_KERNELS[CK_IN_STATS].id_name : "";
+    out->tail_kernel = p.tail_nv > 0 ? CONV_KERNELS[p.tail_kernel].id_name : "";
+    out->n_tiles = p.n_tiles;
+    out->co_tiles = p.co_tiles;
+    out->grid = p.grid;
+    out->tail_nv = p.tail_nv;
+    out->tail_split = p.tail_split;
+    return MV_OK;
+}
+
 int conv1d_launch(const MvConv1dDesc& d_in, hipStream_t stream, int groups) {
     int rc = conv1d_check(d_in, groups);
     if (rc != MV_OK) return rc;
@@ -2189,6 +2210,17 @@ int mv_conv1d_forward_grouped(const MvConv1dDesc* d, int32_t groups, mv_stream_t
     MV_REQUIRE(d->cin % groups == 0 && d->cout % groups == 0, "mv_conv1d_forward_grouped: cin and cout must be divisible by groups");
     const bool native = mv::conv1d_grouped_native(d->cout, d->cin, d->k, groups);
     return mv::conv1d_launch(*d, static_cast<hipStream_t>(stream), native ? groups : 1);   // expanded: the block-diagonal weight, a dense layer
+}
+
+int mv_conv1d_plan_info(const MvConv1dDesc* d, int32_t groups, int32_t cus, MvConv1dPlanInfo* out) {
+    MV_REQUIRE(d != nullptr && out != nullptr, "mv_conv1d_plan_info: null argument");
+    MV_REQUIRE(cus >= 0, "mv_conv1d_plan_info: cus must be 0 (this device) or a count of compute units");
+    if (groups == 1) return mv::conv1d_plan_info(*d, 1, cus, out);
+    // the grouped entry point's own checks and its choice of form (mv_conv1d_forward_grouped)
+    MV_REQUIRE(groups >= 1, "mv_conv1d_forward_grouped: groups must be positive");
+    MV_REQUIRE(d->cin % groups == 0 && d->cout % groups == 0, "mv_conv1d_forward_grouped: cin and cout must be divisible by groups");
+    const bool native = mv::conv1d_grouped_native(d->cout, d->cin, d->k, groups);
+    return mv::conv1d_plan_info(*d, native ? groups : 1, cus, out);
 }
 
 }  // extern "C"

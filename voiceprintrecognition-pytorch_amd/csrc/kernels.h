@@ -13,6 +13,8 @@ int conv_stats_finish_launch(const float* psum, const float* psq, const float* s
                              int64_t ld_out, float clamp_eps, hipStream_t stream);
 // groups > 1: a native grouped 1x1 layer (conv1d_grouped_native; d.cin / d.cout are the layer's, w_packed the per-group packing)
 int conv1d_launch(const MvConv1dDesc& d, hipStream_t stream, int groups = 1);
+// what conv1d_launch would launch for `d` on a chip of `cus` compute units (0: this device's): same checks, same plan, no launch
+int conv1d_plan_info(const MvConv1dDesc& d, int groups, int cus, MvConv1dPlanInfo* out);
 bool conv1d_grouped_native(int cout, int cin, int k, int groups);
 // fused time statistics of a 1x1 layer's INPUT (MvConv1dDesc.in_stat_sum / in_stat_sq): partial buffer size and the finish pass
 int64_t conv_in_stats_elems(int B, int T, int cin);

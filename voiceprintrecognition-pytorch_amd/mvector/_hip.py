@@ -133,6 +133,12 @@ class MvConv1dDesc(ctypes.Structure):
                 ('persist_blocks_hint', c_i32), ('clock_probe', c_vp)]
 
 
+class MvConv1dPlanInfo(ctypes.Structure):
+    """what a conv1d forward would launch (mv_conv1d_plan_info): rows of csrc/conv1d.hip's kernel table by name, b'' where there is no such launch"""
+    _fields_ = [('kernel', ctypes.c_char_p), ('in_stats_kernel', ctypes.c_char_p), ('tail_kernel', ctypes.c_char_p),
+                ('n_tiles', c_i32), ('co_tiles', c_i32), ('grid', c_i32), ('tail_nv', c_i32), ('tail_split', c_i32)]
+
+
 class MvEigCfg(ctypes.Structure):
     _fields_ = [('m', c_i32), ('block', c_i32), ('degree', c_i32), ('max_iters', c_i32), ('tol', ctypes.c_double), ('seed', ctypes.c_uint64)]
 
@@ -219,6 +225,7 @@ _SIGNATURES = {
     'mv_conv1d_grouped_packed_elems': (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     'mv_conv1d_pack_weight_grouped': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp]),
     'mv_conv1d_forward_grouped': (c_i32, [ctypes.POINTER(MvConv1dDesc), c_i32, c_vp]),
+    'mv_conv1d_plan_info': (c_i32, [ctypes.POINTER(MvConv1dDesc), c_i32, c_i32, ctypes.POINTER(MvConv1dPlanInfo)]),
     'mv_conv1d_stats_elems': (c_i64, [c_i32, c_i32, c_i32]),
     'mv_conv1d_in_stats_elems': (c_i64, [c_i32, c_i32, c_i32]),
     'mv_conv1d_in_stats_finish': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, c_f32, c_vp]),
@@ -358,6 +365,19 @@ def current_stream(tensor):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def conv1d_plan_info(desc, groups=1, cus=0, cdll=None):
+    """What mv_conv1d_forward (groups = 1) / mv_conv1d_forward_grouped would launch for the MvConv1dDesc ``desc`` on a chip of ``cus`` compute
+    units (0: the current device's), nothing launched (mv_conv1d_plan_info): {'kernel', 'in_stats_kernel', 'tail_kernel'} -- rows of csrc/conv1d.hip's
+    kernel table by name, '' for no such launch -- and {'n_tiles', 'co_tiles', 'grid', 'tail_nv', 'tail_split'}.  A descriptor the forward refuses
+    raises the forward's error."""
+    cdll = cdll or lib()
+    info = MvConv1dPlanInfo()
+    check(cdll.mv_conv1d_plan_info(ctypes.byref(desc), groups, cus, ctypes.byref(info)), cdll)
+    out = {name: getattr(info, name).decode() for name in ('kernel', 'in_stats_kernel', 'tail_kernel')}
+    out.update((name, getattr(info, name)) for name in ('n_tiles', 'co_tiles', 'grid', 'tail_nv', 'tail_split'))
+    return out
 
 
 # mv_melspec_info / mv_spectrogram_info / mv_mfcc_info: the kernel behind the STFT of a handle
