@@ -1145,6 +1145,46 @@ int mv_cam_dense_block_f16(void* x, int64_t ldx, int32_t B, int32_t T2, int32_t 
                            int32_t dil, int32_t seg_len, int32_t form, int32_t* forms_used, void* workspace, size_t workspace_bytes,
                            mv_stream_t stream);
 
+/* Energy voice activity detection (Kaldi's compute-vad restated) of B fp32 waveform rows: per row the maximal runs [a, b) of speech frames.
+ *   frames    row b has n_b = num_samples[b] samples (device int64 [B], clamped to 0 .. L; NULL: every row has L).  T_b = 0 if n_b < frame_length,
+ *             else 1 + (n_b - frame_length) / frame_shift; frame t = x[t * frame_shift, t * frame_shift + frame_length).  T(L) is the count for n = L.
+ *   logE_t    fp64, v_i = (double)x_i * scale:  m = (sum v) / frame_length,  e = sum (v - m)^2,  logE = log(e < eps ? eps : e), eps = 2^-23 (the
+ *             comparison is written with <: a NaN energy stays NaN).  Both sums in one order: 32 lanes per frame, lane j adds the elements
+ *             j, j + 32, .. in ascending order (the squares by fma), the 32 lane sums fold by a butterfly over the lane offsets 16, 8, 4, 2, 1.
+ *   thr_b     energy_threshold + energy_mean_scale * (S / T_b), S the sum of the row's logE: per tile of MV_VAD_TILE_FRAMES frames a halving
+ *             tree over the tile's (zero-padded) entries, then thread j of 256 adds the tiles j, j + 256, .. in ascending order and a halving
+ *             tree folds the 256 sums.  No atomics on floats: the same bits on every run, stream and batch.  T_b = 0 gives NaN (0 / 0).
+ *   decision  over the frames lo = max(0, t - frames_context) .. hi = min(T_b - 1, t + frames_context): den = hi - lo + 1, num = how many of them
+ *             have logE > thr; speech iff (double)num >= (double)den * proportion_threshold.
+ *   runs      maximal stretches [a, b) of speech frames in ascending order as pairs of int32: num_runs[b] is the row's true count, the first
+ *             min(num_runs[b], max_runs) pairs of runs [B, max_runs, 2] are written and nothing behind them.
+ * A row with T_b = 0 has no runs; a NaN sample makes thr NaN, every logE > thr false and (proportion_threshold > 0) the row free of runs.
+ * wav row b starts at wav + b * wav_stride (wav_stride >= L, any 4-byte alignment: 16-byte loads where the address allows, scalar loads
+ * otherwise).  num_frames [B] int32 = T_b.  Optional device outputs (NULL: not written): log_energy [B, T(L)] fp64, threshold [B] fp64, decisions
+ * [B, T(L)] uint8 -- entries at t >= T_b are written as zeros.  Five ordinary launches on `stream` (energies, thresholds, decisions + boundary
+ * counts per tile, one scan of the counts, the scatter of the boundaries): no workgroup waits for another, the call does not synchronise and
+ * allocates nothing.  workspace: device memory, 16-byte aligned, of the size the companion reports (0 for arguments it refuses); what it and the
+ * outputs held before does not matter.  B = 0 returns MV_OK and touches nothing.  MV_ERR_INVALID_ARGUMENT: a null cfg or required pointer
+ * (runs may be NULL when max_runs = 0), negative B / L / max_runs, wav_stride < L, 1 <= frame_shift <= frame_length <= 4096 violated,
+ * frames_context outside 0 .. 64, a non-finite real field, B * (T(L) + 1) above 2^31 - 1.  MV_ERR_WORKSPACE: a short workspace.
+ * The defaults are compute-vad's: 400 / 160 samples (25 / 10 ms at 16 kHz), context 0, 5.0, 0.5, 0.6; scale 32768 turns [-1, 1) samples into the
+ * int16 range its thresholds assume. */
+#define MV_VAD_TILE_FRAMES 256
+typedef struct MvVadCfg {
+    int32_t frame_length;          /* samples */
+    int32_t frame_shift;           /* samples */
+    int32_t frames_context;
+    int32_t reserved;
+    double energy_threshold;
+    double energy_mean_scale;
+    double proportion_threshold;
+    double scale;
+} MvVadCfg;
+size_t mv_vad_energy_workspace_bytes(const MvVadCfg* cfg, int32_t B, int64_t L);
+int mv_vad_energy_f32(const MvVadCfg* cfg, const float* wav, int64_t wav_stride, const int64_t* num_samples, int32_t B, int64_t L,
+                      int32_t* num_frames, int32_t* num_runs, int32_t* runs, int32_t max_runs, double* log_energy, double* threshold,
+                      uint8_t* decisions, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -156,6 +156,12 @@ class MvVerifCfg(ctypes.Structure):
     _fields_ = [('p_target', ctypes.c_double), ('c_miss', ctypes.c_double), ('c_fa', ctypes.c_double)]
 
 
+class MvVadCfg(ctypes.Structure):
+    _fields_ = [('frame_length', c_i32), ('frame_shift', c_i32), ('frames_context', c_i32), ('reserved', c_i32),
+                ('energy_threshold', ctypes.c_double), ('energy_mean_scale', ctypes.c_double), ('proportion_threshold', ctypes.c_double),
+                ('scale', ctypes.c_double)]
+
+
 class MvVerifResult(ctypes.Structure):
     _fields_ = [('n_target', c_i64), ('n_impostor', c_i64), ('i1', c_i64), ('i2', c_i64), ('tgt_i1', c_i64), ('tgt_i2', c_i64),
                 ('min_cost', ctypes.c_double), ('score_i1', c_f32), ('reserved', c_i32)]
@@ -306,6 +312,8 @@ _SIGNATURES = {
     'mv_cohort_stats_workspace_bytes': (c_sz, [c_i32, c_i32, c_i32, c_i32]),
     'mv_cohort_stats_f32': (c_i32, [c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_vp, c_sz, c_vp]),
     'mv_score_norm_f32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    'mv_vad_energy_workspace_bytes': (c_sz, [ctypes.POINTER(MvVadCfg), c_i32, c_i64]),
+    'mv_vad_energy_f32': (c_i32, [ctypes.POINTER(MvVadCfg), c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1030,6 +1038,65 @@ def score_norm(scores, trial_stats, enroll_stats, mode='s', out=None, cdll=None)
     check(cdll.mv_score_norm_f32(scores.data_ptr(), n_t, n_e, _ptr(tm), _ptr(ts), _ptr(em), _ptr(es), SCORE_NORM_MODES[mode], out.data_ptr(),
                                  current_stream(scores)), cdll)
     return out
+
+
+MV_VAD_TILE_FRAMES = 256
+VAD_DEFAULTS = dict(frame_length=400, frame_shift=160, frames_context=0, energy_threshold=5.0, energy_mean_scale=0.5, proportion_threshold=0.6,
+                    scale=32768.0)   # compute-vad's own; scale: [-1, 1) samples in the int16 range its thresholds assume
+
+
+def vad_cfg(**cfg):
+    """MvVadCfg of VAD_DEFAULTS with ``cfg`` on top; an unknown field is a TypeError"""
+    unknown = sorted(set(cfg) - set(VAD_DEFAULTS))
+    if unknown:
+        raise TypeError(f'vad_energy: unknown configuration field(s) {unknown}; the fields are {sorted(VAD_DEFAULTS)}')
+    values = dict(VAD_DEFAULTS, **cfg)
+    out = MvVadCfg()
+    for name in ('frame_length', 'frame_shift', 'frames_context'):
+        setattr(out, name, int(values[name]))
+    for name in ('energy_threshold', 'energy_mean_scale', 'proportion_threshold', 'scale'):
+        setattr(out, name, float(values[name]))
+    return out
+
+
+def vad_num_frames(n, frame_length=400, frame_shift=160):
+    return 0 if n < frame_length else 1 + (n - frame_length) // frame_shift
+
+
+def vad_energy(wav, lengths=None, max_runs=None, cdll=None, **cfg):
+    """Energy VAD of fp32 waveform rows (mv_vad_energy_f32): ``wav`` [L] or [B, L] with unit stride along time (any row stride and
+    alignment), ``lengths`` int64 [B] = the rows' own sample counts -> dict of tensors on wav's device:
+    'num_frames' int32 [B], 'num_runs' int32 [B], 'runs' int32 [B, max_runs, 2] (frames [a, b); the first min(num_runs, max_runs) pairs of a
+    row are written), 'log_energy' fp64 [B, T(L)], 'threshold' fp64 [B], 'decisions' uint8 [B, T(L)] (zeros at t >= num_frames), and 'packed':
+    the int32 buffer the first three are views of -- one download brings them all.  ``max_runs`` None = ceil(T(L) / 2), the most a row can
+    have.  ``cfg``: the fields of VAD_DEFAULTS.  Nothing synchronises."""
+    cdll = cdll or lib()
+    assert wav.dtype == torch.float32 and wav.dim() in (1, 2)
+    if wav.dim() == 1:
+        wav = wav.unsqueeze(0)
+    B, L = wav.shape
+    if L > 1 and wav.stride(1) != 1 or B > 1 and wav.stride(0) < L:
+        wav = wav.contiguous()
+    c = vad_cfg(**cfg)
+    if lengths is not None:
+        lengths = lengths.to(device=wav.device, dtype=torch.int64).contiguous()
+        if lengths.shape != (B,):
+            raise ValueError(f'lengths must have shape ({B},), got {tuple(lengths.shape)}')
+    # (a configuration the library refuses gives T = 0 here and its message below)
+    T = vad_num_frames(L, c.frame_length, c.frame_shift) if 1 <= c.frame_shift <= c.frame_length else 0
+    if max_runs is None:
+        max_runs = (T + 1) // 2
+    packed = torch.empty((2 * B + 2 * B * max(int(max_runs), 0),), dtype=torch.int32, device=wav.device)
+    num_frames, num_runs, runs = packed[:B], packed[B:2 * B], packed[2 * B:].view(B, max(int(max_runs), 0), 2)
+    log_energy = torch.empty((B, T), dtype=torch.float64, device=wav.device)
+    threshold = torch.empty((B,), dtype=torch.float64, device=wav.device)
+    decisions = torch.empty((B, T), dtype=torch.uint8, device=wav.device)
+    nbytes = int(cdll.mv_vad_energy_workspace_bytes(ctypes.byref(c), B, L))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=wav.device)   # per call: streams never share it
+    check(cdll.mv_vad_energy_f32(ctypes.byref(c), wav.data_ptr(), wav.stride(0) if B > 1 else L, _ptr(lengths), B, L, num_frames.data_ptr(),
+                                 num_runs.data_ptr(), runs.data_ptr() if runs.numel() else None, int(max_runs), log_energy.data_ptr() if T else None,
+                                 threshold.data_ptr(), decisions.data_ptr() if T else None, ws.data_ptr(), nbytes, current_stream(wav)), cdll)
+    return dict(num_frames=num_frames, num_runs=num_runs, runs=runs, log_energy=log_energy, threshold=threshold, decisions=decisions, packed=packed)
 
 
 def wave_chunks(wav, start, length, chunk_len, target_db=None, max_gain_db=300.0, cdll=None):

@@ -412,6 +412,28 @@ class MVectorPredictor:
             raise ValueError(f'无法将段规范化到{dataset.target_dB}dB，音频增益已经超过max_gain_db (300.0dB)')
         return torch.cat(features, dim=0)
 
+    def vad(self, audio_data, sample_rate=16000, vad=None):
+        """语音活动检测 -> [{'start': seconds, 'end': seconds}]: the speech regions of a recording by the energy VAD
+        (mvector/infer_utils/vad.py), in the shape ``speaker_diarization`` takes as ``vad_segments``.
+
+        :param audio_data: 需要识别的数据，支持文件路径，文件对象，字节，numpy，AudioSegment对象
+        :param sample_rate: 如果传入的是numpy数据，需要指定采样率
+        :param vad: an ``EnergyVad`` with other settings (its sample_rate must be the configured one); None = compute-vad's defaults
+
+        The audio is loaded as ``speaker_diarization`` loads it (resampling, dB normalisation), so the times line up.  GPU predictor: the
+        samples go up once and mv_vad_energy_f32 runs there, the list of runs comes down; ``use_gpu=False``: the same definition in numpy."""
+        from mvector.infer_utils.vad import EnergyVad
+        input_data = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+        if vad is None:
+            if getattr(self, 'energy_vad', None) is None or self.energy_vad.sample_rate != input_data.sample_rate:
+                self.energy_vad = EnergyVad(sample_rate=input_data.sample_rate)
+            vad = self.energy_vad
+        assert vad.sample_rate == input_data.sample_rate, f'the VAD is set up for {vad.sample_rate} Hz, the audio has {input_data.sample_rate} Hz'
+        samples = np.ascontiguousarray(input_data.samples, dtype=np.float32)
+        if self.device.type == 'cuda':
+            return vad(torch.from_numpy(samples).to(self.device))
+        return vad(samples)
+
     def speaker_diarization(self, audio_data, sample_rate=16000, speaker_num=None, search_audio_db=False, vad_segments=None):
         """说话人日志识别 -> [{'speaker', 'start', 'end'}]
 
