@@ -1185,6 +1185,54 @@ int mv_vad_energy_f32(const MvVadCfg* cfg, const float* wav, int64_t wav_stride,
                       int32_t* num_frames, int32_t* num_runs, int32_t* runs, int32_t max_runs, double* log_energy, double* threshold,
                       uint8_t* decisions, void* workspace, size_t workspace_bytes, mv_stream_t stream);
 
+/* The runs of speech frames of mv_vad_energy_f32 (its device outputs num_frames, num_runs, runs as they are) -> per row the speech regions in
+ * samples, in integers throughout.  Row b has n_b = num_samples[b] samples (device int64 [B], clamped to 0 .. L; NULL: every row has L), T_b =
+ * num_frames[b] frames and R_b = num_runs[b] runs; the four steps (mvector/infer_utils/vad.py, EnergyVad.smooth, is the same definition in numpy):
+ *   1. run [a, b) covers the samples [a * frame_shift, b * frame_shift); a run with b >= T_b (it reaches the last frame) ends at n_b;
+ *   2. neighbours whose gap (next start - end) is shorter than min_silence are joined;
+ *   3. joined regions shorter than min_speech are dropped;
+ *   4. every region left grows by speech_pad on both sides, stopped at 0, at n_b, and at end + gap / 2 (rounded down) of the gap to a neighbour,
+ *      on either side of that gap.
+ * regions [B, max_runs, 2] int32: the first num_regions[b] pairs [start, end) of a row are written and nothing behind them; kept [B] int64: the
+ * sum of the row's region lengths.  A row with num_runs[b] > max_runs (a truncated run list) cannot be smoothed: num_regions[b] = -1, kept[b] =
+ * -1, nothing else is written for it.  Steps 2 and 3 are flag -> exclusive scan -> compaction over tiles of MV_VAD_REGION_TILE runs, one
+ * workgroup per row walking its tiles in order with the scan values carried (a row may have any number of runs); two ordinary launches on
+ * `stream`: no workgroup waits for another, no atomics, the call does not synchronise and allocates nothing.  workspace: device memory, 16-byte
+ * aligned, mv_vad_regions_workspace_bytes(B, max_runs) bytes (the joined regions before step 4; 0 for B <= 0 or max_runs <= 0); what it and the
+ * outputs held before does not matter.  B = 0 returns MV_OK and touches nothing.  MV_ERR_INVALID_ARGUMENT: a null cfg or required pointer
+ * (runs, regions and the workspace may be NULL when max_runs = 0), negative B / L / max_runs, frame_shift < 1, a negative min_silence /
+ * min_speech / speech_pad, L above 2^31 - 1 (sample positions are int32), regions overlapping runs.  MV_ERR_WORKSPACE: a short workspace. */
+#define MV_VAD_REGION_TILE 256
+typedef struct MvVadSmoothCfg {
+    int32_t frame_shift;           /* samples, as all four */
+    int32_t min_silence;
+    int32_t min_speech;
+    int32_t speech_pad;
+} MvVadSmoothCfg;
+size_t mv_vad_regions_workspace_bytes(int32_t B, int32_t max_runs);
+int mv_vad_regions_i32(const MvVadSmoothCfg* cfg, const int32_t* num_frames, const int32_t* num_runs, const int32_t* runs, int32_t max_runs,
+                       const int64_t* num_samples, int32_t B, int64_t L, int32_t* num_regions, int32_t* regions, int64_t* kept, void* workspace,
+                       size_t workspace_bytes, mv_stream_t stream);
+
+/* Row b of out [B, L_out] = wav[b, s_j : e_j) of the row's first min(num_regions[b], max_regions) regions (regions [B, max_regions, 2] int32, as
+ * mv_vad_regions_i32 writes them) one behind the other in list order, then zeros up to L_out.  Every region is clamped to [0, n_b] (n_b as above);
+ * one with e <= s is empty; the regions need not be ordered or disjoint.  out_samples[b] int64 = the row's total, also where it exceeds L_out (the
+ * first L_out samples are written then).  A row with num_regions[b] < 0 (skipped by mv_vad_regions_i32) is all zeros with out_samples[b] = -1.
+ * Samples are copied as 32-bit words, never computed with: the bits of a NaN or a -0.0 arrive unchanged.  wav row b starts at wav + b *
+ * wav_stride, out row b at out + b * out_stride (any 4-byte alignment: 16-byte loads and stores where an address allows, 4-byte ones otherwise).
+ * Two ordinary launches on `stream`: one workgroup per row scans the region lengths into the workspace; then workgroups of MV_WAVE_GATHER_TILE
+ * outputs each find the region of their first output by binary search and keep the next MV_VAD_REGION_TILE regions in LDS (regions behind those are
+ * searched in the workspace).  No workgroup waits for another, no atomics, no synchronisation, no allocation.  out must not overlap wav.
+ * workspace: device memory, 16-byte aligned, mv_wave_gather_workspace_bytes(B, max_regions) bytes (0 for B <= 0 or a negative max_regions).  B = 0
+ * returns MV_OK and touches nothing.  MV_ERR_INVALID_ARGUMENT: a null required pointer (regions may be NULL when max_regions = 0, wav when L = 0,
+ * out when L_out = 0), negative B / L / L_out / max_regions, wav_stride < L, out_stride < L_out, wav or out not 4-byte aligned, out overlapping
+ * wav, B * ceil(L_out / MV_WAVE_GATHER_TILE) above 2^31 - 1.  MV_ERR_WORKSPACE: a short workspace. */
+#define MV_WAVE_GATHER_TILE 4096
+size_t mv_wave_gather_workspace_bytes(int32_t B, int32_t max_regions);
+int mv_wave_gather_f32(const float* wav, int64_t wav_stride, const int64_t* num_samples, const int32_t* num_regions, const int32_t* regions,
+                       int32_t max_regions, int32_t B, int64_t L, float* out, int64_t out_stride, int64_t L_out, int64_t* out_samples,
+                       void* workspace, size_t workspace_bytes, mv_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -330,3 +330,328 @@ extern "C" int mv_vad_energy_f32(const MvVadCfg* cfg, const float* wav, int64_t 
               p.tiles, p.Tmax, runs, max_runs, num_runs);
     return check_launch("vad_scatter_kernel");
 }
+
+// ================================================================================================ regions and gather
+// Behind the VAD, still on the device (the contracts of include/mvector_hip.h, mv_vad_regions_i32 and mv_wave_gather_f32): the runs of speech
+// frames become regions in samples -- EnergyVad.smooth restated in integers -- and the kept regions of every row are copied into a shorter row.
+//   vad_join_kernel          one workgroup per row walks the row's runs in tiles of MV_VAD_REGION_TILE (one run per thread) and carries its scan
+//                            values: a run is the head of a joined region when the gap in front of it stays, its tail when the gap behind it
+//                            stays; flags -> exclusive scan -> the joined regions that are long enough, compacted into the workspace.
+//   vad_pad_region_kernel    one workgroup per row: every kept region grows by speech_pad against its neighbours' middle; the row's sum of lengths.
+//   wave_gather_scan_kernel  one workgroup per row: exclusive scan of the clamped region lengths into the workspace, the total behind them.
+//   wave_gather_kernel       grid (output tiles of MV_WAVE_GATHER_TILE samples) x B: the region of the tile's first output by binary search over
+//                            the scanned lengths, the next MV_VAD_REGION_TILE regions as a table in LDS (regions behind the table are searched
+//                            in the workspace); four outputs per thread and trip -- one 16-byte load where they lie in one region and the source
+//                            address allows, scalar loads otherwise; one 16-byte store where the row's address allows.  Words are copied as
+//                            32-bit integers: no bit of a sample changes.
+// As above: the stream orders the launches, no workgroup waits for another, no atomics, nothing is read that a launch of the same call did not write.
+namespace mv {
+namespace {
+
+constexpr int VR_R = MV_VAD_REGION_TILE;          // runs / regions per tile, one per thread
+constexpr int WG_TILE = MV_WAVE_GATHER_TILE;      // outputs per workgroup of the gather
+constexpr int WG_TRIPS = WG_TILE / (4 * VAD_THREADS);
+static_assert(VR_R == VAD_THREADS && WG_TILE % (4 * VAD_THREADS) == 0, "tile geometry");
+typedef uint32_t word4v __attribute__((ext_vector_type(4)));
+
+// vad_excl_scan for any integer type.  wave_tot: 4 LDS words of T.
+template <class T>
+__device__ __forceinline__ T block_excl_scan(T v, T* wave_tot, T* total) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    T inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const T o = __shfl_up(inc, (unsigned)d);
+        if (lane >= d) inc += o;
+    }
+    __syncthreads();   // the previous use of wave_tot has been read
+    if (lane == 63) wave_tot[w] = inc;
+    __syncthreads();
+    T base = 0, tot = 0;
+    for (int k = 0; k < VAD_THREADS / 64; ++k) {
+        const T t = wave_tot[k];
+        base += k < w ? t : (T)0;
+        tot += t;
+    }
+    *total = tot;
+    return base + inc - v;
+}
+
+__device__ __forceinline__ int64_t run_start(const int32_t* run, int shift) { return (int64_t)run[0] * shift; }
+// a run that reaches the last frame ends with the row
+__device__ __forceinline__ int64_t run_end(const int32_t* run, int shift, int T, int64_t n) { return run[1] >= T ? n : (int64_t)run[1] * shift; }
+
+// grid (B).  joined [B, max_runs, 2] (workspace): the joined regions of at least min_speech samples.  num_regions [B]: their count; a row with more
+// runs than max_runs gets -1 here and in kept [B]
+__global__ __launch_bounds__(VAD_THREADS) void vad_join_kernel(MvVadSmoothCfg c, const int32_t* num_frames, const int32_t* num_runs, const int32_t* runs,
+                                                               int max_runs, const int64_t* num_samples, int64_t L, int32_t* joined,
+                                                               int32_t* num_regions, int64_t* kept) {
+    __shared__ int64_t head_start[VR_R];   // start of the tile's k-th head
+    __shared__ unsigned wave_tot[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int nr = num_runs[b];
+    if (nr > max_runs) {   // a truncated run list
+        if (tid == 0) num_regions[b] = -1, kept[b] = -1;
+        return;
+    }
+    const int T = num_frames[b], shift = c.frame_shift;
+    const int64_t n = row_samples(num_samples, b, L);
+    const int32_t* row = runs + (int64_t)b * max_runs * 2;
+    int32_t* dst = joined + (int64_t)b * max_runs * 2;
+    int64_t carry_start = 0;               // start of the last head of the tiles before
+    unsigned count = 0u;
+    for (int base = 0; base < nr; base += VR_R) {
+        const int i = base + tid;
+        int64_t s = 0, e = 0;
+        unsigned head = 0u, tail = 0u;
+        if (i < nr) {
+            s = run_start(row + 2 * i, shift), e = run_end(row + 2 * i, shift, T, n);
+            head = i == 0 || s - run_end(row + 2 * (i - 1), shift, T, n) >= c.min_silence ? 1u : 0u;
+            tail = i == nr - 1 || run_start(row + 2 * (i + 1), shift) - e >= c.min_silence ? 1u : 0u;
+        }
+        unsigned heads, keeps;
+        const unsigned hx = block_excl_scan<unsigned>(head, wave_tot, &heads);
+        if (head != 0u) head_start[hx] = s;
+        __syncthreads();
+        const unsigned upto = hx + head;   // heads of the tile up to and including run i
+        const int64_t first = upto > 0u ? head_start[upto - 1] : carry_start;
+        if (heads > 0u) carry_start = head_start[heads - 1];
+        const unsigned keep = tail != 0u && e - first >= c.min_speech ? 1u : 0u;
+        const unsigned kx = block_excl_scan<unsigned>(keep, wave_tot, &keeps);   // (its barriers stand between these reads of head_start and the next tile's writes)
+        if (keep != 0u) {
+            dst[2 * (int64_t)(count + kx)] = (int32_t)first;
+            dst[2 * (int64_t)(count + kx) + 1] = (int32_t)e;
+        }
+        count += keeps;
+    }
+    if (tid == 0) num_regions[b] = (int32_t)count;
+}
+
+// grid (B).  regions [B, max_runs, 2]: the first num_regions[b] pairs of a row; kept [B]: the sum of their lengths
+__global__ __launch_bounds__(VAD_THREADS) void vad_pad_region_kernel(MvVadSmoothCfg c, const int32_t* joined, int max_runs, const int64_t* num_samples, int64_t L,
+                                                                     const int32_t* num_regions, int32_t* regions, int64_t* kept) {
+    __shared__ int64_t red[VAD_THREADS];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int count = num_regions[b];
+    if (count < 0) return;
+    const int64_t n = row_samples(num_samples, b, L);
+    const int32_t* src = joined + (int64_t)b * max_runs * 2;
+    int32_t* dst = regions + (int64_t)b * max_runs * 2;
+    int64_t sum = 0;
+    for (int k = tid; k < count; k += VAD_THREADS) {
+        const int64_t s = src[2 * k], e = src[2 * k + 1];
+        int64_t lo = 0, hi = n;            // the middle of the gap to a neighbour (>> 1: numpy's // 2), else the row's ends
+        if (k > 0) lo = src[2 * k - 1] + ((s - src[2 * k - 1]) >> 1);
+        if (k + 1 < count) hi = e + ((src[2 * k + 2] - e) >> 1);
+        const int64_t ns = s - c.speech_pad > lo ? s - c.speech_pad : lo, ne = e + c.speech_pad < hi ? e + c.speech_pad : hi;
+        dst[2 * k] = (int32_t)ns, dst[2 * k + 1] = (int32_t)ne;
+        sum += ne - ns;
+    }
+    red[tid] = sum;
+#pragma unroll 1
+    for (int s = VAD_THREADS / 2; s > 0; s >>= 1) {
+        __syncthreads();
+        if (tid < s) red[tid] += red[tid + s];
+    }
+    if (tid == 0) kept[b] = red[0];
+}
+
+__device__ __forceinline__ int64_t clamp_to(int64_t v, int64_t n) { return v < 0 ? 0 : (v > n ? n : v); }
+
+// grid (B).  offs [B, max_regions + 1] (workspace): where every region of the row starts in the output, the total at [count]; out_samples [B]
+__global__ __launch_bounds__(VAD_THREADS) void wave_gather_scan_kernel(const int64_t* num_samples, int64_t L, const int32_t* num_regions, const int32_t* regions,
+                                                                       int max_regions, int64_t* offs, int64_t* out_samples) {
+    __shared__ int64_t wave_tot[4];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    int count = num_regions[b];
+    if (count < 0) {   // a skipped row
+        if (tid == 0) out_samples[b] = -1;
+        return;
+    }
+    count = count < max_regions ? count : max_regions;
+    const int64_t n = row_samples(num_samples, b, L);
+    const int32_t* row = regions + (int64_t)b * max_regions * 2;
+    int64_t* o = offs + (int64_t)b * (max_regions + 1);
+    int64_t carry = 0;
+    for (int base = 0; base < count; base += VR_R) {
+        const int j = base + tid;
+        int64_t len = 0;
+        if (j < count) {
+            const int64_t s = clamp_to(row[2 * j], n), e = clamp_to(row[2 * j + 1], n);
+            len = e > s ? e - s : 0;
+        }
+        int64_t total;
+        const int64_t ex = block_excl_scan<int64_t>(len, wave_tot, &total);
+        if (j < count) o[j] = carry + ex;
+        carry += total;
+    }
+    if (tid == 0) o[count] = carry, out_samples[b] = carry;
+}
+
+// grid (B * tiles).  out [B, L_out]: the words of the row's regions one behind the other, zeros behind them
+__global__ __launch_bounds__(VAD_THREADS) void wave_gather_kernel(const uint32_t* wav, int64_t wav_stride, const int64_t* num_samples, int64_t L,
+                                                                  const int32_t* num_regions, const int32_t* regions, int max_regions, const int64_t* offs,
+                                                                  uint32_t* out, int64_t out_stride, int64_t L_out, int tiles) {
+    __shared__ int64_t tab_off[VR_R + 1];   // output offsets of the regions j0 .. j0 + cnt, the last one closing the table
+    __shared__ int64_t tab_src[VR_R];       // their (clamped) first samples
+    const int tid = threadIdx.x;
+    const int b = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const int64_t o0 = (int64_t)tile * WG_TILE;
+    int count = num_regions[b];
+    count = count < max_regions ? count : max_regions;
+    const int64_t n = row_samples(num_samples, b, L);
+    const int32_t* row = regions + (int64_t)b * max_regions * 2;
+    const int64_t* o = offs + (int64_t)b * (max_regions + 1);
+    const int64_t total = count > 0 ? o[count] : 0;
+    const uint32_t* src = wav + (int64_t)b * wav_stride;
+    uint32_t* dst = out + (int64_t)b * out_stride;
+    const bool dst16 = reinterpret_cast<uintptr_t>(dst) % 16 == 0;   // a thread's first output is a multiple of four
+    int j0 = 0, cnt = 0;
+    if (o0 < total) {   // the region of the tile's first output: the first j with o[j + 1] > o0
+        int lo = 0, hi = count - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (o[mid + 1] > o0) hi = mid;
+            else lo = mid + 1;
+        }
+        j0 = lo;
+        cnt = count - j0 < VR_R ? count - j0 : VR_R;
+        for (int g = tid; g <= cnt; g += VAD_THREADS) {
+            tab_off[g] = o[j0 + g];
+            if (g < cnt) tab_src[g] = clamp_to(row[2 * (j0 + g)], n);
+        }
+    }
+    __syncthreads();
+    // the region of output q < total -- the first j with o[j + 1] > q, which passes over empty regions: its outputs [begin, end), its first sample
+    struct Located {
+        int64_t begin, end, first;
+    };
+    const auto locate = [&](int64_t q) {
+        if (q < tab_off[cnt]) {
+            int lo = 0, hi = cnt - 1;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (tab_off[mid + 1] > q) hi = mid;
+                else lo = mid + 1;
+            }
+            return Located{tab_off[lo], tab_off[lo + 1], tab_src[lo]};
+        }
+        int lo = j0 + cnt, hi = count - 1;   // behind the table
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (o[mid + 1] > q) hi = mid;
+            else lo = mid + 1;
+        }
+        return Located{o[lo], o[lo + 1], clamp_to(row[2 * lo], n)};
+    };
+#pragma unroll 1
+    for (int it = 0; it < WG_TRIPS; ++it) {
+        const int64_t p = o0 + (int64_t)it * 4 * VAD_THREADS + 4 * tid;
+        if (p >= L_out) break;
+        uint32_t v[4] = {0u, 0u, 0u, 0u};
+        if (p < total) {
+            const Located r = locate(p);
+            if (p + 4 <= r.end) {           // four outputs of one region
+                const uint32_t* from = src + r.first + (p - r.begin);
+                if (reinterpret_cast<uintptr_t>(from) % 16 == 0) {
+                    const word4v q = *reinterpret_cast<const word4v*>(from);
+                    v[0] = q[0], v[1] = q[1], v[2] = q[2], v[3] = q[3];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = from[e];
+                }
+            } else {                        // a region ends among them (or the row does): every output is located by itself
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int64_t q = p + e;
+                    if (q < total) {
+                        const Located s = q < r.end ? r : locate(q);
+                        v[e] = src[s.first + (q - s.begin)];
+                    }
+                }
+            }
+        }
+        if (dst16 && p + 4 <= L_out) {
+            *reinterpret_cast<word4v*>(dst + p) = word4v{v[0], v[1], v[2], v[3]};
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (p + e < L_out) dst[p + e] = v[e];
+        }
+    }
+}
+
+// [a, a + an) and [b, b + bn) share a byte
+bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn) {
+    const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b);
+    return an > 0 && bn > 0 && ua < ub + bn && ub < ua + an;
+}
+
+}  // namespace
+}  // namespace mv
+
+extern "C" size_t mv_vad_regions_workspace_bytes(int32_t B, int32_t max_runs) {
+    return B > 0 && max_runs > 0 ? mv::align256((size_t)B * (size_t)max_runs * 2 * sizeof(int32_t)) : 0;
+}
+
+extern "C" int mv_vad_regions_i32(const MvVadSmoothCfg* cfg, const int32_t* num_frames, const int32_t* num_runs, const int32_t* runs, int32_t max_runs,
+                                  const int64_t* num_samples, int32_t B, int64_t L, int32_t* num_regions, int32_t* regions, int64_t* kept, void* workspace,
+                                  size_t workspace_bytes, mv_stream_t stream) {
+    using namespace mv;
+    MV_REQUIRE(cfg != nullptr, "mv_vad_regions_i32: null cfg");
+    MV_REQUIRE(cfg->frame_shift >= 1, "mv_vad_regions_i32: frame_shift below 1");
+    MV_REQUIRE(cfg->min_silence >= 0 && cfg->min_speech >= 0 && cfg->speech_pad >= 0, "mv_vad_regions_i32: negative min_silence, min_speech or speech_pad");
+    MV_REQUIRE(B >= 0 && L >= 0 && max_runs >= 0, "mv_vad_regions_i32: negative B, L or max_runs");
+    MV_REQUIRE(L <= (int64_t)0x7FFFFFFF, "mv_vad_regions_i32: L above 2^31 - 1");
+    if (B == 0) return MV_OK;
+    MV_REQUIRE(num_frames != nullptr && num_runs != nullptr && num_regions != nullptr && kept != nullptr && ((runs != nullptr && regions != nullptr) || max_runs == 0),
+               "mv_vad_regions_i32: null tensor");
+    const size_t list_bytes = (size_t)B * (size_t)max_runs * 2 * sizeof(int32_t);
+    MV_REQUIRE(!ranges_overlap(runs, list_bytes, regions, list_bytes), "mv_vad_regions_i32: regions aliases runs");
+    const size_t need = mv_vad_regions_workspace_bytes(B, max_runs);
+    MV_REQUIRE(workspace != nullptr || need == 0, "mv_vad_regions_i32: null workspace");
+    if (workspace_bytes < need) return fail(MV_ERR_WORKSPACE, "mv_vad_regions_i32: workspace smaller than mv_vad_regions_workspace_bytes(B, max_runs)");
+    MV_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "mv_vad_regions_i32: workspace not 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t* joined = static_cast<int32_t*>(workspace);
+    MV_LAUNCH(vad_join_kernel, ((unsigned)B, 1, 1), (VAD_THREADS, 1, 1), 0, st, *cfg, num_frames, num_runs, runs, (int)max_runs, num_samples, L, joined, num_regions, kept);
+    const int rcl = check_launch("vad_join_kernel");
+    if (rcl != MV_OK) return rcl;
+    MV_LAUNCH(vad_pad_region_kernel, ((unsigned)B, 1, 1), (VAD_THREADS, 1, 1), 0, st, *cfg, (const int32_t*)joined, (int)max_runs, num_samples, L,
+              (const int32_t*)num_regions, regions, kept);
+    return check_launch("vad_pad_region_kernel");
+}
+
+extern "C" size_t mv_wave_gather_workspace_bytes(int32_t B, int32_t max_regions) {
+    return B > 0 && max_regions >= 0 ? mv::align256((size_t)B * ((size_t)max_regions + 1) * sizeof(int64_t)) : 0;
+}
+
+extern "C" int mv_wave_gather_f32(const float* wav, int64_t wav_stride, const int64_t* num_samples, const int32_t* num_regions, const int32_t* regions,
+                                  int32_t max_regions, int32_t B, int64_t L, float* out, int64_t out_stride, int64_t L_out, int64_t* out_samples, void* workspace,
+                                  size_t workspace_bytes, mv_stream_t stream) {
+    using namespace mv;
+    MV_REQUIRE(B >= 0 && L >= 0 && L_out >= 0 && max_regions >= 0, "mv_wave_gather_f32: negative B, L, L_out or max_regions");
+    if (B == 0) return MV_OK;
+    MV_REQUIRE(num_regions != nullptr && out_samples != nullptr && (regions != nullptr || max_regions == 0) && (wav != nullptr || L == 0) &&
+                   (out != nullptr || L_out == 0),
+               "mv_wave_gather_f32: null tensor");
+    MV_REQUIRE(wav_stride >= L, "mv_wave_gather_f32: wav_stride below L");
+    MV_REQUIRE(out_stride >= L_out, "mv_wave_gather_f32: out_stride below L_out");
+    MV_REQUIRE(reinterpret_cast<uintptr_t>(wav) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0, "mv_wave_gather_f32: wav or out not 4-byte aligned");
+    MV_REQUIRE(!ranges_overlap(wav, ((size_t)(B - 1) * (size_t)wav_stride + (size_t)L) * sizeof(float), out,
+                               ((size_t)(B - 1) * (size_t)out_stride + (size_t)L_out) * sizeof(float)),
+               "mv_wave_gather_f32: out aliases wav");
+    const int64_t tiles = (L_out + WG_TILE - 1) / WG_TILE;
+    MV_REQUIRE(tiles <= (int64_t)0x7FFFFFFF / B, "mv_wave_gather_f32: B * ceil(L_out / MV_WAVE_GATHER_TILE) above 2^31 - 1");
+    MV_REQUIRE(workspace != nullptr, "mv_wave_gather_f32: null workspace");
+    if (workspace_bytes < mv_wave_gather_workspace_bytes(B, max_regions))
+        return fail(MV_ERR_WORKSPACE, "mv_wave_gather_f32: workspace smaller than mv_wave_gather_workspace_bytes(B, max_regions)");
+    MV_REQUIRE(reinterpret_cast<uintptr_t>(workspace) % 16 == 0, "mv_wave_gather_f32: workspace not 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    int64_t* offs = static_cast<int64_t*>(workspace);
+    MV_LAUNCH(wave_gather_scan_kernel, ((unsigned)B, 1, 1), (VAD_THREADS, 1, 1), 0, st, num_samples, L, num_regions, regions, (int)max_regions, offs, out_samples);
+    const int rcl = check_launch("wave_gather_scan_kernel");
+    if (rcl != MV_OK || tiles == 0) return rcl;
+    MV_LAUNCH(wave_gather_kernel, ((unsigned)(B * tiles), 1, 1), (VAD_THREADS, 1, 1), 0, st, reinterpret_cast<const uint32_t*>(wav), wav_stride, num_samples, L,
+              num_regions, regions, (int)max_regions, (const int64_t*)offs, reinterpret_cast<uint32_t*>(out), out_stride, L_out, (int)tiles);
+    return check_launch("wave_gather_kernel");
+}

@@ -162,6 +162,10 @@ class MvVadCfg(ctypes.Structure):
                 ('scale', ctypes.c_double)]
 
 
+class MvVadSmoothCfg(ctypes.Structure):
+    _fields_ = [('frame_shift', c_i32), ('min_silence', c_i32), ('min_speech', c_i32), ('speech_pad', c_i32)]   # samples
+
+
 class MvVerifResult(ctypes.Structure):
     _fields_ = [('n_target', c_i64), ('n_impostor', c_i64), ('i1', c_i64), ('i2', c_i64), ('tgt_i1', c_i64), ('tgt_i2', c_i64),
                 ('min_cost', ctypes.c_double), ('score_i1', c_f32), ('reserved', c_i32)]
@@ -314,6 +318,10 @@ _SIGNATURES = {
     'mv_score_norm_f32': (c_i32, [c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp]),
     'mv_vad_energy_workspace_bytes': (c_sz, [ctypes.POINTER(MvVadCfg), c_i32, c_i64]),
     'mv_vad_energy_f32': (c_i32, [ctypes.POINTER(MvVadCfg), c_vp, c_i64, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_vad_regions_workspace_bytes': (c_sz, [c_i32, c_i32]),
+    'mv_vad_regions_i32': (c_i32, [ctypes.POINTER(MvVadSmoothCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_wave_gather_workspace_bytes': (c_sz, [c_i32, c_i32]),
+    'mv_wave_gather_f32': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1097,6 +1105,63 @@ def vad_energy(wav, lengths=None, max_runs=None, cdll=None, **cfg):
                                  num_runs.data_ptr(), runs.data_ptr() if runs.numel() else None, int(max_runs), log_energy.data_ptr() if T else None,
                                  threshold.data_ptr(), decisions.data_ptr() if T else None, ws.data_ptr(), nbytes, current_stream(wav)), cdll)
     return dict(num_frames=num_frames, num_runs=num_runs, runs=runs, log_energy=log_energy, threshold=threshold, decisions=decisions, packed=packed)
+
+
+MV_VAD_REGION_TILE = 256      # runs per tile of mv_vad_regions_i32, regions per search table of mv_wave_gather_f32
+MV_WAVE_GATHER_TILE = 4096    # outputs per workgroup of mv_wave_gather_f32
+
+
+def vad_regions(vad_out, lengths, frame_shift, min_silence, min_speech, speech_pad, L=None, cdll=None):
+    """The runs of ``vad_energy`` (its dict, as it is) -> the speech regions in samples (mv_vad_regions_i32: the four steps of
+    ``EnergyVad.smooth`` in integers on the device): (num_regions int32 [B], regions int32 [B, max_runs, 2] -- the first num_regions pairs of a
+    row are written --, kept int64 [B] = the sum of a row's region lengths).  ``lengths`` int64 [B] = the rows' own sample counts, ``L`` the
+    samples of a full row (None: ``lengths`` are taken as they are, and have to be given); the other four in samples.  A row whose run list was
+    truncated (num_runs above max_runs) has -1 in num_regions and kept.  Nothing synchronises."""
+    cdll = cdll or lib()
+    num_frames, num_runs, runs = vad_out['num_frames'], vad_out['num_runs'], vad_out['runs']
+    B, max_runs = runs.shape[0], runs.shape[1]
+    if lengths is not None:
+        lengths = lengths.to(device=runs.device, dtype=torch.int64).contiguous()
+        if lengths.shape != (B,):
+            raise ValueError(f'lengths must have shape ({B},), got {tuple(lengths.shape)}')
+    elif L is None:
+        raise ValueError('vad_regions: lengths or L')
+    c = MvVadSmoothCfg(int(frame_shift), int(min_silence), int(min_speech), int(speech_pad))
+    num_regions = torch.empty((B,), dtype=torch.int32, device=runs.device)
+    regions = torch.empty((B, max_runs, 2), dtype=torch.int32, device=runs.device)
+    kept = torch.empty((B,), dtype=torch.int64, device=runs.device)
+    nbytes = int(cdll.mv_vad_regions_workspace_bytes(B, max_runs))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=runs.device)   # per call: streams never share it
+    check(cdll.mv_vad_regions_i32(ctypes.byref(c), num_frames.data_ptr(), num_runs.data_ptr(), runs.data_ptr() if runs.numel() else None, max_runs,
+                                  _ptr(lengths), B, 0x7FFFFFFF if L is None else int(L), num_regions.data_ptr(),
+                                  regions.data_ptr() if regions.numel() else None, kept.data_ptr(), ws.data_ptr(), nbytes, current_stream(runs)), cdll)
+    return num_regions, regions, kept
+
+
+def wave_gather(wav, lengths, num_regions, regions, cdll=None):
+    """Row b of the result = wav[b, s : e) of the row's first num_regions[b] ``regions`` (int32 [B, max_regions, 2], clamped to the row's
+    ``lengths`` entry; None: L) one behind the other, zeros behind them (mv_wave_gather_f32; the samples are copied bit for bit) ->
+    (out fp32 [B, L], out_samples int64 [B]); a row with num_regions < 0 is zeros with out_samples -1.  Nothing synchronises."""
+    cdll = cdll or lib()
+    assert wav.dtype == torch.float32 and wav.dim() == 2 and regions.dim() == 3 and regions.shape[0] == wav.shape[0] and regions.shape[2] == 2
+    B, L = wav.shape
+    if L > 1 and wav.stride(1) != 1 or B > 1 and wav.stride(0) < L:
+        wav = wav.contiguous()
+    if lengths is not None:
+        lengths = lengths.to(device=wav.device, dtype=torch.int64).contiguous()
+        if lengths.shape != (B,):
+            raise ValueError(f'lengths must have shape ({B},), got {tuple(lengths.shape)}')
+    num_regions = num_regions.to(device=wav.device, dtype=torch.int32).contiguous()
+    regions = regions.to(device=wav.device, dtype=torch.int32).contiguous()
+    max_regions = regions.shape[1]
+    out = torch.empty((B, L), dtype=torch.float32, device=wav.device)
+    out_samples = torch.empty((B,), dtype=torch.int64, device=wav.device)
+    nbytes = int(cdll.mv_wave_gather_workspace_bytes(B, max_regions))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=wav.device)
+    check(cdll.mv_wave_gather_f32(wav.data_ptr() if L else None, wav.stride(0) if B > 1 else L, _ptr(lengths), num_regions.data_ptr(),
+                                  regions.data_ptr() if regions.numel() else None, max_regions, B, L, out.data_ptr() if L else None, L, L,
+                                  out_samples.data_ptr(), ws.data_ptr(), nbytes, current_stream(wav)), cdll)
+    return out, out_samples
 
 
 def wave_chunks(wav, start, length, chunk_len, target_db=None, max_gain_db=300.0, cdll=None):

@@ -17,6 +17,11 @@ and the arbiter of the device path.  There is no fallback between the two.  Both
 3. regions shorter than ``min_speech`` are dropped;
 4. every region grows by ``speech_pad`` on both sides, but not beyond the recording and not beyond the middle of the gap to its neighbour.
 
+``regions`` and ``trim`` go on without the host in between: on CUDA tensors the same four steps run on the device (``_hip.vad_regions``:
+mv_vad_regions_i32) and the kept regions of every row are moved together there (``_hip.wave_gather``: mv_wave_gather_f32) -- nothing comes
+down; on arrays and CPU tensors they are ``smooth`` and a concatenation.  ``MVectorPredictor.predict`` / ``predict_batch`` use ``trim`` for
+their ``vad=`` argument.
+
 Out of scope: int16 input (convert, or let ``MVectorPredictor.vad`` load the audio), selecting voiced frames at the feature level, a neural
 VAD, and any change to what ``speaker_diarization`` does without ``vad_segments``.
 """
@@ -138,6 +143,50 @@ class EnergyVad(object):
         new_end = np.minimum(end + self.speech_pad, np.concatenate([end[:-1] + gap // 2, [n]]))
         new_start = np.maximum(start - self.speech_pad, np.concatenate([[0], end[:-1] + gap // 2]))
         return np.stack([new_start, new_end], axis=1)
+
+    # ------------------------------------------------------------------ regions and trimming, without the host in between
+    def _device_regions(self, wav, lengths):
+        """CUDA rows [B, L] -> (num_regions, regions, kept, lengths tensor or None) on the device; nothing comes down"""
+        from mvector import _hip
+        lengths = None if lengths is None else _as_tensor(lengths)
+        out = _hip.vad_energy(wav, lengths=lengths, cdll=self._cdll, **self.cfg)   # max_runs = (T(L) + 1) // 2: no row can be truncated
+        got = _hip.vad_regions(out, lengths, self.cfg['frame_shift'], self.min_silence, self.min_speech, self.speech_pad, L=wav.shape[-1], cdll=self._cdll)
+        return got + (lengths,)
+
+    def regions(self, wav, lengths=None):
+        """-> (num_regions int32 [B], regions int32 [B, (T(L) + 1) // 2, 2], kept int64 [B]): per row its speech regions [start, end) in samples
+        (``smooth`` of its runs; the first num_regions pairs count) and the sum of their lengths; without the leading B for a 1-D waveform.
+        CUDA tensors give device tensors and download nothing (mv_vad_energy_f32, mv_vad_regions_i32); the host path gives numpy arrays, zeros
+        behind a row's regions."""
+        if self._is_device(wav):
+            got = self._device_regions(wav if wav.dim() == 2 else wav.unsqueeze(0), lengths)[:3]
+            return tuple(g[0] for g in got) if wav.dim() == 1 else got
+        rows, n = self._host_rows(wav, lengths)
+        max_runs = (self.num_frames(rows.shape[1]) + 1) // 2
+        num, reg, kept = np.zeros(len(n), dtype=np.int32), np.zeros((len(n), max_runs, 2), dtype=np.int32), np.zeros(len(n), dtype=np.int64)
+        for b, nb in enumerate(n):
+            dec = self._host_frames(rows[b, :nb])[0]
+            r = self.smooth(self.runs_of(dec), dec.shape[0], nb)
+            num[b], reg[b, :r.shape[0]], kept[b] = r.shape[0], r, (r[:, 1] - r[:, 0]).sum()
+        return (num[0], reg[0], kept[0]) if np.ndim(wav) == 1 else (num, reg, kept)
+
+    def trim(self, wav, lengths=None):
+        """-> (trimmed fp32 [B, L], kept int64 [B]): every row's speech regions one behind the other, zeros behind its kept samples; [L] and a
+        scalar for a 1-D waveform.  CUDA tensors run VAD -> regions -> gather on the current stream (mv_wave_gather_f32 last) and synchronise
+        nowhere: both results are device tensors.  Arrays and CPU tensors run the same definition in numpy.  There is no fallback between the two."""
+        if self._is_device(wav):
+            from mvector import _hip
+            rows = wav if wav.dim() == 2 else wav.unsqueeze(0)
+            num_regions, regions, kept, lengths = self._device_regions(rows, lengths)
+            out, _ = _hip.wave_gather(rows, lengths, num_regions, regions, cdll=self._cdll)
+            return (out[0], kept[0]) if wav.dim() == 1 else (out, kept)
+        rows, n = self._host_rows(wav, lengths)
+        num, reg, kept = self.regions(rows, n)
+        out = np.zeros(rows.shape, dtype=np.float32)
+        for b in range(rows.shape[0]):
+            if num[b]:
+                out[b, :kept[b]] = np.concatenate([rows[b, s:e] for s, e in reg[b, :num[b]]])
+        return (out[0], kept[0]) if np.ndim(wav) == 1 else (out, kept)
 
     def to_seconds(self, regions, n):
         """int64 [S, 2] samples -> [{'start': s, 'end': s}].  An end is lowered to the recording's last whole millisecond where its own

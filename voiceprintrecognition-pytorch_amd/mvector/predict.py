@@ -171,9 +171,53 @@ class MVectorPredictor:
         wav = torch.tensor(input_data.samples, dtype=torch.float32).unsqueeze(0).to(self.device)
         return self.predictor(self._audio_featurizer(wav)).data
 
-    def predict(self, audio_data, sample_rate=16000):
-        """预测一个音频的特征 -> np.ndarray [embd_dim]"""
-        return self._embed(audio_data, sample_rate).cpu().numpy()[0]
+    def predict(self, audio_data, sample_rate=16000, vad=None):
+        """预测一个音频的特征 -> np.ndarray [embd_dim]
+
+        :param vad: None = the whole audio, as always; True or an ``EnergyVad`` = embed the speech only (``predict_batch`` says how)"""
+        if vad is None:
+            return self._embed(audio_data, sample_rate).cpu().numpy()[0]
+        return self._embed_speech(audio_data, sample_rate, vad).cpu().numpy()[0]
+
+    # ------------------------------------------------------------------ speech only: VAD -> regions -> gather in front of the front-end
+    def _embedding_vad(self, vad):
+        """``vad=`` of predict / predict_batch -> the EnergyVad to trim with (True: compute-vad's defaults at the configured rate)"""
+        from mvector.infer_utils.vad import EnergyVad
+        rate = self.configs.dataset_conf.dataset.sample_rate
+        if vad is True:
+            if getattr(self, '_trim_vad', None) is None or self._trim_vad.sample_rate != rate:
+                self._trim_vad = EnergyVad(sample_rate=rate)
+            return self._trim_vad
+        assert isinstance(vad, EnergyVad), f'vad: None, True or an EnergyVad, not {type(vad)}'
+        assert vad.sample_rate == rate, f'the VAD is set up for {vad.sample_rate} Hz, the audio has {rate} Hz'
+        return vad
+
+    def _trim_batch(self, wav, lens, vad):
+        """the prepared batch ``wav`` [B, L] (a tensor on the predictor's device) with the rows' sample counts ``lens`` -> (the rows' speech
+        regions one behind the other, cut to the longest kept row; the kept sample counts as a list).  GPU predictor: EnergyVad.trim on the
+        device, the [B] kept counts are the one thing that comes down; ``use_gpu=False``: the same definition in numpy.  A row that keeps less
+        than min_duration is refused as _load_audio refuses a short file."""
+        dataset = self.configs.dataset_conf.dataset
+        vad = self._embedding_vad(vad)
+        if wav.is_cuda:
+            trimmed, kept = vad.trim(wav, lengths=torch.as_tensor(lens, dtype=torch.int64))
+            kept = kept.cpu().tolist()
+        else:
+            trimmed, kept = vad.trim(wav.numpy(), lengths=lens)
+            trimmed, kept = torch.from_numpy(trimmed), kept.tolist()
+        min_samples = int(math.ceil(round(dataset.min_duration * dataset.sample_rate, 6)))
+        for i, k in enumerate(kept):
+            assert k >= min_samples, (f'音频太短，最小应该为{dataset.min_duration}s，当前音频为{k / dataset.sample_rate}s '
+                                      f'(item {i}: {k} samples of speech are left by the VAD, {min_samples} are needed)')
+        return trimmed[:, :max(kept)], kept
+
+    @torch.no_grad()
+    def _embed_speech(self, audio_data, sample_rate, vad):
+        """``_embed`` of the speech regions of one utterance"""
+        input_data = self._load_audio(audio_data=audio_data, sample_rate=sample_rate)
+        wav = torch.tensor(input_data.samples, dtype=torch.float32).unsqueeze(0).to(self.device)
+        wav, _ = self._trim_batch(wav, [wav.shape[1]], vad)
+        return self.predictor(self._audio_featurizer(wav)).data
 
     def _pcm16_batch(self, audios_data):
         """Raw int16 mono PCM at the configured rate for EVERY item (paths / bytes of 16-bit mono WAVs), else None.
@@ -193,7 +237,7 @@ class MVectorPredictor:
         return out
 
     @torch.no_grad()
-    def _predict_batch_pcm16(self, pcms, batch_size):
+    def _predict_batch_pcm16(self, pcms, batch_size, vad=None):
         """GPU fast path of predict_batch: same padding / length-ratio semantics (predict.py:244-255), int16 upload from
         pinned memory, int16 -> float + dB normalisation + front-end + CMN + mask + backbone on the device."""
         from mvector import _hip
@@ -208,6 +252,9 @@ class MVectorPredictor:
         pcm = staging.to(self.device, non_blocking=True)
         n = torch.tensor(lens, dtype=torch.int64, device=self.device)
         wav, too_quiet = _hip.wave_prepare(pcm, n, dataset.target_dB if dataset.use_dB_normalization else None)
+        if vad is not None:
+            wav, lens = self._trim_batch(wav, lens, vad)
+            max_len = wav.shape[1]
         ratio = torch.tensor([l / max_len for l in lens], dtype=torch.float32, device=self.device)
         audio_feature = self._audio_featurizer(wav, ratio)
         step = max(int(batch_size), 256)  # 288 GB of HBM: the reference's 32-row chunks only multiply launches
@@ -265,7 +312,7 @@ class MVectorPredictor:
         return cache[rate]
 
     @torch.no_grad()
-    def _predict_batch_resampled(self, frames, batch_size):
+    def _predict_batch_resampled(self, frames, batch_size, vad=None):
         """GPU path of predict_batch for 16-bit files that are not all mono at the configured rate: per (rate, channels) group one pinned int16
         staging buffer, one upload and one call of the group's Resampler (target-rate mono rows: wave_prepare, as the pcm16 path), written into
         one [B, max n_out] batch; the length ratios come from the frame counts on the host -- nothing waits for the device."""
@@ -293,6 +340,9 @@ class MVectorPredictor:
             index = torch.tensor([i for i, _ in members], dtype=torch.int64, device=self.device)
             wav[index, :rows.shape[1]] = rows
             flags.append(quiet)
+        if vad is not None:
+            wav, lens = self._trim_batch(wav, lens, vad)
+            max_len = wav.shape[1]
         ratio = torch.tensor([l / max_len for l in lens], dtype=torch.float32, device=self.device)
         audio_feature = self._audio_featurizer(wav, ratio)
         step = max(int(batch_size), 256)
@@ -303,18 +353,27 @@ class MVectorPredictor:
         return out
 
     @torch.no_grad()
-    def predict_batch(self, audios_data, sample_rate=16000, batch_size=32):
-        """预测一批音频的特征 -> np.ndarray [B, embd_dim] (row order = input order)"""
+    def predict_batch(self, audios_data, sample_rate=16000, batch_size=32, vad=None):
+        """预测一批音频的特征 -> np.ndarray [B, embd_dim] (row order = input order)
+
+        :param vad: None = the whole audio, as always.  True (compute-vad's defaults at the configured rate) or an ``EnergyVad`` = embed the
+                    speech only: the batch is prepared exactly as without it (int16 upload, resampling, dB normalisation, on whichever of the
+                    three batch paths applies), then every row's speech regions are moved together on the device (``EnergyVad.trim``:
+                    mv_vad_energy_f32, mv_vad_regions_i32, mv_wave_gather_f32), the [B] kept sample counts come down -- the one added
+                    synchronisation --, the batch is cut to the longest kept row and the length ratios are those of the kept counts.
+                    ``use_gpu=False``: the same in numpy.  The VAD sees the dB-normalised waveform, as ``vad`` does, and the gain is NOT
+                    recomputed from the speech that is left.  A row that keeps less than min_duration of speech (a row of silence, say)
+                    raises the assertion a short file raises, with the item's index."""
         self._last_batch_path = 'host'
         if self.device.type == 'cuda':   # every feature method: wave_prepare and the ratio form of the front-end serve all four
             pcms = self._pcm16_batch(audios_data)
             if pcms is not None:
                 self._last_batch_path = 'pcm16'
-                return self._predict_batch_pcm16(pcms, batch_size)
+                return self._predict_batch_pcm16(pcms, batch_size, vad)
             frames = self._pcm16_frames_batch(audios_data)
             if frames is not None:
                 self._last_batch_path = 'pcm16_resampled'
-                return self._predict_batch_resampled(frames, batch_size)
+                return self._predict_batch_resampled(frames, batch_size, vad)
         samples = [self._load_audio(audio_data=a, sample_rate=sample_rate).samples for a in audios_data]
         max_len = max(s.shape[0] for s in samples)
         inputs = np.zeros((len(samples), max_len), dtype=np.float32)
@@ -323,6 +382,9 @@ class MVectorPredictor:
             inputs[i, :s.shape[0]] = s
             ratios.append(s.shape[0] / max_len)
         wav = torch.from_numpy(inputs).to(self.device)
+        if vad is not None:
+            wav, kept = self._trim_batch(wav, [s.shape[0] for s in samples], vad)
+            ratios = [k / wav.shape[1] for k in kept]
         ratio = torch.tensor(ratios, dtype=torch.float32, device=self.device)
         audio_feature = self._audio_featurizer(wav, ratio)
         features = []
