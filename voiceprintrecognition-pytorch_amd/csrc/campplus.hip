@@ -30,7 +30,6 @@
 #include <array>
 #include <cfloat>
 #include <functional>
-#include <memory>
 
 #include "kernels.h"
 #include "model.h"
@@ -868,15 +867,7 @@ struct CamppModel : MvModelBase {
 extern "C" {
 
 int mv_campp_create(const MvCamppCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_campp_create: null argument");
-    mv::Weights w;
-    int rc = w.init(tensors, num_tensors);
-    if (rc != MV_OK) return rc;
-    auto m = std::make_unique<mv::CamppModel>();
-    rc = m->create(*cfg, w);
-    if (rc != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
-    return MV_OK;
+    return mv::create_model<mv::CamppModel>("mv_campp_create", cfg, tensors, num_tensors, out);
 }
 
 }  // extern "C"

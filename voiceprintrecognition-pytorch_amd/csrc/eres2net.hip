@@ -1,59 +1,33 @@
 // ERes2Net / ERes2NetV2 forward orchestrated natively (mvector/models/eres2net.py:173-287, 383-456).
 //
-// create(): reads the reference-layout fp32 state_dict, folds every eval-mode BatchNorm into the conv in front of it
-// (BN follows each conv directly: eres2net.py:86-87, 96, 101-102; AFF eres2net.py:39-45), pads the channel groups to
-// multiples of 16 and packs the weights for conv2ds_kernel: split fp16 pairs with a per-layer power-of-two scale, maps in the S16 form (conv2ds.hip;
-// the fp32 kernels of conv2d.hip remain the CAM++ fp32 head's).  The two width-sized channel groups that
-// torch.split / torch.cat move around (eres2net.py:89, 99) are fixed slices of two buffers instead:
+// create(): reads the reference-layout fp32 state_dict; every eval-mode BatchNorm folds into the conv in front of it (BN follows each conv directly:
+// eres2net.py:86-87, 96, 101-102; AFF eres2net.py:39-45), the channel groups padded to multiples of 16 and packed for conv2ds_kernel
+// (make_s16_conv_bn, s16model.h).  The two width-sized channel groups that torch.split / torch.cat move around (eres2net.py:89, 99) are fixed
+// slices of two buffers instead (s16_grouped_map):
 //   A  = conv1 output   [.., scale * wpad]   group i = spx[i]
 //   Bc = "cat" buffer   [.., scale * wpad]   group i = relu(bn_i(conv_i(.)))
 // so a 3x3 conv writes slice i of Bc -- and, in the plain blocks, "its output + slice i+1 of A" (eres2net.py:92) as a second output into
 // a width-sized temporary that the next 3x3 conv reads (its loader is a plain copy); the AFF blocks fuse (slice i-1 of Bc, slice i of A) first;
 // conv3 reads Bc whole.  Padded channels carry exact zeros through every layer.
 // forward(): a fixed sequence of launches on the caller's stream over the caller's workspace.
-#include <memory>
-#include <vector>
-
-#include "kernels.h"
-#include "model.h"
+#include "s16model.h"
 
 namespace mv {
 
 namespace {
 
-struct C2Layer {
-    half_t* w = nullptr;   // split-packed (conv2ds_pack_host)
-    float* bias = nullptr;
-    float oscale = 0.0f;
-    int cin16 = 0, cout16 = 0, ks = 1, stride = 1;
-    int cin = 0, cout = 0;  // the layer's own channel counts (algorithmic FLOP accounting)
-};
-
 struct AffLayer {  // AFF (eres2net.py:32-52) on `ch` channels (padded chp per operand)
-    C2Layer att1, att2;
+    S16Conv att1, att2;
     int ch = 0, chp = 0, inter16 = 0;
 };
 
 struct Block {
-    C2Layer conv1, conv3, shortcut;
-    std::vector<C2Layer> convs;
+    S16Conv conv1, conv3, shortcut;
+    std::vector<S16Conv> convs;
     std::vector<AffLayer> fuse;  // empty for the plain blocks
     bool has_shortcut = false;
     int in_c16 = 0, out_c16 = 0, width = 0, wpad = 0, stride = 1;
 };
-
-std::vector<int> dense_map(int c) {
-    std::vector<int> m(c);
-    for (int i = 0; i < c; ++i) m[i] = i;
-    return m;
-}
-
-// channel c of a [scale * width] tensor lives at (c / width) * wpad + c % width
-std::vector<int> grouped_map(int width, int scale, int wpad) {
-    std::vector<int> m((size_t)width * scale);
-    for (int c = 0; c < width * scale; ++c) m[c] = (c / width) * wpad + c % width;
-    return m;
-}
 
 }  // namespace
 
@@ -64,7 +38,7 @@ struct Eres2Model : MvModelBase {
     float* stem_b = nullptr;
     std::vector<Block> layers[4];
     // ERes2Net: layer{1,2,3}_downsample + fuse_mode{12,123,1234}; ERes2NetV2: layer3_ds + fuse34 (slot 2)
-    C2Layer ds[3];
+    S16Conv ds[3];
     AffLayer top_fuse[3];
     float* seg1_w = nullptr;
     float* seg1_b = nullptr;
@@ -73,52 +47,6 @@ struct Eres2Model : MvModelBase {
     int final_c = 0, final_h = 0;
 
     // ---- packing -----------------------------------------------------------------------------------------------
-    // w: [cout][cin][ks][ks]; out channel c -> row out_pos[c] scaled by oscale[c]; in channel c -> column in_pos[c]
-    int pack(const std::vector<float>& w, int cout, int cin, int ks, const std::vector<float>& oscale, const std::vector<float>& obias,
-             const std::vector<int>& out_pos, int cout16, const std::vector<int>& in_pos, int cin16, int stride, C2Layer* L) {
-        const int taps = ks * ks;
-        std::vector<float> packed((size_t)cout16 * taps * cin16, 0.0f);
-        std::vector<float> bias((size_t)cout16, 0.0f);
-        for (int co = 0; co < cout; ++co) {
-            const float s = oscale.empty() ? 1.0f : oscale[co];
-            bias[out_pos[co]] = obias.empty() ? 0.0f : obias[co];
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < taps; ++t) {
-                    packed[((size_t)out_pos[co] * taps + t) * cin16 + in_pos[ci]] = w[((size_t)co * cin + ci) * taps + t] * s;
-                }
-        }
-        std::vector<half_t> split((size_t)conv2ds_packed_floats(cout16, cin16, ks) * 2);
-        L->oscale = conv2ds_pack_host(packed.data(), cout16, cin16, ks, split.data());
-        L->w = static_cast<half_t*>(dev_alloc(split.size() * sizeof(half_t)));
-        L->bias = upload(bias);
-        if (L->w == nullptr || L->bias == nullptr) return fail(MV_ERR_HIP, "eres2net create: out of device memory");
-        MV_HIP_OK(hipMemcpy(L->w, split.data(), split.size() * sizeof(half_t), hipMemcpyHostToDevice));
-        L->cin16 = cin16;
-        L->cout16 = cout16;
-        L->cin = cin;
-        L->cout = cout;
-        L->ks = ks;
-        L->stride = stride;
-        return MV_OK;
-    }
-
-    // conv (no bias) followed by BatchNorm `bn` (empty: none)
-    int make_conv_bn(const Weights& w, const std::string& conv, const std::string& bn, int cout, int cin, int ks, int stride,
-                     const std::vector<int>& out_pos, int cout16, const std::vector<int>& in_pos, int cin16, C2Layer* L) {
-        std::vector<float> W, s, t, cb;
-        int rc;
-        if ((rc = w.host(conv + ".weight", (int64_t)cout * cin * ks * ks, W))) return rc;
-        if (w.has(conv + ".bias") && (rc = w.host(conv + ".bias", cout, cb))) return rc;
-        if (!bn.empty()) {
-            if ((rc = fold_bn(w, bn, cout, s, t, 1e-5f))) return rc;
-            if (!cb.empty())
-                for (int c = 0; c < cout; ++c) t[c] += cb[c] * s[c];
-        } else if (!cb.empty()) {
-            t = cb;
-        }
-        return pack(W, cout, cin, ks, s, t, out_pos, cout16, in_pos, cin16, stride, L);
-    }
-
     int make_aff(const Weights& w, const std::string& prefix, int ch, AffLayer* A) {
         const int r = 4, inter = ch / r;
         MV_REQUIRE(inter > 0, "eres2net: AFF needs at least 4 channels");
@@ -128,11 +56,10 @@ struct Eres2Model : MvModelBase {
         std::vector<int> in_pos((size_t)2 * ch);
         for (int c = 0; c < 2 * ch; ++c) in_pos[c] = c < ch ? c : A->chp + (c - ch);
         int rc;
-        if ((rc = make_conv_bn(w, prefix + ".local_att.0", prefix + ".local_att.1", inter, 2 * ch, 1, 1, dense_map(inter), A->inter16,
-                               in_pos, 2 * A->chp, &A->att1)))
+        if ((rc = make_s16_conv_bn(this, w, "eres2net", prefix + ".local_att.0", prefix + ".local_att.1", inter, 2 * ch, 1, 1, s16_dense_map(inter),
+                                   A->inter16, in_pos, 2 * A->chp, &A->att1)))
             return rc;
-        return make_conv_bn(w, prefix + ".local_att.3", prefix + ".local_att.4", ch, inter, 1, 1, dense_map(ch), A->chp, dense_map(inter),
-                            A->inter16, &A->att2);
+        return make_s16_conv_bn(this, w, "eres2net", prefix + ".local_att.3", prefix + ".local_att.4", ch, inter, 1, 1, &A->att2);
     }
 
     int make_block(const Weights& w, const std::string& p, int in_planes, int planes, int stride, bool aff, Block* b) {
@@ -144,29 +71,26 @@ struct Eres2Model : MvModelBase {
         b->in_c16 = (int)round_up(in_planes, 16);
         const int out_planes = planes * cfg.expansion;
         b->out_c16 = (int)round_up(out_planes, 16);
-        const std::vector<int> gmap = grouped_map(width, scale, b->wpad);
+        const std::vector<int> gmap = s16_grouped_map(width, scale, b->wpad);
+        const char* who = "eres2net";
         int rc;
-        if ((rc = make_conv_bn(w, p + ".conv1", p + ".bn1", width * scale, in_planes, 1, stride, gmap, scale * b->wpad, dense_map(in_planes),
-                               b->in_c16, &b->conv1)))
+        if ((rc = make_s16_conv_bn(this, w, who, p + ".conv1", p + ".bn1", width * scale, in_planes, 1, stride, gmap, scale * b->wpad,
+                                   s16_dense_map(in_planes), b->in_c16, &b->conv1)))
             return rc;
         b->convs.resize(scale);
         for (int i = 0; i < scale; ++i)
-            if ((rc = make_conv_bn(w, p + ".convs." + std::to_string(i), p + ".bns." + std::to_string(i), width, width, 3, 1,
-                                   dense_map(width), b->wpad, dense_map(width), b->wpad, &b->convs[i])))
+            if ((rc = make_s16_conv_bn(this, w, who, p + ".convs." + std::to_string(i), p + ".bns." + std::to_string(i), width, width, 3, 1, &b->convs[i])))
                 return rc;
         if (aff) {
             b->fuse.resize(scale - 1);
             for (int j = 0; j < scale - 1; ++j)
                 if ((rc = make_aff(w, p + ".fuse_models." + std::to_string(j), width, &b->fuse[j]))) return rc;
         }
-        if ((rc = make_conv_bn(w, p + ".conv3", p + ".bn3", out_planes, width * scale, 1, 1, dense_map(out_planes), b->out_c16, gmap,
-                               scale * b->wpad, &b->conv3)))
+        if ((rc = make_s16_conv_bn(this, w, who, p + ".conv3", p + ".bn3", out_planes, width * scale, 1, 1, s16_dense_map(out_planes), b->out_c16, gmap,
+                                   scale * b->wpad, &b->conv3)))
             return rc;
         b->has_shortcut = stride != 1 || in_planes != out_planes;
-        if (b->has_shortcut)
-            if ((rc = make_conv_bn(w, p + ".shortcut.0", p + ".shortcut.1", out_planes, in_planes, 1, stride, dense_map(out_planes),
-                                   b->out_c16, dense_map(in_planes), b->in_c16, &b->shortcut)))
-                return rc;
+        if (b->has_shortcut) return make_s16_conv_bn(this, w, who, p + ".shortcut.0", p + ".shortcut.1", out_planes, in_planes, 1, stride, &b->shortcut);
         return MV_OK;
     }
 
@@ -183,15 +107,8 @@ struct Eres2Model : MvModelBase {
         embd_dim = c.embd_dim;
         input_size = c.input_size;
         int rc;
-        {   // conv1 + bn1 + relu (eres2net.py:196-201, 270): fp32 weights for the VALU stem kernel
-            std::vector<float> W, s, t;
-            if ((rc = w.host("conv1.weight", (int64_t)m * 9, W)) || (rc = fold_bn(w, "bn1", m, s, t, 1e-5f))) return rc;
-            for (int co = 0; co < m; ++co)
-                for (int j = 0; j < 9; ++j) W[(size_t)co * 9 + j] *= s[co];
-            stem_w = upload(W);
-            stem_b = upload(t);
-            if (stem_w == nullptr || stem_b == nullptr) return fail(MV_ERR_HIP, "eres2net create: upload failed");
-        }
+        // conv1 + bn1 + relu (eres2net.py:196-201, 270): fp32 weights for the VALU stem kernel
+        if ((rc = fold_s16_stem(this, w, "eres2net", m, 9, &stem_w, &stem_b))) return rc;
         int in_planes = m;
         for (int l = 0; l < 4; ++l) {
             const int planes = m << l;
@@ -211,16 +128,12 @@ struct Eres2Model : MvModelBase {
             const char* fn[3] = {"fuse_mode12", "fuse_mode123", "fuse_mode1234"};
             for (int i = 0; i < 3; ++i) {
                 const int cin = (m << i) * e, cout = (m << (i + 1)) * e;
-                if ((rc = make_conv_bn(w, dsn[i], "", cout, cin, 3, 2, dense_map(cout), (int)round_up(cout, 16), dense_map(cin),
-                                       (int)round_up(cin, 16), &ds[i])) ||
-                    (rc = make_aff(w, fn[i], cout, &top_fuse[i])))
+                if ((rc = make_s16_conv_bn(this, w, "eres2net", dsn[i], "", cout, cin, 3, 2, &ds[i])) || (rc = make_aff(w, fn[i], cout, &top_fuse[i])))
                     return rc;
             }
         } else {
             const int cin = (m << 2) * e, cout = (m << 3) * e;
-            if ((rc = make_conv_bn(w, "layer3_ds", "", cout, cin, 3, 2, dense_map(cout), (int)round_up(cout, 16), dense_map(cin),
-                                   (int)round_up(cin, 16), &ds[2])) ||
-                (rc = make_aff(w, "fuse34", cout, &top_fuse[2])))
+            if ((rc = make_s16_conv_bn(this, w, "eres2net", "layer3_ds", "", cout, cin, 3, 2, &ds[2])) || (rc = make_aff(w, "fuse34", cout, &top_fuse[2])))
                 return rc;
         }
         final_c = (m << 3) * e;
@@ -239,7 +152,6 @@ struct Eres2Model : MvModelBase {
         float *stats, *emb_a, *lin_ws;
         size_t bytes, lin_ws_floats;
     };
-    static int down(int n) { return (n - 1) / 2 + 1; }
 
     Ws carve(void* base, int B, int T) const {
         Carver c(base);
@@ -248,8 +160,8 @@ struct Eres2Model : MvModelBase {
         H[0] = cfg.input_size;
         W[0] = T;
         for (int l = 1; l < 4; ++l) {
-            H[l] = down(H[l - 1]);
-            W[l] = down(W[l - 1]);
+            H[l] = s16_down(H[l - 1]);
+            W[l] = s16_down(W[l - 1]);
         }
         size_t max_io = 0, max_a = 0, max_r = 0, max_t = 0, max_h = 0;
         for (int l = 0; l < 4; ++l) {
@@ -266,25 +178,24 @@ struct Eres2Model : MvModelBase {
         }
         for (int i = 0; i < 3; ++i)
             if (top_fuse[i].ch) max_h = std::max(max_h, (size_t)B * H[i + 1] * W[i + 1] * top_fuse[i].inter16);
-        const size_t slack = 64;  // the loader reads whole 16-byte chunks
-        s.ping[0] = c.take<float>(max_io + slack);
-        s.ping[1] = c.take<float>(max_io + slack);
-        s.a = c.take<float>(max_a + slack);
-        s.bc = c.take<float>(max_a + slack);
-        s.r = c.take<float>(max_r + slack);
-        s.t = c.take<float>(max_t + slack);
-        s.t2 = c.take<float>(max_t + slack);
-        s.hh = c.take<float>(max_h + slack);
-        for (int l = 0; l < 4; ++l) s.out[l] = c.take<float>((size_t)B * H[l] * W[l] * layers[l].back().out_c16 + slack);
+        s.ping[0] = c.take<float>(max_io + S16_SLACK);
+        s.ping[1] = c.take<float>(max_io + S16_SLACK);
+        s.a = c.take<float>(max_a + S16_SLACK);
+        s.bc = c.take<float>(max_a + S16_SLACK);
+        s.r = c.take<float>(max_r + S16_SLACK);
+        s.t = c.take<float>(max_t + S16_SLACK);
+        s.t2 = c.take<float>(max_t + S16_SLACK);
+        s.hh = c.take<float>(max_h + S16_SLACK);
+        for (int l = 0; l < 4; ++l) s.out[l] = c.take<float>((size_t)B * H[l] * W[l] * layers[l].back().out_c16 + S16_SLACK);
         size_t max_ds = 0, max_f = 0;
         for (int i = 0; i < 3; ++i)
             if (top_fuse[i].ch) {
                 max_ds = std::max(max_ds, (size_t)B * H[i + 1] * W[i + 1] * ds[i].cout16);
                 max_f = std::max(max_f, (size_t)B * H[i + 1] * W[i + 1] * top_fuse[i].chp);
             }
-        s.dsb = c.take<float>(max_ds + slack);
-        s.fuse[0] = c.take<float>(max_f + slack);
-        s.fuse[1] = c.take<float>(max_f + slack);
+        s.dsb = c.take<float>(max_ds + S16_SLACK);
+        s.fuse[0] = c.take<float>(max_f + S16_SLACK);
+        s.fuse[1] = c.take<float>(max_f + S16_SLACK);
         s.stats = c.take<float>((size_t)B * 2 * final_c * final_h);
         s.emb_a = c.take<float>((size_t)B * cfg.embd_dim);
         s.lin_ws_floats = linear_f32_splitk_floats(B, 2 * final_c * final_h, cfg.embd_dim);   // K slices of seg_1 (linear.hip)
@@ -300,63 +211,66 @@ struct Eres2Model : MvModelBase {
     }
 
     // ---- launches ----------------------------------------------------------------------------------------------
-    // x2 != nullptr: the channels behind the first cin1 come from x2 (AFF concatenation); y2 != nullptr: second output y + add
-    static int conv(const C2Layer& L, const float* x, int64_t ldx, const float* x2, int64_t ldx2, int cin1, float* y, int64_t ldy, int B, int H,
-                    int W, int epi, float lo, float hi, const float* res, int64_t ldres, const float* res2, int64_t ldres2, hipStream_t st,
-                    const float* add = nullptr, int64_t ldadd = 0, float* y2 = nullptr, int64_t ldy2 = 0) {
-        MvConv2dsDesc d{};
-        d.x = x; d.x2 = x2; d.cin1 = cin1; d.ldx = ldx; d.ldx2 = ldx2;
-        d.w = L.w; d.bias = L.bias; d.oscale = L.oscale; d.res = res; d.res2 = res2; d.ldres = ldres; d.ldres2 = ldres2;
-        d.add = add; d.ldadd = ldadd; d.y2 = y2; d.ldy2 = ldy2;
-        d.y = y; d.ldy = ldy; d.B = B; d.H = H; d.W = W; d.cin16 = L.cin16; d.cout16 = L.cout16; d.ks = L.ks; d.stride = L.stride;
-        d.epi = epi; d.lo = lo; d.hi = hi;
-        d.cin_alg = L.cin; d.cout_alg = L.cout;
-        return conv2ds_launch(d, st);
-    }
-
     // out = xa * (1 + tanh(att)) + ya * (1 - tanh(att)),  att = BN(conv(SiLU(BN(conv(cat(xa, ya))))))   (eres2net.py:47-52)
     static int aff(const AffLayer& A, const float* xa, int64_t ldxa, const float* ya, int64_t ldya, float* hidden, float* out,
                    int64_t ldo, int B, int H, int W, hipStream_t st) {
-        int rc = conv(A.att1, xa, ldxa, ya, ldya, A.chp, hidden, A.inter16, B, H, W, MV_EPI_SILU, 0.0f, 0.0f, nullptr, 0, nullptr, 0, st);
+        MvConv2dsDesc d = s16_conv_desc(A.att1, xa, ldxa, hidden, A.inter16, B, H, W);
+        d.x2 = ya; d.ldx2 = ldya; d.cin1 = A.chp;   // the channels behind the first chp come from ya
+        d.epi = MV_EPI_SILU;
+        int rc = conv2ds_launch(d, st);
         if (rc != MV_OK) return rc;
-        return conv(A.att2, hidden, A.inter16, nullptr, 0, 0, out, ldo, B, H, W, MV_EPI_AFF, 0.0f, 0.0f, xa, ldxa, ya, ldya, st);
+        d = s16_conv_desc(A.att2, hidden, A.inter16, out, ldo, B, H, W);
+        d.epi = MV_EPI_AFF; d.res = xa; d.ldres = ldxa; d.res2 = ya; d.ldres2 = ldya;
+        return conv2ds_launch(d, st);
     }
 
+    // (d.peak stays null in every launch of this model: it has no peak word and runs the instantiations without one)
     int run_block(const Block& b, const float* x, float* y, const Ws& s, int B, int Hin, int Win, hipStream_t st) const {
         const float NEG = -3.0e38f, POS = 3.0e38f;
-        const int Ho = b.stride == 2 ? down(Hin) : Hin, Wo = b.stride == 2 ? down(Win) : Win;
+        const int Ho = b.stride == 2 ? s16_down(Hin) : Hin, Wo = b.stride == 2 ? s16_down(Win) : Win;
         const int64_t lda = (int64_t)scale * b.wpad;
         int rc;
         // out = relu(bn1(conv1(x)))   (eres2net.py:86-88)
-        if ((rc = conv(b.conv1, x, b.in_c16, nullptr, 0, 0, s.a, lda, B, Hin, Win, MV_EPI_CLAMP, 0.0f, 20.0f, nullptr, 0, nullptr, 0, st)))
-            return rc;
+        MvConv2dsDesc d = s16_conv_desc(b.conv1, x, b.in_c16, s.a, lda, B, Hin, Win);
+        d.lo = 0.0f; d.hi = 20.0f;
+        if ((rc = conv2ds_launch(d, st))) return rc;
         float* const sums[2] = {s.t, s.t2};
         for (int i = 0; i < scale; ++i) {
             const float* spx = s.a + (int64_t)i * b.wpad;
             float* dst = s.bc + (int64_t)i * b.wpad;
             if (b.fuse.empty()) {
                 // sp = sp + spx[i] (eres2net.py:92) was formed by the previous conv's second output; this one forms the next
-                const bool more = i + 1 < scale;
-                rc = conv(b.convs[i], i == 0 ? spx : sums[(i - 1) & 1], i == 0 ? lda : b.wpad, nullptr, 0, 0, dst, lda, B, Ho, Wo, MV_EPI_CLAMP, 0.0f, 20.0f,
-                          nullptr, 0, nullptr, 0, st, more ? spx + b.wpad : nullptr, lda, more ? sums[i & 1] : nullptr, b.wpad);
+                d = s16_conv_desc(b.convs[i], i == 0 ? spx : sums[(i - 1) & 1], i == 0 ? lda : b.wpad, dst, lda, B, Ho, Wo);
+                if (i + 1 < scale) {
+                    d.add = spx + b.wpad; d.ldadd = lda; d.y2 = sums[i & 1]; d.ldy2 = b.wpad;
+                }
             } else if (i == 0) {
-                rc = conv(b.convs[0], spx, lda, nullptr, 0, 0, dst, lda, B, Ho, Wo, MV_EPI_CLAMP, 0.0f, 20.0f, nullptr, 0, nullptr, 0, st);
+                d = s16_conv_desc(b.convs[0], spx, lda, dst, lda, B, Ho, Wo);
             } else {                      // sp = fuse_models[i-1](sp, spx[i])   (eres2net.py:152)
                 if ((rc = aff(b.fuse[i - 1], dst - b.wpad, lda, spx, lda, s.hh, s.t, b.wpad, B, Ho, Wo, st))) return rc;
-                rc = conv(b.convs[i], s.t, b.wpad, nullptr, 0, 0, dst, lda, B, Ho, Wo, MV_EPI_CLAMP, 0.0f, 20.0f, nullptr, 0, nullptr, 0, st);
+                d = s16_conv_desc(b.convs[i], s.t, b.wpad, dst, lda, B, Ho, Wo);
             }
-            if (rc != MV_OK) return rc;
-        }
-        const float* resid = x;
-        int64_t ldr = b.in_c16;
-        if (b.has_shortcut) {
-            if ((rc = conv(b.shortcut, x, b.in_c16, nullptr, 0, 0, s.r, b.out_c16, B, Hin, Win, MV_EPI_CLAMP, NEG, POS, nullptr, 0, nullptr, 0, st)))
-                return rc;
-            resid = s.r;
-            ldr = b.out_c16;
+            d.lo = 0.0f; d.hi = 20.0f;
+            if ((rc = conv2ds_launch(d, st))) return rc;
         }
         // relu(bn3(conv3(cat)) + residual)   (eres2net.py:101-106)
-        return conv(b.conv3, s.bc, lda, nullptr, 0, 0, y, b.out_c16, B, Ho, Wo, MV_EPI_CLAMP, 0.0f, 20.0f, resid, ldr, nullptr, 0, st);
+        MvConv2dsDesc d3 = s16_conv_desc(b.conv3, s.bc, lda, y, b.out_c16, B, Ho, Wo);
+        d3.res = x; d3.ldres = b.in_c16;
+        if (b.has_shortcut) {
+            d = s16_conv_desc(b.shortcut, x, b.in_c16, s.r, b.out_c16, B, Hin, Win);
+            d.lo = NEG; d.hi = POS;
+            if ((rc = conv2ds_launch(d, st))) return rc;
+            d3.res = s.r; d3.ldres = b.out_c16;
+        }
+        d3.lo = 0.0f; d3.hi = 20.0f;
+        return conv2ds_launch(d3, st);
+    }
+
+    // layer{1,2,3}_downsample / layer3_ds: a 3x3 stride-2 conv with no BN and no activation
+    static int downsample(const S16Conv& L, const float* x, int64_t ldx, float* y, int B, int H, int W, hipStream_t st) {
+        MvConv2dsDesc d = s16_conv_desc(L, x, ldx, y, L.cout16, B, H, W);
+        d.lo = -3.0e38f; d.hi = 3.0e38f;
+        return conv2ds_launch(d, st);
     }
 
     int forward(const float* feats, int B, int T, float* emb, void* ws, size_t ws_bytes, hipStream_t st) const override {
@@ -364,7 +278,6 @@ struct Eres2Model : MvModelBase {
         MV_REQUIRE(B > 0 && T >= 9, "eres2net forward: needs at least 9 frames (two time steps after three stride-2 stages)");
         const Ws s = carve(ws, B, T);
         if (s.bytes > ws_bytes) return fail(MV_ERR_WORKSPACE, "eres2net forward: workspace too small");
-        const float NEG = -3.0e38f, POS = 3.0e38f;
         int rc;
         int H = cfg.input_size, W = T;
         int Hs[4], Wsz[4];
@@ -379,8 +292,8 @@ struct Eres2Model : MvModelBase {
                 float* dst = j == nb - 1 ? s.out[l] : s.ping[pp];
                 if ((rc = run_block(b, cur, dst, s, B, H, W, st))) return rc;
                 if (b.stride == 2) {
-                    H = down(H);
-                    W = down(W);
+                    H = s16_down(H);
+                    W = s16_down(W);
                 }
                 cur = dst;
                 if (j != nb - 1) pp ^= 1;
@@ -395,9 +308,7 @@ struct Eres2Model : MvModelBase {
             const float* prev = s.out[0];
             int64_t prev_ld = layers[0].back().out_c16;
             for (int i = 0; i < 3; ++i) {
-                if ((rc = conv(ds[i], prev, prev_ld, nullptr, 0, 0, s.dsb, ds[i].cout16, B, Hs[i], Wsz[i], MV_EPI_CLAMP, NEG, POS, nullptr, 0,
-                               nullptr, 0, st)))
-                    return rc;
+                if ((rc = downsample(ds[i], prev, prev_ld, s.dsb, B, Hs[i], Wsz[i], st))) return rc;
                 float* fo = s.fuse[i & 1];
                 if ((rc = aff(top_fuse[i], s.out[i + 1], layers[i + 1].back().out_c16, s.dsb, ds[i].cout16, s.hh, fo, top_fuse[i].chp, B,
                               Hs[i + 1], Wsz[i + 1], st)))
@@ -409,8 +320,7 @@ struct Eres2Model : MvModelBase {
             pooled_ld = prev_ld;
         } else {
             // fuse34(out4, layer3_ds(out3))   (eres2net.py:446-447)
-            if ((rc = conv(ds[2], s.out[2], layers[2].back().out_c16, nullptr, 0, 0, s.dsb, ds[2].cout16, B, Hs[2], Wsz[2], MV_EPI_CLAMP, NEG,
-                           POS, nullptr, 0, nullptr, 0, st)) ||
+            if ((rc = downsample(ds[2], s.out[2], layers[2].back().out_c16, s.dsb, B, Hs[2], Wsz[2], st)) ||
                 (rc = aff(top_fuse[2], s.out[3], layers[3].back().out_c16, s.dsb, ds[2].cout16, s.hh, s.fuse[0], top_fuse[2].chp, B, Hs[3],
                           Wsz[3], st)))
                 return rc;
@@ -434,15 +344,7 @@ struct Eres2Model : MvModelBase {
 extern "C" {
 
 int mv_eres2net_create(const MvEres2Cfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_eres2net_create: null argument");
-    mv::Weights w;
-    int rc = w.init(tensors, num_tensors);
-    if (rc != MV_OK) return rc;
-    auto m = std::make_unique<mv::Eres2Model>();
-    rc = m->create(*cfg, w);
-    if (rc != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<mv::MvModelBase*>(m.release()));
-    return MV_OK;
+    return mv::create_model<mv::Eres2Model>("mv_eres2net_create", cfg, tensors, num_tensors, out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
-// Internal model scaffolding shared by model.hip (EcapaTdnn, TDNN) and campplus.hip (CAM++).
+// Internal model scaffolding shared by every backbone: model.hip (EcapaTdnn, TDNN), campplus.hip (CAM++) and, through s16model.h, the S16 backbones.
 #pragma once
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -119,5 +120,24 @@ struct Pooling {
     // EcapaTdnn's norm behind the head: BatchNorm1d wrapped in a module of the reference's behind ASP, a plain one behind the others (ecapa_tdnn.py:229-250)
     const char* ecapa_bn_name() const { return type == MV_POOL_ASP ? "asp_bn.norm" : "asp_bn"; }
 };
+
+// the mv_*_create* entry points: the checks under the entry point's own name `fn`, the state_dict, the model.  pooling_type: the one argument of
+// the models whose create() takes a pooling head (its range is checked here), none for the others
+template <typename Model, typename Cfg, typename... PoolingType>
+int create_model(const char* fn, const Cfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out, PoolingType... pooling_type) {
+    static_assert(sizeof...(PoolingType) <= 1, "at most the pooling_type");
+    MV_REQUIRE(cfg != nullptr && out != nullptr, std::string(fn) + ": null argument");
+    if constexpr (sizeof...(PoolingType) == 1)
+        if (const int32_t p = (pooling_type, ...); p < MV_POOL_ASP || p > MV_POOL_TSP)
+            return fail(MV_ERR_INVALID_ARGUMENT, std::string(fn) + ": pooling_type " + std::to_string(p) +
+                                                     " is not MV_POOL_ASP (0), MV_POOL_SAP (1), MV_POOL_TAP (2) or MV_POOL_TSP (3)");
+    int rc;
+    Weights w;
+    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
+    auto m = std::make_unique<Model>();
+    if ((rc = m->create(*cfg, w, pooling_type...)) != MV_OK) return rc;
+    *out = reinterpret_cast<MvModel*>(static_cast<MvModelBase*>(m.release()));
+    return MV_OK;
+}
 
 }  // namespace mv

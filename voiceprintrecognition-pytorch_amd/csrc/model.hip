@@ -9,7 +9,6 @@
 // forward(): a fixed sequence of kernel launches on the caller's stream over a caller-provided workspace; no
 // allocation, no synchronisation, so it can be captured in a hipGraph.
 #include <map>
-#include <memory>
 #include <vector>
 
 #include "kernels.h"
@@ -793,44 +792,28 @@ struct TdnnModel : MvModelBase {
     }
 };
 
-// the mv_*_create* entry points: the checks under the entry point's own name `fn`, the state_dict, the model
-template <typename Model, typename Cfg>
-static int create_model(const char* fn, const Cfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    MV_REQUIRE(cfg != nullptr && out != nullptr, std::string(fn) + ": null argument");
-    if (pooling_type < MV_POOL_ASP || pooling_type > MV_POOL_TSP)
-        return fail(MV_ERR_INVALID_ARGUMENT, std::string(fn) + ": pooling_type " + std::to_string(pooling_type) +
-                                                 " is not MV_POOL_ASP (0), MV_POOL_SAP (1), MV_POOL_TAP (2) or MV_POOL_TSP (3)");
-    int rc;
-    Weights w;
-    if ((rc = w.init(tensors, num_tensors)) != MV_OK) return rc;
-    auto m = std::make_unique<Model>();
-    if ((rc = m->create(*cfg, w, pooling_type)) != MV_OK) return rc;
-    *out = reinterpret_cast<MvModel*>(static_cast<MvModelBase*>(m.release()));
-    return MV_OK;
-}
-
 }  // namespace mv
 
 extern "C" {
 
 int mv_ecapa_create(const MvEcapaCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    return mv::create_model<mv::EcapaModel>("mv_ecapa_create", cfg, MV_POOL_ASP, tensors, num_tensors, out);
+    return mv::create_model<mv::EcapaModel>("mv_ecapa_create", cfg, tensors, num_tensors, out, MV_POOL_ASP);
 }
 
 int mv_ecapa_create_pooled(const MvEcapaCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    return mv::create_model<mv::EcapaModel>("mv_ecapa_create_pooled", cfg, pooling_type, tensors, num_tensors, out);
+    return mv::create_model<mv::EcapaModel>("mv_ecapa_create_pooled", cfg, tensors, num_tensors, out, pooling_type);
 }
 
 int mv_ecapa_create_ex(const MvEcapaCfgEx* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    return mv::create_model<mv::EcapaModel>("mv_ecapa_create_ex", cfg, pooling_type, tensors, num_tensors, out);
+    return mv::create_model<mv::EcapaModel>("mv_ecapa_create_ex", cfg, tensors, num_tensors, out, pooling_type);
 }
 
 int mv_tdnn_create(const MvTdnnCfg* cfg, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    return mv::create_model<mv::TdnnModel>("mv_tdnn_create", cfg, MV_POOL_ASP, tensors, num_tensors, out);
+    return mv::create_model<mv::TdnnModel>("mv_tdnn_create", cfg, tensors, num_tensors, out, MV_POOL_ASP);
 }
 
 int mv_tdnn_create_pooled(const MvTdnnCfg* cfg, int32_t pooling_type, const MvTensorRef* tensors, int32_t num_tensors, MvModel** out) {
-    return mv::create_model<mv::TdnnModel>("mv_tdnn_create_pooled", cfg, pooling_type, tensors, num_tensors, out);
+    return mv::create_model<mv::TdnnModel>("mv_tdnn_create_pooled", cfg, tensors, num_tensors, out, pooling_type);
 }
 
 int mv_model_destroy(MvModel* m) {
