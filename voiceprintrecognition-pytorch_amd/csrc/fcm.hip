@@ -392,7 +392,7 @@ __global__ __launch_bounds__(256) void fcm_band_kernel(FcmConvArgs a, int n_ttil
     }
 }
 
-// fp32 head (campplus.hip): [B, F8, T, 32] fp32 -> [B, T, F8, 32] fp16; thread = 8 maps of one (b, f, t)
+// fp32 head (campp_head.hip): [B, F8, T, 32] fp32 -> [B, T, F8, 32] fp16; thread = 8 maps of one (b, f, t)
 // S16: the maps in the split-fp16 form of conv2ds.hip (s16map.h) instead of fp32
 template <bool S16>
 __global__ __launch_bounds__(256) void fcm_rows_from_f32_kernel(const float* maps, half_t* rows, int64_t n8, int T, int F8, float scale) {

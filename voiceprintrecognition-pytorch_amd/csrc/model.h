@@ -1,4 +1,4 @@
-// Internal model scaffolding shared by every backbone: model.hip (EcapaTdnn, TDNN), campplus.hip (CAM++) and, through s16model.h, the S16 backbones.
+// Internal model scaffolding shared by every backbone: model.hip (EcapaTdnn, TDNN), campplus.hip (CAM++, with campp_head.hip and campp_probe.hip) and, through s16model.h, the S16 backbones.
 #pragma once
 #include <map>
 #include <memory>

@@ -11,7 +11,7 @@ constexpr float CS_XSCALE_INV = 1.0f / 64.0f;
 // Stored values are clamped to the fp16 range (|V| <= 65504, i.e. |value| <= 1023.5 at the scale of 64): the split SATURATES there.  A NaN is not a
 // number to clamp -- fminf / fmaxf would turn it into a bound and hide it -- so it travels on.  Kernels that store S16 maps can report the largest
 // |V| they wanted to store (before the clamp) to a device word (s16_peak_*: the float's bits, monotonic under an unsigned max), which is how a
-// handle learns that its maps need a smaller scale (campplus.hip: the exact head's gain) and how saturation on real inputs becomes visible.
+// handle learns that its maps need a smaller scale (campp_probe.hip: the exact head's gain) and how saturation on real inputs becomes visible.
 __device__ __forceinline__ float s16_clamp(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
 __device__ __forceinline__ float s16_clamp(float v) { return s16_clamp(v, -65504.0f, 65504.0f); }
 __device__ __forceinline__ float s16_peak_of(float pk, const float4v& X) {   // (fmaxf drops NaNs: they are reported by the data itself)

@@ -1,4 +1,4 @@
-// Host-side scaffolding shared by the backbones that run conv2ds_kernel on S16 maps: eres2net.hip, resnet_se.hip, res2net.hip (s16model.hip).
+// Host-side scaffolding shared by what runs conv2ds_kernel on S16 maps: eres2net.hip, resnet_se.hip, res2net.hip, CAM++'s exact head (campp_head.hip).
 // The packed-conv record and its packer, the fp32 stem's weights, the launch descriptor builder, the peak word and the reshape -> pooling -> linear head.
 // A model file keeps what is its own: block structs, make_block, cfg checks, the carve of its maps, run_block and forward.
 #pragma once
@@ -21,13 +21,15 @@ std::vector<int> s16_grouped_map(int width, int scale, int wpad);
 
 // conv [cout][cin][ks][ks] (its bias optional) followed by BatchNorm `bn` (eps 1e-5; empty: none), folded and packed for conv2ds_kernel:
 // out channel c -> row out_pos[c], in channel c -> column in_pos[c], zeros elsewhere.  `who` names the model in the messages.
+// bias_host (optional): the uploaded bias [cout16] once more, for a handle that re-uploads it scaled (CAM++'s head gain).
 int make_s16_conv_bn(MvModelBase* m, const Weights& w, const char* who, const std::string& conv, const std::string& bn, int cout, int cin, int ks,
-                     int stride, const std::vector<int>& out_pos, int cout16, const std::vector<int>& in_pos, int cin16, S16Conv* L);
+                     int stride, const std::vector<int>& out_pos, int cout16, const std::vector<int>& in_pos, int cin16, S16Conv* L,
+                     std::vector<float>* bias_host = nullptr);
 // channels in their own order, zero rows / columns up to the next multiples of 16
 inline int make_s16_conv_bn(MvModelBase* m, const Weights& w, const char* who, const std::string& conv, const std::string& bn, int cout, int cin,
-                            int ks, int stride, S16Conv* L) {
+                            int ks, int stride, S16Conv* L, std::vector<float>* bias_host = nullptr) {
     return make_s16_conv_bn(m, w, who, conv, bn, cout, cin, ks, stride, s16_dense_map(cout), (int)round_up(cout, 16), s16_dense_map(cin),
-                            (int)round_up(cin, 16), L);
+                            (int)round_up(cin, 16), L, bias_host);
 }
 
 // conv1 + bn1 of the fp32 VALU stem kernels: conv1.weight [C][taps] times the BN scale, the BN shift as bias
@@ -45,6 +47,17 @@ constexpr size_t S16_SLACK = 64;                         // floats behind every 
 struct S16Peak {
     // *pool_type: pooling_type without the flag, refused unless one of MV_POOL_*
     int create(MvModelBase* m, int cfg_pooling_type, const char* who, int* pool_type);
+    int alloc(MvModelBase* m, const char* who);   // the word, cleared: all create() does for a tracked handle (CAM++: no flag, its own info keys)
+    int clear() const {   // the word (it must exist) back to 0
+        MV_HIP_OK(hipMemset(d_peak, 0, sizeof(unsigned)));
+        return MV_OK;
+    }
+    int raw(float* v) const {   // the word (it must exist) as it stands, as a float; no wait for the device
+        unsigned bits = 0;
+        MV_HIP_OK(hipMemcpy(&bits, d_peak, sizeof(bits), hipMemcpyDeviceToHost));
+        *v = __builtin_bit_cast(float, bits);
+        return MV_OK;
+    }
     unsigned* word() const { return d_peak; }
     // true: `key` is MV_INFO_S16_PEAK / _SATURATED and *rc, *value are its answer (-1 without a word); waits for the device, not a hot-path call
     bool info(int key, float* value, int* rc) const;

@@ -18,7 +18,8 @@ std::vector<int> s16_grouped_map(int width, int scale, int wpad) {
 }
 
 int make_s16_conv_bn(MvModelBase* m, const Weights& w, const char* who, const std::string& conv, const std::string& bn, int cout, int cin, int ks,
-                     int stride, const std::vector<int>& out_pos, int cout16, const std::vector<int>& in_pos, int cin16, S16Conv* L) {
+                     int stride, const std::vector<int>& out_pos, int cout16, const std::vector<int>& in_pos, int cin16, S16Conv* L,
+                     std::vector<float>* bias_host) {
     std::vector<float> W, s, t, cb;
     int rc;
     if ((rc = w.host(conv + ".weight", (int64_t)cout * cin * ks * ks, W))) return rc;
@@ -52,6 +53,7 @@ int make_s16_conv_bn(MvModelBase* m, const Weights& w, const char* who, const st
     L->cout = cout;
     L->ks = ks;
     L->stride = stride;
+    if (bias_host != nullptr) *bias_host = bias;
     return MV_OK;
 }
 
@@ -97,11 +99,13 @@ int S16Peak::create(MvModelBase* m, int cfg_pooling_type, const char* who, int* 
     if (*pool_type < MV_POOL_ASP || *pool_type > MV_POOL_TSP)
         return fail(MV_ERR_INVALID_ARGUMENT, std::string(who) + ": pooling_type " + std::to_string(*pool_type) +
                                                  " is not MV_POOL_ASP (0), MV_POOL_SAP (1), MV_POOL_TAP (2) or MV_POOL_TSP (3)");
-    if (!track) return MV_OK;
+    return track ? alloc(m, who) : MV_OK;
+}
+
+int S16Peak::alloc(MvModelBase* m, const char* who) {
     d_peak = static_cast<unsigned*>(m->dev_alloc(sizeof(unsigned)));
     if (d_peak == nullptr) return fail(MV_ERR_HIP, std::string(who) + " create: out of device memory");
-    MV_HIP_OK(hipMemset(d_peak, 0, sizeof(unsigned)));
-    return MV_OK;
+    return clear();
 }
 
 int S16Peak::read(int key, float* value) const {
@@ -109,10 +113,9 @@ int S16Peak::read(int key, float* value) const {
         *value = -1.0f;
         return MV_OK;
     }
-    unsigned bits = 0;
+    float v = 0.0f;
     MV_HIP_OK(hipDeviceSynchronize());
-    MV_HIP_OK(hipMemcpy(&bits, d_peak, sizeof(bits), hipMemcpyDeviceToHost));
-    const float v = __builtin_bit_cast(float, bits);
+    if (const int rc = raw(&v)) return rc;
     *value = key == MV_INFO_S16_PEAK ? v / CS_XSCALE : (v >= 65504.0f ? 1.0f : 0.0f);
     return MV_OK;
 }

@@ -174,7 +174,7 @@ class CAMPPlus(NativeBackbone, nn.Module):
 
     def _native_created(self, handle, build):
         """a fresh handle: say so ONCE per build when the checkpoint is sensitive to the fp16 operands of the x-vector part -- the part that has no
-        exact form to fall back to (csrc/campplus.hip::probe_xvector; DESIGN.md section 3)"""
+        exact form to fall back to (csrc/campp_probe.hip::probe_xvector; DESIGN.md section 3)"""
         rep = handle.campp_head()
         if rep.get('xvector_warning'):
             import warnings
