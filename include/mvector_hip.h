@@ -702,8 +702,28 @@ typedef struct MvConv2dsDesc {
     int32_t nbw_hint, ct_hint, rows_hint, ring_hint, wgs_hint, spw_hint, nprod_hint; /* 0 = the launcher's choice; otherwise blocks of 16 output channels per wave
                                            * (1..3), blocks per workgroup, rows per 3x3 tile (1..8), LDS ring stages (>= 2), workgroups per CU
                                            * (1 | 2), segments per consumer wave (8 | 4 | 2 | 1), producer waves: launch shapes for tests and tools/bench_conv2d.py (never the bits of a result) */
+    int32_t wg_hint;           /* since ABI 5.  0 = the launcher's choice (the chip's workgroup slots); otherwise the workgroups per channel tile are
+                                * min(wg_hint, B * pixel tiles): a small layer then walks several tiles per workgroup on a large chip (tests; the counterpart
+                                * of MvConv1dDesc.persist_blocks_hint; never the bits of a result).  Negative: refused */
 } MvConv2dsDesc;
 int mv_conv2ds_forward(const MvConv2dsDesc* d, mv_stream_t stream);
+/* What mv_conv2ds_forward would launch for `d`, without launching (additive since ABI 5).  cus = 0 plans for the current device; any other value for a
+ * chip of that many compute units.  The descriptor goes through the same checks and the same plan as a forward call, so a refused descriptor returns
+ * that call's error code and message.  kernel: the row of csrc/conv2ds.hip's kernel table, "conv2ds_kernel<KS, NBW, SPW, MAXT, TRACK>" as spelled
+ * there (a static string owned by the library); nbw / spw / track repeat its parameters (blocks of 16 output channels and 16-pixel segments per
+ * consumer wave; track = 1 with a peak word).  ncons / nprod: consumer and producer waves; ns: LDS ring stages; pp: transfers per producer wave and
+ * stage (padded); wgs_per_cu: workgroups per compute unit the ring was sized for; rows: output rows per 3x3 tile (1x1: 8 segments); ct: blocks per
+ * channel tile, ctiles of them; tiles: pixel tiles per utterance; wg_per_ct: workgroups per channel tile (each walks the pixel tiles
+ * widx, widx + wg_per_ct, ... of all B * tiles); grid = wg_per_ct * ctiles; stages_per_tile: K stages of one tile; lds_bytes: dynamic LDS. */
+typedef struct MvConv2dsPlanInfo {
+    const char* kernel;
+    int32_t nbw, spw, track;
+    int32_t ncons, nprod, ns, pp, wgs_per_cu;
+    int32_t rows, ct, ctiles, tiles, wg_per_ct, grid;
+    int32_t stages_per_tile;
+    int32_t lds_bytes;
+} MvConv2dsPlanInfo;
+int mv_conv2ds_plan_info(const MvConv2dsDesc* d, int32_t cus, MvConv2dsPlanInfo* out);
 /* the first conv and the pooling with S16 maps on the map side */
 int mv_conv2d_first_s16(const float* feats, void* out, const float* w, const float* bias, int32_t B, int32_t T, int32_t F,
                         int32_t C, mv_stream_t stream);

@@ -277,13 +277,14 @@ def s16_merge(cdll, buf):
     return out.cpu()
 
 
-def conv2ds_case(cdll, device, B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1, stride_w=0, concat=False, epi=0, with_res=False, with_sum=False,
-                 lo=0.0, hi=20.0, seed=0, nbw=0, ct=0, rows=0, ring=0, wgs=0, spw=0, nprod=0, x_scale=1.0, peak=False, nan_at=None):
-    """mv_conv2ds_forward (split-fp16 operands on S16 maps) against F.conv2d in fp64 on the SAME 22-bit inputs: the map round trip
-    (split -> merge) is what the layer sees, so the bar is the fp32 one of conv2d_case.
-    peak: MvConv2dsDesc.peak -- the reported word must hold the largest |64 * value| the layer wanted to store (before the clamp to the fp16
-    range; values beyond 1023.5 are then stored as +-1023.5: the reference values are clamped the same way).  nan_at: input element (b, h, w, c)
-    set to NaN -- the outputs that read it must be NaN (a clamp must not turn it into a bound), everything else as without it."""
+CONV2DS_BOUND_MAX_K, CONV2DS_BOUND_MAX_WORK = 1024, 1 << 28
+
+
+def conv2ds_operands(B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1, stride_w=0, concat=False, epi=0, with_res=False, with_sum=False,
+                     lo=0.0, hi=20.0, seed=0, x_scale=1.0, add_scale=1.0, only_b=None):
+    """the random operands of conv2ds_case, on the CPU and before any rounding (tests/conv2ds_cases.py evaluates its fp64 reference on them without a
+    kernel).  add_scale: gain of the second output's addend (peak cases: max |y2| above max |y|).  only_b: utterance b of the batch alone."""
+    import types
     g = torch.Generator().manual_seed(seed)
     rn = lambda *s: torch.randn(*s, generator=g)
     r16 = lambda n: -(-n // 16) * 16
@@ -301,10 +302,48 @@ def conv2ds_case(cdll, device, B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1,
     ldy = c16 + 16
     res = rn(B, Ho, Wo, c16) if (with_res or epi == 2) else None
     res2 = rn(B, Ho, Wo, c16) if epi == 2 else None
-    add = rn(B, Ho, Wo, c16) if with_sum else None
+    add = rn(B, Ho, Wo, c16) * add_scale if with_sum else None
     for t in (res, res2, add):   # operands are maps of the same model: their padded channels are zero (eres2net.hip pads weights with zero rows)
         if t is not None:
             t[..., cout:] = 0.0
+    if only_b is not None:
+        one = lambda t: None if t is None else t[only_b:only_b + 1].contiguous()
+        xa, xb, res, res2, add, B = one(xa), one(xb), one(res), one(res2), one(add), 1
+    if concat:   # the weight as the packer gets it: the two sources' channels each padded to 16
+        wfull = torch.zeros(cout, 2 * r16(cin_a), ks, ks)
+        wfull[:, :cin_a] = w[:, :cin_a]
+        wfull[:, r16(cin_a):r16(cin_a) + cin_a] = w[:, cin_a:]
+        cin_k = 2 * r16(cin_a)
+    else:
+        wfull, cin_k = w, cin
+    return types.SimpleNamespace(B=B, H=H, W=W, cin=cin, cout=cout, ks=ks, stride=stride, sw=sw, concat=concat, epi=epi, with_res=with_res,
+                                 with_sum=with_sum, lo=lo, hi=hi, cin_a=cin_a, lda=lda, xa=xa, xb=xb, w=w, wfull=wfull, cin_k=cin_k, bn_scale=bn_scale,
+                                 bias=bias, p=p, Ho=Ho, Wo=Wo, c16=c16, ldy=ldy, res=res, res2=res2, add=add)
+
+
+def s16_words(buf):
+    """(hi, lo) fp64 [..., channels] of an S16 buffer (a float32 tensor whose storage holds, per unit of 16 channels, 16 x hi | 16 x lo fp16 of
+    64 * value): the stored words themselves, nothing rounded on the way"""
+    h = buf.cpu().contiguous().view(torch.float16).reshape(*buf.shape[:-1], buf.shape[-1] // 16, 2, 16)
+    return h[..., 0, :].reshape(buf.shape).double(), h[..., 1, :].reshape(buf.shape).double()
+
+
+def conv2ds_case(cdll, device, B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1, stride_w=0, concat=False, epi=0, with_res=False, with_sum=False,
+                 lo=0.0, hi=20.0, seed=0, nbw=0, ct=0, rows=0, ring=0, wgs=0, spw=0, nprod=0, x_scale=1.0, peak=False, nan_at=None,
+                 wg=0, add_scale=1.0, only_b=None, expect=None, plan_cus=None, log=None, tag='', return_words=False):
+    """mv_conv2ds_forward (split-fp16 operands on S16 maps) against F.conv2d in fp64 on the SAME 22-bit inputs: the map round trip
+    (split -> merge) is what the layer sees, so the bar is the fp32 one of conv2d_case.
+    peak: MvConv2dsDesc.peak -- the reported word must hold the largest |64 * value| the layer wanted to store in either output (before the clamp to
+    the fp16 range; values beyond 1023.5 are then stored as +-1023.5: the reference values are clamped the same way).  nan_at: input element (b, h, w, c)
+    set to NaN -- the outputs that read it must be NaN (a clamp must not turn it into a bound), everything else as without it.
+    wg: MvConv2dsDesc.wg_hint.  expect: fields of mv_conv2ds_plan_info the descriptor must plan to on this device, asserted before the launch.
+    plan_cus: launch nothing; return {cus: plan info} of the case's descriptor for these compute-unit counts.  log: receives the per-element
+    bound's line (tests/conv2ds_cases.py).  return_words: (y, y2 | None, peak bits | None), the raw S16 words of the outputs' channel slices."""
+    o = conv2ds_operands(B=B, H=H, W=W, cin=cin, cout=cout, ks=ks, stride=stride, stride_w=stride_w, concat=concat, epi=epi, with_res=with_res,
+                         with_sum=with_sum, lo=lo, hi=hi, seed=seed, x_scale=x_scale, add_scale=add_scale, only_b=only_b)
+    r16 = lambda n: -(-n // 16) * 16
+    B, cin_a, lda, xa, xb, w, bn_scale, bias = o.B, o.cin_a, o.lda, o.xa, o.xb, o.w, o.bn_scale, o.bias
+    p, sw, Ho, Wo, c16, ldy, res, res2, add = o.p, o.sw, o.Ho, o.Wo, o.c16, o.ldy, o.res, o.res2, o.add
     dev = lambda t: None if t is None else t.to(device).contiguous()
     sp = lambda t: None if t is None else s16_split(cdll, t, device)
     xad, xbd, resd, res2d, addd = sp(xa), sp(xb), sp(res), sp(res2), sp(add)
@@ -312,15 +351,7 @@ def conv2ds_case(cdll, device, B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1,
     mg = lambda t: None if t is None else s16_merge(cdll, t).double()
     xa_q, xb_q, res_q, res2_q, add_q = mg(xad), mg(xbd), mg(resd), mg(res2d), mg(addd)
     assert (xa_q - xa.double()).abs().max().item() <= 3e-7 * max(1.0, xa.abs().max().item()), 'S16 round trip is not 22-bit'
-    wd, sd = dev(w), dev(bn_scale)
-    if concat:
-        wfull = torch.zeros(cout, 2 * r16(cin_a), ks, ks)
-        wfull[:, :cin_a] = w[:, :cin_a]
-        wfull[:, r16(cin_a):r16(cin_a) + cin_a] = w[:, cin_a:]
-        wd = dev(wfull)
-        cin_k = 2 * r16(cin_a)
-    else:
-        cin_k = cin
+    wd, sd, cin_k = dev(o.wfull), dev(bn_scale), o.cin_k
     n = cdll.mv_conv2ds_packed_elems(cout, cin_k, ks)
     packed = torch.zeros(n, dtype=torch.float32, device=device)
     osc = ctypes.c_float(0.0)
@@ -348,7 +379,12 @@ def conv2ds_case(cdll, device, B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1,
     d.lo, d.hi = lo, hi
     d.stride_w = stride_w
     d.peak = peak_word.data_ptr() if peak else None
-    d.nbw_hint, d.ct_hint, d.rows_hint, d.ring_hint, d.wgs_hint, d.spw_hint, d.nprod_hint = nbw, ct, rows, ring, wgs, spw, nprod
+    d.nbw_hint, d.ct_hint, d.rows_hint, d.ring_hint, d.wgs_hint, d.spw_hint, d.nprod_hint, d.wg_hint = nbw, ct, rows, ring, wgs, spw, nprod, wg
+    if plan_cus is not None:
+        return {cus: _hip.conv2ds_plan_info(d, cus, cdll) for cus in plan_cus}
+    plan = _hip.conv2ds_plan_info(d, 0, cdll)
+    for name, want in (expect or {}).items():
+        assert plan[name] == want, f'{tag}: the plan has {name} = {plan[name]!r}, the case is pinned to {want!r} ({plan})'
     _hip.check(cdll.mv_conv2ds_forward(ctypes.byref(d), _stream(xad)), cdll)
     if device != 'cpu':
         torch.cuda.synchronize()
@@ -371,6 +407,8 @@ def conv2ds_case(cdll, device, B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1,
     if peak:
         import struct
         want = ref.abs().max().item() * 64.0            # (before the range clamp; after lo / hi)
+        if with_sum:   # the second output is a stored map too: y (as stored, within the range) + add
+            want = max(want, (ref.clamp(-65504.0 / 64.0, 65504.0 / 64.0) + add_q[..., :cout]).abs().max().item() * 64.0)
         seen = struct.unpack('f', struct.pack('i', int(peak_word.cpu().item())))[0]
         assert abs(seen - want) <= 2e-5 * want, (seen, want)
         ref = ref.clamp(-65504.0 / 64.0, 65504.0 / 64.0)  # the split saturates at +-1023.5
@@ -395,6 +433,16 @@ def conv2ds_case(cdll, device, B=2, H=10, W=37, cin=16, cout=16, ks=3, stride=1,
         err2 = (got2[..., :cout] - (got[..., :cout] + add_q[..., :cout])).abs().max().item()
         assert err2 < 1e-6 * scale, f'conv2ds second output mismatch {err2}'
         assert torch.all(got2[..., c16:] == 7.0)
+    # every output element within its derived bound of the fp64 reference on the operands as the kernel holds them: the pinned cases, and every
+    # other case up to CONV2DS_BOUND_MAX_K products per output and CONV2DS_BOUND_MAX_WORK products in all (above, the bound is as loose as the
+    # tolerance above, and its three fp64 convolutions on the CPU take longer than the layer's test should)
+    small = cin * ks * ks <= CONV2DS_BOUND_MAX_K and B * Ho * Wo * cout * cin * ks * ks <= CONV2DS_BOUND_MAX_WORK
+    if nan_at is None and (expect is not None or small):
+        import conv2ds_cases
+        conv2ds_cases.assert_within_bound(o, y, y2, kernel=plan['kernel'], tag=tag, log=log, device_x=(xad, xbd, resd, res2d, addd), device_w=(packed, osc.value))
+    if return_words:
+        words = lambda t: None if t is None else t.cpu().contiguous().view(torch.int32)[..., :c16].clone()
+        return words(y), words(y2), (int(peak_word.cpu().item()) if peak else None)
     return err
 
 
@@ -408,21 +456,21 @@ CONV2DS_CASES = [
     dict(cin=96, cout=16, ks=1, concat=True, epi=1),                         # concat of two 48-channel operands: a K chunk straddles the sources
     dict(cin=16, cout=64, ks=1, epi=2),                                      # AFF local_att[3:5] + fusion
     dict(cin=104, cout=104, ks=3, H=5, W=40, B=1),                           # width 104: an odd number of 16-channel units, 7 blocks
-    dict(cin=256, cout=512, ks=3, stride=2, H=6, W=20, B=1, hi=65504.0, lo=-65504.0),  # layer3_downsample: two channel tiles
-    dict(cin=48, cout=144, ks=3, H=3, W=20, B=1),                            # 9 blocks on waves of 2: the last wave has one
-    dict(cin=48, cout=208, ks=1, H=2, W=37, B=2, with_res=True),             # 1x1: 13 blocks, an odd number of K chunks
+    dict(cin=256, cout=512, ks=3, stride=2, H=6, W=20, B=1, hi=65504.0, lo=-65504.0),  # layer3_downsample: 32 blocks as three channel tiles of 11 (11, 11, 10), three blocks per wave
+    dict(cin=48, cout=144, ks=3, H=3, W=20, B=1),                            # 9 blocks: one channel tile on three consumer waves of three blocks
+    dict(cin=48, cout=208, ks=1, H=2, W=37, B=2, with_res=True),             # 1x1: 13 blocks as two channel tiles (7 + 6); three input units: the second K chunk is half empty
     dict(cin=32, cout=48, ks=1, stride=2, H=5, W=37, B=2),                   # strided 1x1 on odd sizes: 5 x 37 -> 3 x 19
     dict(cin=16, cout=32, ks=3, stride=2, H=5, W=33, B=1),                   # strided 3x3 on odd sizes
-    dict(cin=48, cout=48, ks=3, H=21, W=50, B=1, with_sum=True),             # 21 rows: tiles of 7 rows
+    dict(cin=48, cout=48, ks=3, H=21, W=50, B=1, with_sum=True),             # 21 rows: tiles of 8 rows on the emulator's 8 compute units, of 3 rows on 256 (cs_rows follows the chip)
     dict(cin=80, cout=80, ks=3, H=10, W=20, B=1, nbw=2),                     # forced two blocks per wave on 5 blocks
     dict(cin=64, cout=256, ks=1, H=4, W=40, B=1, nbw=2, ct=6),               # two blocks per wave, three channel tiles (the last with 4 blocks)
     dict(cin=64, cout=192, ks=3, H=9, W=17, B=1, nbw=2, rows=3),             # two blocks per wave on 12 blocks, tiles of 3 rows
-    dict(cin=64, cout=64, ks=3, H=24, W=40, B=2, ring=2, wgs=1),             # shortest ring, many tiles per workgroup
+    dict(cin=64, cout=64, ks=3, H=24, W=40, B=2, ring=2, wgs=1),             # shortest ring; 9 tiles per workgroup on the emulator's chip, one on 256 compute units (tests/conv2ds_cases.py walks on both)
     dict(cin=96, cout=48, ks=1, H=30, W=40, B=2, ring=2, wgs=1),             # 1x1, a ring of two
     dict(cin=160, cout=48, ks=1, H=30, W=40, B=2, ring=3, wgs=1),            # 1x1, ring of three
     dict(cin=64, cout=160, ks=3, H=10, W=20, B=1),                           # 10 blocks on four waves of <= 3 (3, 3, 2, 2), four producer waves
     dict(cin=96, cout=192, ks=1, H=6, W=50, B=1, with_res=True),             # residual + short K: two blocks on six consumer waves, two producers
-    dict(cin=320, cout=192, ks=1, H=6, W=50, B=1, with_res=True),            # the same layer with four K stages ... and one more (12 blocks on 4 x 3)
+    dict(cin=320, cout=192, ks=1, H=6, W=50, B=1, with_res=True),            # the same layer with four K stages per tile: still two blocks on six consumer waves (the limit of that form)
     dict(cin=48, cout=48, ks=3, H=13, W=40, B=1, nbw=3, spw=4, with_sum=True),   # all three blocks in one wave, two pixel groups
     dict(cin=80, cout=80, ks=3, H=10, W=20, B=1, nbw=3, spw=4),              # five blocks as 3 + 2 on two pixel groups: four consumer waves
     dict(cin=32, cout=32, ks=3, H=11, W=30, B=2, nbw=2, spw=2),              # two blocks per wave, four pixel groups of two segments

@@ -553,7 +553,10 @@ __global__ __launch_bounds__(MAXT) void conv2ds_kernel(Conv2dsArgs a) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const float th = tanhf(X[r] * CS_XSCALE_INV);  // x_att = 1 + th;  out = x * x_att + y * (2 - x_att)
-                            X[r] = o1[r] * (1.0f + th) + o2[r] * (1.0f - th);
+                            // One product rounded, the other fused, and WHICH is written out: left as a * b + c * d the compiler contracts either
+                            // product into the sum, and it chose differently in the instantiations with and without the peak word (the same
+                            // launch form gave other S16 words on the device: tests/conv2ds_cases.py SAME_BITS 'aff').
+                            X[r] = __builtin_fmaf(o1[r], 1.0f + th, o2[r] * (1.0f - th));
                         }
                         if (track && ok[u]) pk = s16_peak_of(pk, X);
 #pragma unroll
@@ -581,6 +584,7 @@ namespace {
 
 struct CsPlan {
     int nbw, spw, CT, ctiles, ncons, nprod, R, ncs, tiles, pc, pcv, ns, pp, wg_per_ct, wgs_per_cu;
+    int nst;      // K stages per tile: what the kernel computes as `nst`
     size_t lds;
 };
 
@@ -607,7 +611,8 @@ int cs_rows(int Ho, int stride, int64_t strips, int ctiles, int slots, int steps
     return best;
 }
 
-int cs_plan(const MvConv2dsDesc& d, int Ho, int Wo, int sw, CsPlan* p) {
+// A pure function of the descriptor and the chip's compute-unit count `cus` (conv2ds_launch: the device's; conv2ds_plan_info: the caller's).
+int cs_plan(const MvConv2dsDesc& d, int Ho, int Wo, int sw, int cus, CsPlan* p) {
     const int nblk = d.cout16 / 16;
     // Wave roles.  Up to 7 blocks: one block per consumer wave (<= 168 registers, 12 waves per CU).  From 8 blocks on: FOUR consumer waves -- one per
     // SIMD, so no two of them share a matrix pipe (five or six waves leave one SIMD with twice the work: the barrier of a stage waits for it, r12w
@@ -667,7 +672,7 @@ int cs_plan(const MvConv2dsDesc& d, int Ho, int Wo, int sw, CsPlan* p) {
     if (d.ks == 3) {
         const int64_t strips = (int64_t)d.B * ceil_div(Wo, 16);
         const int steps_per_tile = (int)ceil_div(d.cin16, 32) * 9;
-        p->R = d.rows_hint > 0 ? d.rows_hint : cs_rows(Ho, d.stride, strips, p->ctiles, device_cu_count() * (p->ncons + nprod_want <= max_waves / 2 ? 2 : 1), steps_per_tile, nbw, p->spw);
+        p->R = d.rows_hint > 0 ? d.rows_hint : cs_rows(Ho, d.stride, strips, p->ctiles, cus * (p->ncons + nprod_want <= max_waves / 2 ? 2 : 1), steps_per_tile, nbw, p->spw);
         MV_REQUIRE(p->R >= 1 && p->R <= CS_SEGS, "conv2ds: rows per tile must be 1..8");
         p->ncs = (int)ceil_div(Wo, 16);
         p->tiles = (int)ceil_div(Ho, p->R) * p->ncs;
@@ -709,9 +714,12 @@ int cs_plan(const MvConv2dsDesc& d, int Ho, int Wo, int sw, CsPlan* p) {
     const int wgs = p->wgs_per_cu;
     const int64_t ptiles = (int64_t)d.B * p->tiles;
     MV_REQUIRE(ptiles < ((int64_t)1 << 30), "conv2ds: too many pixel tiles");
-    int64_t per_ct = (int64_t)device_cu_count() * wgs / p->ctiles;
+    // MvConv2dsDesc.wg_hint overrides the workgroups per channel tile (tests walk several tiles per workgroup on small layers; never the bits of a result)
+    MV_REQUIRE(d.wg_hint >= 0, "conv2ds: wg_hint must be 0 (the launcher's choice) or a count of workgroups per channel tile");
+    int64_t per_ct = d.wg_hint > 0 ? d.wg_hint : (int64_t)cus * wgs / p->ctiles;
     if (per_ct < 1) per_ct = 1;
     p->wg_per_ct = (int)(per_ct < ptiles ? per_ct : ptiles);
+    p->nst = stages_per_tile;
     return MV_OK;
 }
 
@@ -727,14 +735,38 @@ int cs_launch_t(const Conv2dsArgs& a, const CsPlan& p, hipStream_t stream) {
     return MV_OK;
 }
 
-template <int KS, int NBW, int SPW, int MAXT>
-int cs_launch(const Conv2dsArgs& a, const CsPlan& p, hipStream_t stream) {
-    return a.peak != nullptr ? cs_launch_t<KS, NBW, SPW, MAXT, true>(a, p, stream) : cs_launch_t<KS, NBW, SPW, MAXT, false>(a, p, stream);
+// The kernels conv2ds_launch runs, one table row each: the only place that names the instantiations.  Every launch goes through the table, and
+// mv_conv2ds_plan_info reports the row's name.  (KS, NBW, SPW, MAXT, TRACK); MAXT = 768 threads with one block per wave, 512 with two or three.
+struct CsKernelRow {
+    int ks, nbw, spw;
+    bool track;
+    int (*launch)(const Conv2dsArgs&, const CsPlan&, hipStream_t);
+    const char* name;
+};
+#define MV_CS_ROW(KS, NBW, SPW, MAXT, TRACK) {KS, NBW, SPW, TRACK, cs_launch_t<KS, NBW, SPW, MAXT, TRACK>, "conv2ds_kernel<" #KS ", " #NBW ", " #SPW ", " #MAXT ", " #TRACK ">"}
+const CsKernelRow CS_KERNELS[] = {
+    MV_CS_ROW(1, 1, 8, 768, false), MV_CS_ROW(1, 1, 8, 768, true), MV_CS_ROW(3, 1, 8, 768, false), MV_CS_ROW(3, 1, 8, 768, true),
+    MV_CS_ROW(1, 1, 4, 768, false), MV_CS_ROW(1, 1, 4, 768, true), MV_CS_ROW(3, 1, 4, 768, false), MV_CS_ROW(3, 1, 4, 768, true),
+    MV_CS_ROW(1, 1, 2, 768, false), MV_CS_ROW(1, 1, 2, 768, true), MV_CS_ROW(3, 1, 2, 768, false), MV_CS_ROW(3, 1, 2, 768, true),
+    MV_CS_ROW(1, 1, 1, 768, false), MV_CS_ROW(1, 1, 1, 768, true), MV_CS_ROW(3, 1, 1, 768, false), MV_CS_ROW(3, 1, 1, 768, true),
+    MV_CS_ROW(1, 2, 8, 512, false), MV_CS_ROW(1, 2, 8, 512, true), MV_CS_ROW(3, 2, 8, 512, false), MV_CS_ROW(3, 2, 8, 512, true),
+    MV_CS_ROW(1, 2, 4, 512, false), MV_CS_ROW(1, 2, 4, 512, true), MV_CS_ROW(3, 2, 4, 512, false), MV_CS_ROW(3, 2, 4, 512, true),
+    MV_CS_ROW(1, 2, 2, 512, false), MV_CS_ROW(1, 2, 2, 512, true), MV_CS_ROW(3, 2, 2, 512, false), MV_CS_ROW(3, 2, 2, 512, true),
+    MV_CS_ROW(1, 3, 8, 512, false), MV_CS_ROW(1, 3, 8, 512, true), MV_CS_ROW(3, 3, 8, 512, false), MV_CS_ROW(3, 3, 8, 512, true),
+    MV_CS_ROW(1, 3, 4, 512, false), MV_CS_ROW(1, 3, 4, 512, true), MV_CS_ROW(3, 3, 4, 512, false), MV_CS_ROW(3, 3, 4, 512, true),
+    MV_CS_ROW(1, 3, 2, 512, false), MV_CS_ROW(1, 3, 2, 512, true), MV_CS_ROW(3, 3, 2, 512, false), MV_CS_ROW(3, 3, 2, 512, true),
+};
+#undef MV_CS_ROW
+
+// the row of a plan: cs_plan makes spw one of 8 / 4 / 2 (one block per wave: also 1), so every plan it accepts has one
+const CsKernelRow* cs_row(int ks, const CsPlan& p, bool track) {
+    for (const CsKernelRow& row : CS_KERNELS)
+        if (row.ks == ks && row.nbw == p.nbw && row.spw == p.spw && row.track == track) return &row;
+    return nullptr;
 }
 
-}  // namespace
-
-int conv2ds_launch(const MvConv2dsDesc& d, hipStream_t stream) {
+// every argument check of a forward call, and the output size
+int cs_check(const MvConv2dsDesc& d, int* Ho_out, int* Wo_out, int* sw_out) {
     MV_REQUIRE(d.x != nullptr && d.w != nullptr && d.bias != nullptr && d.y != nullptr, "conv2ds: null pointer");
     MV_REQUIRE(d.B > 0 && d.H > 0 && d.W > 0, "conv2ds: empty input");
     MV_REQUIRE((d.ks == 1 || d.ks == 3) && (d.stride == 1 || d.stride == 2), "conv2ds: kernel 1 or 3, stride 1 or 2");
@@ -756,8 +788,30 @@ int conv2ds_launch(const MvConv2dsDesc& d, hipStream_t stream) {
                "conv2ds: one utterance's map too large (4 GiB)");
     const int p = d.ks / 2;
     const int Ho = (d.H + 2 * p - d.ks) / d.stride + 1, Wo = (d.W + 2 * p - d.ks) / sw + 1;
+    *Ho_out = Ho;
+    *Wo_out = Wo;
+    *sw_out = sw;
+    return MV_OK;
+}
+
+// checks and plan of a descriptor for a chip of `cus` compute units (0: this device's): what conv2ds_launch and conv2ds_plan_info share
+int cs_check_and_plan(const MvConv2dsDesc& d, int cus, int* Ho, int* Wo, int* sw, CsPlan* plan, const CsKernelRow** row) {
+    int rc = cs_check(d, Ho, Wo, sw);
+    if (rc != MV_OK) return rc;
+    if (cus == 0) cus = device_cu_count();   // (cached per device)
+    if ((rc = cs_plan(d, *Ho, *Wo, *sw, cus, plan)) != MV_OK) return rc;
+    *row = cs_row(d.ks, *plan, d.peak != nullptr);
+    MV_REQUIRE(*row != nullptr, "conv2ds: the plan has no row in the kernel table");
+    return MV_OK;
+}
+
+}  // namespace
+
+int conv2ds_launch(const MvConv2dsDesc& d, hipStream_t stream) {
+    int Ho, Wo, sw;
     CsPlan plan;
-    int rc = cs_plan(d, Ho, Wo, sw, &plan);
+    const CsKernelRow* row;
+    int rc = cs_check_and_plan(d, 0, &Ho, &Wo, &sw, &plan, &row);
     if (rc != MV_OK) return rc;
     Conv2dsArgs a;
     a.x = static_cast<const half_t*>(d.x); a.x2 = static_cast<const half_t*>(d.x2); a.w = static_cast<const half_t*>(d.w); a.bias = d.bias;
@@ -777,29 +831,27 @@ int conv2ds_launch(const MvConv2dsDesc& d, hipStream_t stream) {
     a.ns = plan.ns; a.pp = plan.pp; a.wg_per_ct = plan.wg_per_ct;
     const int prof = prof_begin(MV_PROF_CONV2D, 2.0 * d.B * Ho * Wo * (double)(d.cin_alg > 0 ? d.cin_alg : d.cin16) *
                                                 (d.cout_alg > 0 ? d.cout_alg : d.cout16) * d.ks * d.ks, stream);
-#define MV_CS_DISPATCH(KS)                                                                       \
-    do {                                                                                         \
-        if (plan.nbw == 3) {                                                                     \
-            if (plan.spw == 8) rc = cs_launch<KS, 3, 8, 512>(a, plan, stream);                   \
-            else if (plan.spw == 4) rc = cs_launch<KS, 3, 4, 512>(a, plan, stream);              \
-            else rc = cs_launch<KS, 3, 2, 512>(a, plan, stream);                                 \
-        } else if (plan.nbw == 2) {                                                              \
-            if (plan.spw == 8) rc = cs_launch<KS, 2, 8, 512>(a, plan, stream);                   \
-            else if (plan.spw == 4) rc = cs_launch<KS, 2, 4, 512>(a, plan, stream);              \
-            else rc = cs_launch<KS, 2, 2, 512>(a, plan, stream);                                 \
-        } else {                                                                                 \
-            if (plan.spw == 8) rc = cs_launch<KS, 1, 8, 768>(a, plan, stream);                   \
-            else if (plan.spw == 4) rc = cs_launch<KS, 1, 4, 768>(a, plan, stream);              \
-            else if (plan.spw == 2) rc = cs_launch<KS, 1, 2, 768>(a, plan, stream);              \
-            else rc = cs_launch<KS, 1, 1, 768>(a, plan, stream);                                 \
-        }                                                                                        \
-    } while (0)
-    if (d.ks == 3) MV_CS_DISPATCH(3);
-    else MV_CS_DISPATCH(1);
-#undef MV_CS_DISPATCH
+    rc = row->launch(a, plan, stream);
     prof_end(prof, stream);
     if (rc != MV_OK) return rc;
     return check_launch("conv2ds_kernel");
+}
+
+// The plan of a descriptor as conv2ds_launch would make it, for a chip of `cus` compute units (0: this device's), and nothing launched: the same
+// cs_check and cs_plan, so the same refusals.  (mv_conv2ds_plan_info: tests name the table row a case has to run.)
+int conv2ds_plan_info(const MvConv2dsDesc& d, int cus, MvConv2dsPlanInfo* out) {
+    int Ho, Wo, sw;
+    CsPlan p;
+    const CsKernelRow* row;
+    int rc = cs_check_and_plan(d, cus, &Ho, &Wo, &sw, &p, &row);
+    if (rc != MV_OK) return rc;
+    out->kernel = row->name;
+    out->nbw = p.nbw; out->spw = p.spw; out->track = row->track ? 1 : 0;
+    out->ncons = p.ncons; out->nprod = p.nprod; out->ns = p.ns; out->pp = p.pp; out->wgs_per_cu = p.wgs_per_cu;
+    out->rows = p.R; out->ct = p.CT; out->ctiles = p.ctiles; out->tiles = p.tiles; out->wg_per_ct = p.wg_per_ct; out->grid = p.wg_per_ct * p.ctiles;
+    out->stages_per_tile = p.nst;
+    out->lds_bytes = (int32_t)p.lds;
+    return MV_OK;
 }
 
 // ---- weights: fp32 [cout16][taps][cin16] (BatchNorm folded) -> split fp16 [cout16][taps][wunits][hi 16 | lo 16], scaled by 2^s -------------
@@ -893,6 +945,12 @@ int mv_conv2ds_pack_weight(const float* w, const float* out_scale, int32_t cout,
 int mv_conv2ds_forward(const MvConv2dsDesc* d, mv_stream_t stream) {
     MV_REQUIRE(d != nullptr, "mv_conv2ds_forward: null descriptor");
     return mv::conv2ds_launch(*d, static_cast<hipStream_t>(stream));
+}
+
+int mv_conv2ds_plan_info(const MvConv2dsDesc* d, int32_t cus, MvConv2dsPlanInfo* out) {
+    MV_REQUIRE(d != nullptr && out != nullptr, "mv_conv2ds_plan_info: null argument");
+    MV_REQUIRE(cus >= 0, "mv_conv2ds_plan_info: cus must be 0 (this device) or a count of compute units");
+    return mv::conv2ds_plan_info(*d, cus, out);
 }
 
 int mv_map_split_f32(const float* x, void* y, int64_t n, mv_stream_t stream) { return mv::map_split_launch(x, y, n, static_cast<hipStream_t>(stream)); }

@@ -31,6 +31,8 @@ int tstp_launch(const float* x, int64_t ld, int B, int H, int W, int C, float* s
 
 // split-fp16 form of the same layers on S16 maps (conv2ds.hip)
 int conv2ds_launch(const MvConv2dsDesc& d, hipStream_t stream);
+// what conv2ds_launch would launch for `d` on a chip of `cus` compute units (0: this device's): same checks, same plan, no launch
+int conv2ds_plan_info(const MvConv2dsDesc& d, int cus, MvConv2dsPlanInfo* out);
 int64_t conv2ds_packed_floats(int cout16, int cin16, int ks);
 float conv2ds_pack_host(const float* w_dense, int cout16, int cin16, int ks, half_t* out);  // [cout16][taps][cin16] fp32 -> split; returns oscale
 int map_split_launch(const float* x, void* y, int64_t n, hipStream_t stream);

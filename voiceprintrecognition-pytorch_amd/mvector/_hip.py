@@ -115,7 +115,15 @@ class MvConv2dsDesc(ctypes.Structure):
                 ('ldadd', c_i64), ('y', c_vp), ('ldy', c_i64), ('y2', c_vp), ('ldy2', c_i64), ('B', c_i32), ('H', c_i32),
                 ('W', c_i32), ('cin16', c_i32), ('cout16', c_i32), ('ks', c_i32), ('stride', c_i32), ('epi', c_i32),
                 ('lo', c_f32), ('hi', c_f32), ('cin_alg', c_i32), ('cout_alg', c_i32), ('stride_w', c_i32), ('peak', c_vp), ('nbw_hint', c_i32),
-                ('ct_hint', c_i32), ('rows_hint', c_i32), ('ring_hint', c_i32), ('wgs_hint', c_i32), ('spw_hint', c_i32), ('nprod_hint', c_i32)]
+                ('ct_hint', c_i32), ('rows_hint', c_i32), ('ring_hint', c_i32), ('wgs_hint', c_i32), ('spw_hint', c_i32), ('nprod_hint', c_i32),
+                ('wg_hint', c_i32)]
+
+
+class MvConv2dsPlanInfo(ctypes.Structure):
+    """what a conv2ds forward would launch (mv_conv2ds_plan_info): the row of csrc/conv2ds.hip's kernel table by name, and the launch shape"""
+    _fields_ = [('kernel', ctypes.c_char_p), ('nbw', c_i32), ('spw', c_i32), ('track', c_i32), ('ncons', c_i32), ('nprod', c_i32), ('ns', c_i32),
+                ('pp', c_i32), ('wgs_per_cu', c_i32), ('rows', c_i32), ('ct', c_i32), ('ctiles', c_i32), ('tiles', c_i32), ('wg_per_ct', c_i32),
+                ('grid', c_i32), ('stages_per_tile', c_i32), ('lds_bytes', c_i32)]
 
 
 class MvTdnnCfg(ctypes.Structure):
@@ -215,6 +223,7 @@ _SIGNATURES = {
     'mv_conv2ds_packed_elems': (c_i64, [c_i32, c_i32, c_i32]),
     'mv_conv2ds_pack_weight': (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, ctypes.POINTER(c_f32), c_vp]),
     'mv_conv2ds_forward': (c_i32, [ctypes.POINTER(MvConv2dsDesc), c_vp]),
+    'mv_conv2ds_plan_info': (c_i32, [ctypes.POINTER(MvConv2dsDesc), c_i32, ctypes.POINTER(MvConv2dsPlanInfo)]),
     'mv_map_split_f32': (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     'mv_map_merge_f32': (c_i32, [c_vp, c_vp, c_i64, c_vp]),
     'mv_conv2d_first_s16': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
@@ -393,6 +402,18 @@ def conv1d_plan_info(desc, groups=1, cus=0, cdll=None):
     check(cdll.mv_conv1d_plan_info(ctypes.byref(desc), groups, cus, ctypes.byref(info)), cdll)
     out = {name: getattr(info, name).decode() for name in ('kernel', 'in_stats_kernel', 'tail_kernel')}
     out.update((name, getattr(info, name)) for name in ('n_tiles', 'co_tiles', 'grid', 'tail_nv', 'tail_split'))
+    return out
+
+
+def conv2ds_plan_info(desc, cus=0, cdll=None):
+    """What mv_conv2ds_forward would launch for the MvConv2dsDesc ``desc`` on a chip of ``cus`` compute units (0: the current device's), nothing
+    launched (mv_conv2ds_plan_info): {'kernel'} -- the row of csrc/conv2ds.hip's kernel table by name -- and the launch shape, every integer field
+    of MvConv2dsPlanInfo.  A descriptor the forward refuses raises the forward's error."""
+    cdll = cdll or lib()
+    info = MvConv2dsPlanInfo()
+    check(cdll.mv_conv2ds_plan_info(ctypes.byref(desc), cus, ctypes.byref(info)), cdll)
+    out = {'kernel': info.kernel.decode()}
+    out.update((name, getattr(info, name)) for name, _ in MvConv2dsPlanInfo._fields_[1:])
     return out
 
 
