@@ -336,6 +336,37 @@ int mv_hfenc_forward_varlen(const MvHfEncoder* h, const float* wav, int32_t B, i
 int mv_hfenc_forward_timed(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio,
                            float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream, float* stage_ms_host, int32_t num_stages);
 
+/* The kernels of the forward one at a time (additive since ABI 5; layer-level checks -- the forward reaches its kernels through the same launch
+ * code).  All pointers are device pointers; a refused call names what is wrong and launches nothing.  Widths C: multiples of 64 up to 1024.
+ *
+ * mv_hfenc_wave_stats: stats [B][2] = (mean, sqrt(biased var + 1e-7)) of every row over its own n_b = clamp(num_samples[b], 0, L) samples
+ *   (num_samples NULL: L); n_b = 0 gives (0, 1). */
+int mv_hfenc_wave_stats(const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples, float* stats, mv_stream_t stream);
+/* mv_hfenc_layer0: the 1 -> C conv of k <= 16 taps at stride s <= 8 over (wav - mean) / sd (wstats [B][2] as mv_hfenc_wave_stats leaves them, or
+ *   NULL: the samples as they are), w [C][k] fp32, bias [C] or NULL; y [B, T0, C] fp16, T0 = floor((L - k) / s) + 1 >= 1.
+ *   gamma and beta given ("group" mode): GroupNorm(C, C) over the row's own T0_b frames (eps 1e-5) + exact GELU; cstats [B][C][2] receives
+ *   (mean, rstd), (0, 1) where T0_b = 0; workspace: mv_hfenc_layer0_workspace_bytes, 8-byte aligned (the fp64 sums of the 128-frame chunks).
+ *   gamma and beta NULL ("layer" mode before its row pass): conv + bias stored as fp16; cstats and workspace are not touched.
+ *   Frames t >= T0_b of a row are zeros; samples at or behind n_b are never read. */
+int mv_hfenc_layer0_workspace_bytes(int32_t B, int64_t L, int32_t C, int32_t k, int32_t s, size_t* bytes);
+int mv_hfenc_layer0(const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples, const float* wstats, const float* w,
+                    const float* bias, const float* gamma, const float* beta, int32_t C, int32_t k, int32_t s, void* y, float* cstats,
+                    void* workspace, size_t workspace_bytes, mv_stream_t stream);
+/* mv_hfenc_rows: one pass over n_rows frames of C fp16 channels.  MV_HF_ROWS_GELU: y = gelu(x), fp16 (gamma, beta, eps unused);
+ *   MV_HF_ROWS_LN_GELU: y = gelu(LayerNorm(x) * gamma + beta), fp16; MV_HF_ROWS_LN_F32: y = LayerNorm(x) * gamma + beta, fp32 (y != x).
+ *   The fp16 modes may run in place (y == x).  C = 512: x and y 16-byte aligned. */
+#define MV_HF_ROWS_GELU 0
+#define MV_HF_ROWS_LN_GELU 1
+#define MV_HF_ROWS_LN_F32 2
+int mv_hfenc_rows(const void* x, void* y, const float* gamma, const float* beta, float eps, int64_t n_rows, int32_t C, int32_t mode,
+                  mv_stream_t stream);
+/* mv_hfenc_cmn_mask: out [B, T, C] fp32 in place: minus the mean over the row's frames (cmn != 0), then zeros behind the mask length.
+ *   lens_ratio [B] or NULL: all T frames count, zeros from round_half_even(ratio * T) on.  num_samples [B] or NULL (not both): the row's frames
+ *   are Tb = its clamp(num_samples[b], 0, L) samples carried through num_layers valid convs (conv_kernel, conv_stride: HOST arrays; T must be
+ *   the count of L samples); the mean runs over Tb frames, zeros from Tb on whatever lies there. */
+int mv_hfenc_cmn_mask(float* out, int32_t B, int32_t T, int32_t C, const float* lens_ratio, const int64_t* num_samples, int64_t L,
+                      const int32_t* conv_kernel, const int32_t* conv_stride, int32_t num_layers, int32_t cmn, mv_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Backbones.  A model handle is built from the reference-layout fp32 ``state_dict`` (same key names
  * and shapes as the reference modules, so ``model.pth`` loads unchanged: mvector/utils/checkpoint.py:

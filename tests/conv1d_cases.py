@@ -64,8 +64,9 @@ def reference(o, drop_term=False):
     x = lc.conv1d_rounded_input(o).double()
     w = o.w.half().double()
     conv = lambda x_, w_, b_: F.conv1d(x_, w_, b_, stride=o.stride, dilation=o.dil).transpose(1, 2)
-    pre = conv(x, w, o.bias.double())
-    S = conv(x.abs(), w.abs(), o.bias.double().abs())
+    bias = None if o.bias is None else o.bias.double()     # (no bias: its term leaves the sum and S)
+    pre = conv(x, w, bias)
+    S = conv(x.abs(), w.abs(), None if bias is None else bias.abs())
     if drop_term:
         w1 = torch.zeros_like(w)
         w1[:, -1, 0] = w[:, -1, 0]
@@ -112,6 +113,7 @@ def _pin(cfg, kernel, in_stats_kernel='', tail_kernel='', **plan):
 _C = lc.CONV_CASES
 _TAPS = dict(B=2, T=75, cin=72, cout=200, k=3, dil=2)      # 150 rows x 200 channels: 2 x 2 tiles of 128, both ragged; an utterance boundary in row tile 0
 _EPI = dict(B=2, T=75, cin=136, cout=136, k=1, dil=1, tile=128)
+_HF = dict(B=3, dil=1, stride=2, valid=True, pad_mode='zero', pre_act=0, affine=False)
 PINNED = {
     # one-shot 128 x 128: second row tile ragged, reflect taps across the utterance boundary inside tile 0, a partial second K stage, a ragged second channel tile
     'glds128_taps': _pin(dict(_TAPS, tile=128), 'CK_GLDS_128', n_tiles=2, co_tiles=2, grid=4),
@@ -154,6 +156,15 @@ PINNED = {
     'mfma_x2': _pin(dict(_TAPS, with_x2=True), 'CK_MFMA_X2', n_tiles=2, co_tiles=2),
     'mfma_in_affine': _pin(dict(B=2, T=75, cin=72, cout=200, k=1, dil=1, in_affine=True, pre_act=0, affine=True, post_act=1), 'CK_MFMA_IN_AFFINE',
                            n_tiles=2, co_tiles=2),
+    # the HF encoder's layers 1 .. 6 (csrc/hfencoder.hip): unpadded stride-2 convs, k = 3 and the even k = 2, bias alone in the epilogue, three
+    # utterances so that boundaries fall inside a tile; each on the four tile families hf_forward's descriptor can plan to, at both parities of T_in
+    # (k = 3 at even T_in and k = 2 at odd T_in leave every utterance's last input row unread: the utterance's stride is not stride * T_out)
+    **{f'hf_k{k}_{fam}_T{T}{"" if bias else "_no_bias"}': _pin(dict(_HF, cin=cin, k=k, T=T, cout=256 if tile == 256 else 72, tile=tile, bias=bias),
+                                                              kernel)
+       for (cin, k) in ((256, 3), (512, 2))
+       for fam, tile, kernel, T0 in (('glds64', 64, 'CK_GLDS_64', 60), ('glds128', 128, 'CK_GLDS_128', 110), ('glds160', 160, 'CK_GLDS_160', 110),
+                                     ('persist', 256, 'CK_PERSIST_TAPS', 110))
+       for T, bias in ((T0, True), (T0 + 1, k == 3))},
 }
 # 10 to 20 s each under the emulator: MV_SLOW_EMU=1 (the device tier runs them all)
 SLOW_EMU = ('persist_taps_walk', 'ring_walk', 'ring_tail_quarters', 'ring_tail_sixteenths')
@@ -189,6 +200,9 @@ SAME_BITS = {
                                               (dict(tile=256), 'CK_PERSIST_TAPS')]),
     'dense_1x1_row_bias': (dict(_DENSE, k=1, dil=1, row_bias=True), [(dict(tile=64), 'CK_GLDS_64'), (dict(tile=128), 'CK_GLDS_128'),
                                                                       (dict(tile=160), 'CK_GLDS_160'), (dict(tile=256), 'CK_GLDS_256')]),
+    # the HF encoder's k = 3 stride-2 valid layer: "a row's bits do not depend on B" rests on every family accumulating strided taps in one order
+    'hf_valid_k3_s2': (dict(_HF, T=111, cin=256, cout=256, k=3), [(dict(tile=64), 'CK_GLDS_64'), (dict(tile=128), 'CK_GLDS_128'),
+                                                                   (dict(tile=160), 'CK_GLDS_160'), (dict(tile=256), 'CK_PERSIST_TAPS')]),
 }
 
 
@@ -228,6 +242,9 @@ PRODUCTION_LAYERS = {
     'campp_local': _layer(128, 32, k=3, dil=1, pad_mode='zero', pre_act=0, affine=False, gate=True, frames=149),
     'campp_transit1': _layer(512, 256, pre_act=0, affine=False, pad_mode='zero', frames=149),   # (tile = 256 from 16384 rows on: campplus.hip)
     'campp_transit2': _layer(1024, 512, pre_act=0, affine=False, pad_mode='zero', frames=149),
+    # the HF encoder (wav2vec2-base, one second of audio) as hf_forward fills the descriptor: no padding, stride 2, the bias (none without conv_bias) alone
+    'hf_conv_k3': _layer(512, 512, k=3, stride=2, pad=0, pad_mode='zero', pre_act=0, affine=False, bias=False, T_in=3199, frames=1599),   # layer 1
+    'hf_conv_k2': _layer(512, 512, k=2, stride=2, pad=0, pad_mode='zero', pre_act=0, affine=False, bias=False, T_in=199, frames=99),      # layer 5
 }
 ECAPA_BATCHES, CAMPP_BATCHES = (1, 8, 48, 256), (1, 256)
 
@@ -298,6 +315,14 @@ PRODUCTION_PLAN = {
     ('campp_transit1', 256): ('CK_RING', 149, 152, 0),
     ('campp_transit2', 1): ('CK_GLDS_64', 24, 24, 0),
     ('campp_transit2', 256): ('CK_RING+CK_GLDS_128_TAIL', 298, 256, 42),
+    ('hf_conv_k3', 1): ('CK_GLDS_64', 200, 200, 0),
+    ('hf_conv_k3', 8): ('CK_GLDS_128', 400, 400, 0),
+    ('hf_conv_k3', 48): ('CK_PERSIST_TAPS', 600, 256, 0),
+    ('hf_conv_k3', 256): ('CK_PERSIST_TAPS', 3198, 256, 0),
+    ('hf_conv_k2', 1): ('CK_GLDS_64', 16, 16, 0),
+    ('hf_conv_k2', 8): ('CK_GLDS_64', 104, 104, 0),
+    ('hf_conv_k2', 48): ('CK_GLDS_128', 152, 152, 0),
+    ('hf_conv_k2', 256): ('CK_PERSIST_TAPS', 198, 200, 0),
 }
 
 

@@ -27,7 +27,7 @@ def pack_weight(cdll, w):
 
 def conv1d_operands(B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, pad_mode='reflect', valid=False, x_f32=False, y_f32=False, with_x2=False,
                     in_affine=False, pre_act=1, affine=True, post_act=0, row_bias=False, gate_seg=0, extra_ld=8, second_out=False, seed=0, out_gain=1.0,
-                    **launch_only):
+                    bias=True, **launch_only):
     """The seeded fp32 operands of a conv1d_case on the CPU, by the case's keywords (tile, stats, ... only shape the launch): what conv1d_case
     uploads, and what the CPU self-checks of tests/conv1d_cases.py evaluate without a launch."""
     from types import SimpleNamespace
@@ -39,7 +39,7 @@ def conv1d_operands(B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, pad_mode='
     o.xfull = rn(B, T, o.ldx)
     o.x2full = rn(B, T, o.ldx) if with_x2 else None
     o.w = rn(cout, cin, k) * (2.0 / (cin * k)) ** 0.5
-    o.bias = rn(cout) * 0.1
+    o.bias = rn(cout) * 0.1 if bias else None   # None: a null bias pointer (the HF encoder's "group" mode without conv_bias)
     o.scale = (torch.rand(cout, generator=g) + 0.5) * out_gain if affine else None   # out_gain: drives the outputs beyond the fp16 range (saturation at +-65504)
     o.shift = rn(cout) * 0.1 if affine else None
     o.in_s = torch.rand(cin, generator=g) + 0.5 if in_affine else None
@@ -92,13 +92,13 @@ CONV_BOUND_MAX_K = 1024
 def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, pad_mode='reflect', valid=False,
                 x_f32=False, y_f32=False, with_x2=False, in_affine=False, pre_act=1, affine=True, post_act=0,
                 row_bias=False, gate_seg=0, extra_ld=8, second_out=False, tile=0, stats=0, in_stats=False, seed=0, persist_blocks=0, clock_probe=False, return_y=False, out_gain=1.0,
-                expect=None, plan_cus=None, log=None, tag=''):
+                bias=True, expect=None, plan_cus=None, log=None, tag=''):
     """expect: {'kernel': ..., ...} -- fields of mv_conv1d_plan_info the descriptor must plan to on this device, asserted before the launch.
     plan_cus: launch nothing; return {cus: plan info} of the case's descriptor for these compute-unit counts (the weights stay unpacked).
     log: receives the per-element bound's line (tests/conv1d_cases.py) where the bound applies."""
     o = conv1d_operands(B=B, T=T, cin=cin, cout=cout, k=k, dil=dil, stride=stride, pad_mode=pad_mode, valid=valid, x_f32=x_f32, y_f32=y_f32,
                         with_x2=with_x2, in_affine=in_affine, pre_act=pre_act, affine=affine, post_act=post_act, row_bias=row_bias,
-                        gate_seg=gate_seg, extra_ld=extra_ld, second_out=second_out, seed=seed, out_gain=out_gain)
+                        gate_seg=gate_seg, extra_ld=extra_ld, second_out=second_out, seed=seed, out_gain=out_gain, bias=bias)
     ldx, w, bias, scale, shift, in_s, in_t, pad, T_out, rb, gate = o.ldx, o.w, o.bias, o.scale, o.shift, o.in_s, o.in_t, o.pad, o.T_out, o.rb, o.gate
 
     xd = o.x.to(device)
@@ -114,7 +114,7 @@ def conv1d_case(cdll, device, B=2, T=37, cin=24, cout=40, k=3, dil=2, stride=1, 
     d.x_dtype = _hip.MV_DT_F32 if x_f32 else _hip.MV_DT_F16
     d.ldx = d.ldx2 = ldx
     d.in_scale, d.in_shift = (in_sd.data_ptr(), in_td.data_ptr()) if in_affine else (None, None)
-    d.w_packed, d.bias = packed.data_ptr(), biasd.data_ptr()
+    d.w_packed, d.bias = packed.data_ptr(), (None if biasd is None else biasd.data_ptr())
     d.row_bias = rbd.data_ptr() if row_bias else None
     d.pre_act, d.post_act = pre_act, post_act
     d.scale, d.shift = (scaled.data_ptr(), shiftd.data_ptr()) if affine else (None, None)
@@ -245,7 +245,7 @@ def conv1d_window_case(cdll, device, B=3, T=300, F_=80, k=5, cout=512, tile=0, s
     y = torch.full((B, T, cout + 8), 7.0, dtype=torch.float16, device=device)
     d = _hip.MvConv1dDesc()
     d.x, d.x_dtype, d.ldx = xp.data_ptr(), _hip.MV_DT_F16, F_
-    d.w_packed, d.bias = packed.data_ptr(), biasd.data_ptr()
+    d.w_packed, d.bias = packed.data_ptr(), (None if biasd is None else biasd.data_ptr())
     d.pre_act, d.post_act = 1, 0
     d.y, d.y_dtype, d.ldy = y.data_ptr(), _hip.MV_DT_F16, cout + 8
     d.B, d.T_in, d.T_out, d.cin, d.cout, d.k = B, T + 2 * pad, T, k * F_, cout, 1

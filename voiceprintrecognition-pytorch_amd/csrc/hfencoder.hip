@@ -38,6 +38,7 @@ constexpr int HF_L0_FR = 128;     // frames of layer 0 per workgroup: the chunk 
 constexpr int HF_L0_MAX_S = 8;    // largest stride of layer 0
 constexpr int HF_L0_MAX_K = 16;   // largest kernel of layer 0
 constexpr int HF_MAX_C = 1024;    // widest frame a wave holds in registers (16 per lane)
+constexpr float HF_ENC_EPS = 1e-5f;   // GroupNorm / LayerNorm of the feature encoder (nn defaults)
 
 // frames behind one valid (unpadded) strided conv: n -> floor((n - k) / s) + 1, 0 as soon as no whole window fits
 __host__ __device__ __forceinline__ int64_t hf_conv_frames(int64_t n, int k, int s) { return n >= k ? (n - k) / s + 1 : 0; }
@@ -118,7 +119,7 @@ struct HfL0Args {
     const float* bias;     // [C] or null
     const float* gamma;    // GroupNorm affine ("group") or null
     const float* beta;
-    const float* cstats;   // [B][C][2] mean, rstd ("group", APPLY)
+    float* cstats;         // [B][C][2] mean, rstd ("group": written by hf_l0_finish_kernel, read by APPLY)
     double* partial;       // [B][nchunk][C][2] sum, sum of squares (STATS)
     half_t* y;             // [B, T1, C]
     int T1, C, k, s, nchunk;
@@ -219,7 +220,7 @@ __global__ void hf_l0_finish_kernel(const double* partial, int B, int nchunk, in
     cstats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
-enum { HF_ROWS_GELU = 0, HF_ROWS_LN_GELU = 1, HF_ROWS_LN_F32 = 2 };
+enum { HF_ROWS_GELU = MV_HF_ROWS_GELU, HF_ROWS_LN_GELU = MV_HF_ROWS_LN_GELU, HF_ROWS_LN_F32 = MV_HF_ROWS_LN_F32 };
 
 // One wave per frame of a channel-last fp16 tensor, C <= 1024 values in registers.  GELU: elementwise, in place.  LN_GELU: LayerNorm over the C
 // channels (two passes over the registers, biased variance) + affine + GELU, fp16 out.  LN_F32: LayerNorm + affine, fp32 out (the features).
@@ -317,6 +318,48 @@ static int hf_rows_launch(const half_t* x, void* y, const float* gamma, const fl
     else
         MV_LAUNCH((hf_rows_kernel<MODE, false>), ((unsigned)grid, 1, 1), (HF_THREADS, 1, 1), 0, stream, x, y, gamma, beta, eps, n_rows, C);
     return check_launch("hf_rows_kernel");
+}
+
+static int hf_wave_stats_launch(const float* wav, int B, int64_t L, int64_t wav_stride, const int64_t* num_samples, float* stats, hipStream_t stream) {
+    MV_LAUNCH(hf_wave_stats_kernel, (B, 1, 1), (HF_THREADS, 1, 1), 0, stream, wav, L, wav_stride, num_samples, stats);
+    return check_launch("hf_wave_stats_kernel");
+}
+
+template <bool STATS>
+static void hf_l0_launch(const HfL0Args& a, int B, hipStream_t stream) {
+    if (a.k <= 10)
+        MV_LAUNCH((hf_l0_kernel<STATS, 10>), (a.nchunk, B, 1), (HF_THREADS, 1, 1), 0, stream, a);
+    else
+        MV_LAUNCH((hf_l0_kernel<STATS, HF_L0_MAX_K>), (a.nchunk, B, 1), (HF_THREADS, 1, 1), 0, stream, a);
+}
+
+// layer 0 of B rows.  gamma given ("group"): STATS into a.partial, the chunk sums into a.cstats, APPLY with GroupNorm + GELU; otherwise
+// ("layer", before its row pass) APPLY alone stores conv + bias.
+static int hf_layer0_launch(const HfL0Args& a, int B, hipStream_t stream) {
+    int rc;
+    if (a.gamma != nullptr) {
+        hf_l0_launch<true>(a, B, stream);
+        if ((rc = check_launch("hf_l0_kernel<STATS>"))) return rc;
+        const int64_t bc = (int64_t)B * a.C;
+        MV_LAUNCH(hf_l0_finish_kernel, ((unsigned)ceil_div(bc, HF_THREADS), 1, 1), (HF_THREADS, 1, 1), 0, stream, (const double*)a.partial, B, a.nchunk,
+                  a.C, a.num_samples, a.L, a.k, a.s, HF_ENC_EPS, a.cstats);
+        if ((rc = check_launch("hf_l0_finish_kernel"))) return rc;
+    }
+    hf_l0_launch<false>(a, B, stream);
+    return check_launch("hf_l0_kernel<APPLY>");
+}
+
+static int hf_cmn_mask_launch(float* out, const float* lens_ratio, const int64_t* num_samples, int64_t L, const HfGeom& g, int B, int T, int C, int cmn,
+                              hipStream_t stream) {
+    MV_LAUNCH(hf_cmn_mask_kernel, (B, C / 64, 1), (HF_THREADS, 1, 1), 0, stream, out, lens_ratio, num_samples, L, g, T, C, cmn);
+    return check_launch("hf_cmn_mask_kernel");
+}
+
+// the width rule of mv_hfenc_create, for the layer-level entry points
+static int hf_check_width(const char* who, int C) {
+    if (C < 64 || C > HF_MAX_C || C % 64 != 0)
+        return fail(MV_ERR_UNSUPPORTED, std::string(who) + ": C = " + std::to_string(C) + ": the kernels are built for widths that are multiples of 64 up to 1024");
+    return MV_OK;
 }
 
 }  // namespace mv
@@ -439,14 +482,6 @@ int hf_create(const MvHfEncoderCfg* cfg, const MvTensorRef* tensors, int32_t n, 
     return MV_OK;
 }
 
-template <bool STATS>
-void hf_l0_launch(const HfL0Args& a, int B, hipStream_t stream) {
-    if (a.k <= 10)
-        MV_LAUNCH((hf_l0_kernel<STATS, 10>), (a.nchunk, B, 1), (HF_THREADS, 1, 1), 0, stream, a);
-    else
-        MV_LAUNCH((hf_l0_kernel<STATS, HF_L0_MAX_K>), (a.nchunk, B, 1), (HF_THREADS, 1, 1), 0, stream, a);
-}
-
 }  // namespace
 
 extern "C" {
@@ -530,10 +565,7 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
     const bool group = c.feat_extract_norm == MV_HF_NORM_GROUP;
 
     if (ev != nullptr) MV_HIP_OK(hipEventRecord(ev[0], stream));
-    if (c.do_normalize) {
-        MV_LAUNCH(hf_wave_stats_kernel, (B, 1, 1), (HF_THREADS, 1, 1), 0, stream, wav, L, wav_stride, num_samples, s.wstats);
-        if ((rc = check_launch("hf_wave_stats_kernel"))) return rc;
-    }
+    if (c.do_normalize && (rc = hf_wave_stats_launch(wav, B, L, wav_stride, num_samples, s.wstats, stream))) return rc;
     HfL0Args a = {};
     a.wav = wav;
     a.L = L;
@@ -542,6 +574,8 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
     a.wstats = c.do_normalize ? s.wstats : nullptr;
     a.w = h->w0;
     a.bias = h->bias[0];
+    a.gamma = group ? h->ln_w[0] : nullptr;
+    a.beta = group ? h->ln_b[0] : nullptr;
     a.partial = s.partial;
     a.cstats = s.cstats;
     a.y = s.buf[0];
@@ -550,19 +584,8 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
     a.k = c.conv_kernel[0];
     a.s = c.conv_stride[0];
     a.nchunk = (int)ceil_div(T[0], HF_L0_FR);
-    if (group) {
-        hf_l0_launch<true>(a, B, stream);
-        if ((rc = check_launch("hf_l0_kernel<STATS>"))) return rc;
-        const int64_t bc = (int64_t)B * a.C;
-        MV_LAUNCH(hf_l0_finish_kernel, ((unsigned)ceil_div(bc, HF_THREADS), 1, 1), (HF_THREADS, 1, 1), 0, stream, (const double*)s.partial, B, a.nchunk,
-                  a.C, num_samples, L, a.k, a.s, 1e-5f, s.cstats);
-        if ((rc = check_launch("hf_l0_finish_kernel"))) return rc;
-        a.gamma = h->ln_w[0];
-        a.beta = h->ln_b[0];
-    }
-    hf_l0_launch<false>(a, B, stream);
-    if ((rc = check_launch("hf_l0_kernel<APPLY>"))) return rc;
-    if (!group && (rc = hf_rows_launch<HF_ROWS_LN_GELU>(s.buf[0], s.buf[0], h->ln_w[0], h->ln_b[0], 1e-5f, (int64_t)B * T[0], a.C, stream))) return rc;
+    if ((rc = hf_layer0_launch(a, B, stream))) return rc;
+    if (!group && (rc = hf_rows_launch<HF_ROWS_LN_GELU>(s.buf[0], s.buf[0], h->ln_w[0], h->ln_b[0], HF_ENC_EPS, (int64_t)B * T[0], a.C, stream))) return rc;
     if (ev != nullptr) MV_HIP_OK(hipEventRecord(ev[1], stream));
 
     for (int i = 1; i < n; ++i) {
@@ -589,7 +612,7 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
         if (group)
             rc = hf_rows_launch<HF_ROWS_GELU>(s.buf[i & 1], s.buf[i & 1], nullptr, nullptr, 0.0f, rows, c.conv_dim[i], stream);
         else
-            rc = hf_rows_launch<HF_ROWS_LN_GELU>(s.buf[i & 1], s.buf[i & 1], h->ln_w[i], h->ln_b[i], 1e-5f, rows, c.conv_dim[i], stream);
+            rc = hf_rows_launch<HF_ROWS_LN_GELU>(s.buf[i & 1], s.buf[i & 1], h->ln_w[i], h->ln_b[i], HF_ENC_EPS, rows, c.conv_dim[i], stream);
         if (rc != MV_OK) return rc;
         if (ev != nullptr) MV_HIP_OK(hipEventRecord(ev[i + 1], stream));
     }
@@ -601,9 +624,7 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
         g.k[i] = c.conv_kernel[i];
         g.s[i] = c.conv_stride[i];
     }
-    MV_LAUNCH(hf_cmn_mask_kernel, (B, CL / 64, 1), (HF_THREADS, 1, 1), 0, stream, out, lens_ratio, num_samples, L, g, TL, CL,
-              c.subtract_time_mean ? 1 : 0);
-    if ((rc = check_launch("hf_cmn_mask_kernel"))) return rc;
+    if ((rc = hf_cmn_mask_launch(out, lens_ratio, num_samples, L, g, B, TL, CL, c.subtract_time_mean ? 1 : 0, stream))) return rc;
     if (ev != nullptr) MV_HIP_OK(hipEventRecord(ev[n + 1], stream));
     return MV_OK;
 }
@@ -611,6 +632,112 @@ int hf_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int
 }  // namespace
 
 extern "C" {
+
+// ---- the kernels of the forward one at a time (layer-level checks): the launch helpers of hf_forward behind argument checks of their own ----
+
+int mv_hfenc_wave_stats(const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples, float* stats, mv_stream_t stream) {
+    MV_REQUIRE(wav != nullptr && stats != nullptr, "mv_hfenc_wave_stats: null argument");
+    MV_REQUIRE(B > 0 && B <= 65535, "mv_hfenc_wave_stats: batch size must be 1 .. 65535");
+    MV_REQUIRE(L >= 0 && wav_stride >= L, "mv_hfenc_wave_stats: wav_stride below the row length");
+    return hf_wave_stats_launch(wav, B, L, wav_stride, num_samples, stats, static_cast<hipStream_t>(stream));
+}
+
+int mv_hfenc_layer0_workspace_bytes(int32_t B, int64_t L, int32_t C, int32_t k, int32_t s, size_t* bytes) {
+    MV_REQUIRE(bytes != nullptr, "mv_hfenc_layer0_workspace_bytes: null argument");
+    MV_REQUIRE(B >= 0 && L >= 0 && C >= 0 && k >= 1 && s >= 1, "mv_hfenc_layer0_workspace_bytes: negative size");
+    *bytes = (size_t)B * (size_t)ceil_div(hf_conv_frames(L, k, s), HF_L0_FR) * (size_t)C * 2 * sizeof(double);
+    return MV_OK;
+}
+
+int mv_hfenc_layer0(const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples, const float* wstats, const float* w,
+                    const float* bias, const float* gamma, const float* beta, int32_t C, int32_t k, int32_t s, void* y, float* cstats, void* workspace,
+                    size_t workspace_bytes, mv_stream_t stream) {
+    MV_REQUIRE(wav != nullptr && w != nullptr && y != nullptr, "mv_hfenc_layer0: null argument");
+    MV_REQUIRE((gamma == nullptr) == (beta == nullptr), "mv_hfenc_layer0: gamma and beta come together (GroupNorm) or not at all");
+    MV_REQUIRE(B > 0 && B <= 65535, "mv_hfenc_layer0: batch size must be 1 .. 65535");
+    MV_REQUIRE(L >= 0 && wav_stride >= L, "mv_hfenc_layer0: wav_stride below the row length");
+    int rc;
+    if ((rc = hf_check_width("mv_hfenc_layer0", C))) return rc;
+    if (k < 1 || s < 1 || k > HF_L0_MAX_K || s > HF_L0_MAX_S)
+        return fail(MV_ERR_UNSUPPORTED, "mv_hfenc_layer0: layer 0 is built for 1 <= k <= 16 and 1 <= s <= 8");
+    const int64_t T0 = hf_conv_frames(L, k, s);
+    MV_REQUIRE(T0 > 0, "mv_hfenc_layer0: a waveform shorter than the kernel: no frame");
+    MV_REQUIRE((int64_t)B * T0 < ((int64_t)1 << 31) - 512, "mv_hfenc_layer0: too many frames for 32-bit row indexing");
+    HfL0Args a = {};
+    a.wav = wav;
+    a.L = L;
+    a.wav_stride = wav_stride;
+    a.num_samples = num_samples;
+    a.wstats = wstats;
+    a.w = w;
+    a.bias = bias;
+    a.gamma = gamma;
+    a.beta = beta;
+    a.partial = static_cast<double*>(workspace);
+    a.cstats = cstats;
+    a.y = static_cast<half_t*>(y);
+    a.T1 = (int)T0;
+    a.C = C;
+    a.k = k;
+    a.s = s;
+    a.nchunk = (int)ceil_div(T0, HF_L0_FR);
+    if (gamma != nullptr) {
+        MV_REQUIRE(cstats != nullptr, "mv_hfenc_layer0: GroupNorm needs cstats");
+        const size_t need = (size_t)B * a.nchunk * C * 2 * sizeof(double);
+        if (workspace == nullptr || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0)
+            return fail(MV_ERR_WORKSPACE, "mv_hfenc_layer0: workspace of " + std::to_string(need) + " bytes (8-byte aligned) required");
+    }
+    return hf_layer0_launch(a, B, static_cast<hipStream_t>(stream));
+}
+
+int mv_hfenc_rows(const void* x, void* y, const float* gamma, const float* beta, float eps, int64_t n_rows, int32_t C, int32_t mode,
+                  mv_stream_t stream_) {
+    MV_REQUIRE(x != nullptr && y != nullptr, "mv_hfenc_rows: null argument");
+    MV_REQUIRE(mode == MV_HF_ROWS_GELU || mode == MV_HF_ROWS_LN_GELU || mode == MV_HF_ROWS_LN_F32,
+               "mv_hfenc_rows: mode must be MV_HF_ROWS_GELU, MV_HF_ROWS_LN_GELU or MV_HF_ROWS_LN_F32");
+    MV_REQUIRE(n_rows > 0, "mv_hfenc_rows: n_rows must be positive");
+    int rc;
+    if ((rc = hf_check_width("mv_hfenc_rows", C))) return rc;
+    if (mode != MV_HF_ROWS_GELU) {
+        MV_REQUIRE(gamma != nullptr && beta != nullptr, "mv_hfenc_rows: LayerNorm needs gamma and beta");
+        MV_REQUIRE(eps > 0.0f, "mv_hfenc_rows: eps must be positive");
+    }
+    if (mode == MV_HF_ROWS_LN_F32) MV_REQUIRE(x != y, "mv_hfenc_rows: the fp32 output cannot share the fp16 input's buffer");
+    if (C == 512)
+        MV_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0,
+                   "mv_hfenc_rows: x and y must be 16-byte aligned at C = 512 (16-byte loads and stores)");
+    hipStream_t stream = static_cast<hipStream_t>(stream_);
+    const half_t* xh = static_cast<const half_t*>(x);
+    switch (mode) {
+        case MV_HF_ROWS_GELU: return hf_rows_launch<HF_ROWS_GELU>(xh, y, nullptr, nullptr, 0.0f, n_rows, C, stream);
+        case MV_HF_ROWS_LN_GELU: return hf_rows_launch<HF_ROWS_LN_GELU>(xh, y, gamma, beta, eps, n_rows, C, stream);
+        default: return hf_rows_launch<HF_ROWS_LN_F32>(xh, y, gamma, beta, eps, n_rows, C, stream);
+    }
+}
+
+int mv_hfenc_cmn_mask(float* out, int32_t B, int32_t T, int32_t C, const float* lens_ratio, const int64_t* num_samples, int64_t L,
+                      const int32_t* conv_kernel, const int32_t* conv_stride, int32_t num_layers, int32_t cmn, mv_stream_t stream) {
+    MV_REQUIRE(out != nullptr, "mv_hfenc_cmn_mask: null argument");
+    MV_REQUIRE(lens_ratio == nullptr || num_samples == nullptr, "mv_hfenc_cmn_mask: lens_ratio or num_samples, not both");
+    MV_REQUIRE(B > 0 && B <= 65535, "mv_hfenc_cmn_mask: batch size must be 1 .. 65535");
+    MV_REQUIRE(T > 0, "mv_hfenc_cmn_mask: T must be positive");
+    int rc;
+    if ((rc = hf_check_width("mv_hfenc_cmn_mask", C))) return rc;
+    HfGeom g = {};
+    if (num_samples != nullptr) {   // the row's own frame count comes from its samples: T has to be the count of a full row
+        MV_REQUIRE(conv_kernel != nullptr && conv_stride != nullptr, "mv_hfenc_cmn_mask: num_samples needs the layers' kernels and strides");
+        MV_REQUIRE(num_layers >= 1 && num_layers <= MV_HFENC_MAX_LAYERS, "mv_hfenc_cmn_mask: num_layers must be 1 .. MV_HFENC_MAX_LAYERS (8)");
+        g.n = num_layers;
+        for (int i = 0; i < num_layers; ++i) {
+            MV_REQUIRE(conv_kernel[i] >= 1 && conv_stride[i] >= 1 && conv_kernel[i] <= 64 && conv_stride[i] <= 64,
+                       "mv_hfenc_cmn_mask: conv_kernel / conv_stride must be 1 .. 64");
+            g.k[i] = conv_kernel[i];
+            g.s[i] = conv_stride[i];
+        }
+        MV_REQUIRE(L >= 0 && hf_frames_behind(g, L) == T, "mv_hfenc_cmn_mask: T is not the frame count of L samples behind these layers");
+    }
+    return hf_cmn_mask_launch(out, lens_ratio, num_samples, L, g, B, T, C, cmn ? 1 : 0, static_cast<hipStream_t>(stream));
+}
 
 int mv_hfenc_forward(const MvHfEncoder* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, float* out,
                      void* workspace, size_t workspace_bytes, mv_stream_t stream) {

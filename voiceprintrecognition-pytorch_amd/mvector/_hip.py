@@ -51,6 +51,7 @@ class MvMfccCfg(ctypes.Structure):
 MV_HFENC_MAX_LAYERS = 8
 MV_HF_NORM_GROUP, MV_HF_NORM_LAYER = 0, 1
 MV_ACT_GELU = 4
+MV_HF_ROWS_GELU, MV_HF_ROWS_LN_GELU, MV_HF_ROWS_LN_F32 = 0, 1, 2
 
 
 class MvHfEncoderCfg(ctypes.Structure):
@@ -292,6 +293,11 @@ _SIGNATURES = {
     'mv_hfenc_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_hfenc_forward_varlen': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_hfenc_forward_timed': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp, ctypes.POINTER(c_f32), c_i32]),
+    'mv_hfenc_wave_stats': (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    'mv_hfenc_layer0_workspace_bytes': (c_i32, [c_i32, c_i64, c_i32, c_i32, c_i32, ctypes.POINTER(c_sz)]),
+    'mv_hfenc_layer0': (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_hfenc_rows': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_vp]),
+    'mv_hfenc_cmn_mask': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i32, c_i32, c_vp]),
     'mv_fcm_conv3x3_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'mv_fcm_block_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
     'mv_fcm_block_c1_f16': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
