@@ -368,6 +368,67 @@ int mv_hfenc_cmn_mask(float* out, int32_t B, int32_t T, int32_t C, const float* 
                       const int32_t* conv_kernel, const int32_t* conv_stride, int32_t num_layers, int32_t cmn, mv_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Front-end 6: a HuggingFace Wav2Vec2-BERT model's (facebook/w2v-bert-2.0) `extract_features` + time-mean subtraction + mask
+ * (csrc/w2vbert.hip).  For Wav2Vec2BertModel that is feature_projection.layer_norm(input_features), and input_features is what the
+ * SeamlessM4TFeatureExtractor computes on the host: waveform * 2^15 -> Kaldi log-mel (80 bins, 25 / 10 ms at 16 kHz, Povey window, pre-emphasis
+ * 0.97, DC removal, 512-point transform, mel banks 20 Hz .. Nyquist, floor 1.192092955078125e-07, snip_edges) -> per mel bin over the row's T
+ * frames (x - mean) / sqrt(var(ddof = 1) + 1e-7) -> zero frames up to a multiple of `stride` -> `stride` frames stacked into stride * 80
+ * columns; then the model's LayerNorm over those columns and featurizer.py:79-90.  The log-mel runs on an Fbank handle of this handle's own
+ * whose window table carries the 2^15 (exact: a power of two); frames T = 1 + (n - 400) / 160 for n >= 400, stacked frames T2 = ceil(T / stride).
+ * Output [B, T2, stride * num_mel_bins] fp32.  None of the transformer is evaluated.  Additive since ABI 5.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct MvW2vBertCfg {
+    int32_t num_mel_bins;        /* 80; anything else: MV_ERR_UNSUPPORTED */
+    int32_t stride;              /* 2; anything else: MV_ERR_UNSUPPORTED */
+    int32_t sampling_rate;       /* 16000; anything else: MV_ERR_UNSUPPORTED */
+    float layer_norm_eps;        /* of feature_projection.layer_norm (config.layer_norm_eps); positive */
+    int32_t subtract_time_mean;  /* 1: featurizer.py:79 */
+} MvW2vBertCfg;
+
+typedef struct MvW2vBert MvW2vBert;
+
+/* ln_weight, ln_bias: feature_projection.layer_norm.{weight, bias}, stride * num_mel_bins fp32 each, HOST pointers (copied).  The handle owns
+ * its tables and no mutable state: forwards on different streams with different workspaces may run concurrently. */
+int mv_w2vbert_create(const MvW2vBertCfg* cfg, const float* ln_weight, const float* ln_bias, MvW2vBert** out);
+int mv_w2vbert_destroy(MvW2vBert* h);
+/* stacked frames T2 of a row of num_samples samples (0 below 400 samples) */
+int mv_w2vbert_num_frames(const MvW2vBert* h, int64_t num_samples, int64_t* num_frames);
+int mv_w2vbert_workspace_bytes(const MvW2vBert* h, int32_t B, int64_t L, size_t* bytes);
+/* wav [B, L] fp32 rows wav_stride apart; lens_ratio [B] fp32 or NULL (stacked frames t >= round_half_even(ratio * T2) are zeroed); out
+ * [B, T2, stride * num_mel_bins] fp32 contiguous, 16-byte aligned; workspace: mv_w2vbert_workspace_bytes(h, B, L) bytes, 16-byte aligned.  Every
+ * row is normalised over all T frames of the padded length L (the reference's behaviour behind collate_fn).  L < 560 (fewer than two frames: the
+ * reference's var(ddof = 1) is NaN, below 400 samples its extractor raises) is refused by name.  Launches only, no host synchronisation; a row's
+ * bits depend on the row alone: not on B, the other rows, the stream or what out and the workspace held.  B = 0 returns MV_OK and touches
+ * nothing.  MV_ERR_INVALID_ARGUMENT: a null pointer, negative sizes, wav_stride < L, a misaligned out; MV_ERR_WORKSPACE: a short or misaligned
+ * workspace. */
+int mv_w2vbert_forward(const MvW2vBert* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const float* lens_ratio, float* out,
+                       void* workspace, size_t workspace_bytes, mv_stream_t stream);
+/* Variable-length batch: row b holds n_b = clamp(num_samples[b], 0, L) valid samples (device array, int64, B entries, read on the device only).
+ * Row b is featurised as if alone -- own T_b, own per-bin statistics, own zero half-frame when T_b is odd, own time mean over its T2_b stacked
+ * frames, zeros behind -- and BIT FOR BIT equals mv_w2vbert_forward of the same handle on that row as a [1, n_b] batch without a ratio.  A row with
+ * n_b < 560 is all zero; samples at or behind n_b are never read (NaN included).  The output keeps the shape [B, T2(L), .]; T2(L) = 0 touches
+ * nothing. */
+int mv_w2vbert_forward_varlen(const MvW2vBert* h, const float* wav, int32_t B, int64_t L, int64_t wav_stride, const int64_t* num_samples,
+                              float* out, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+/* The new kernels of the forward one at a time (kernel-level checks; the forward reaches them through the same launch code).  Device pointers;
+ * built for 80 bins and stride 2; a refused call names what is wrong and launches nothing.  num_samples [B] int64 or NULL: the row's frames are
+ * T_b = frames of clamp(num_samples[b], 0, L) samples, 0 below 560 samples (T must then be the frame count of L samples); NULL: T_b = T.
+ *
+ * mv_w2vbert_binstats_f32: x [B, T, 80] fp32 -> mean, var [B, 80] fp32: per bin over the row's T_b >= 2 frames the mean and the unbiased variance,
+ *   centred two-pass in fp64 in one fixed order (partial sums of 16-frame tiles folded in tile order), rounded once to fp32; (0, 0) where T_b = 0. */
+int mv_w2vbert_binstats_f32(const float* x, int32_t B, int32_t T, const int64_t* num_samples, int64_t L, float* mean, float* var, mv_stream_t stream);
+/* mv_w2vbert_rows_f32: z = (x - mean) / sqrt(var + 1e-7), zeros for frames t >= T_b; frames 2 t2, 2 t2 + 1 stacked into 160 columns; LayerNorm over
+ *   them (biased variance, eps) times ln_weight plus ln_bias -> out [B, ceil(T / 2), 160] fp32; stacked frames at or behind ceil(T_b / 2) are zero
+ *   rows.  x, mean, var, ln_weight, ln_bias and out 16-byte aligned (16-byte loads and stores). */
+int mv_w2vbert_rows_f32(const float* x, const float* mean, const float* var, const float* ln_weight, const float* ln_bias, float eps, int32_t B,
+                        int32_t T, const int64_t* num_samples, int64_t L, float* out, mv_stream_t stream);
+/* mv_w2vbert_cmn_mask_f32: out [B, T2, 160] fp32 in place: minus the mean over the row's stacked frames (cmn != 0; summed in fp64 in one fixed
+ *   order, rounded once), then zeros behind the mask length.  lens_ratio [B] or NULL: all T2 frames count, zeros from round_half_even(ratio * T2)
+ *   on.  num_samples [B] or NULL (not both; T2 must be the count of L samples): the mean runs over the row's own T2_b frames, zeros from T2_b on. */
+int mv_w2vbert_cmn_mask_f32(float* out, int32_t B, int32_t T2, const float* lens_ratio, const int64_t* num_samples, int64_t L, int32_t cmn,
+                            mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Backbones.  A model handle is built from the reference-layout fp32 ``state_dict`` (same key names
  * and shapes as the reference modules, so ``model.pth`` loads unchanged: mvector/utils/checkpoint.py:
  * 11-51).  create() folds eval-mode BatchNorm into per-channel scale/shift, packs conv weights to the

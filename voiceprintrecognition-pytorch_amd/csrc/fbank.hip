@@ -1027,7 +1027,9 @@ int check_cfg(const MvFbankCfg* cfg, int win, int shift) {
 }
 
 // torchaudio.compliance.kaldi._feature_window_function (all symmetric, periodic=False) on the 512-point grid, zero beyond the frame length, and its half
-void kaldi_window(const MvFbankCfg* cfg, int win, std::vector<float>* window, std::vector<float>* window_half) {
+// `scale` (a power of two; 1 for mv_fbank_create) multiplies every tap: exact, and the same as featurising scale * waveform -- every step up to the power
+// spectrum is linear, so a power of two commutes with each of its roundings
+void kaldi_window(const MvFbankCfg* cfg, int win, float scale, std::vector<float>* window, std::vector<float>* window_half) {
     const double pi = 3.14159265358979323846;
     window->assign(512, 0.0f);
     window_half->assign(512, 0.0f);
@@ -1038,7 +1040,7 @@ void kaldi_window(const MvFbankCfg* cfg, int win, std::vector<float>* window, st
         if (cfg->window_type == MV_WINDOW_HANNING) w = 0.5 - 0.5 * cos(a * i);
         if (cfg->window_type == MV_WINDOW_HAMMING) w = 0.54 - 0.46 * cos(a * i);
         if (cfg->window_type == MV_WINDOW_BLACKMAN) w = cfg->blackman_coeff - 0.5 * cos(a * i) + (0.5 - cfg->blackman_coeff) * cos(2.0 * a * i);
-        (*window)[i] = (float)w;
+        (*window)[i] = (float)w * scale;
         (*window_half)[i] = 0.5f * (*window)[i];  // exact: the halved spectrum squares to |X|^2 without a final scale
     }
 }
@@ -1126,9 +1128,17 @@ void mv_fbank_default_cfg(MvFbankCfg* cfg) {
     cfg->htk_compat = 0;
 }
 
+int mv_fbank_create(const MvFbankCfg* cfg, MvFbank** out) { return mv::fbank_create_scaled(cfg, 1.0f, out); }
+
+}  // extern "C"
+
 // checks, the host tables, their upload, then the kernel: fbank_tile_kernel where the geometry has an instantiation, else fbank_kernel
-int mv_fbank_create(const MvFbankCfg* cfg, MvFbank** out) {
+int mv::fbank_create_scaled(const MvFbankCfg* cfg, float window_scale, MvFbank** out) {
     MV_REQUIRE(cfg != nullptr && out != nullptr, "mv_fbank_create: null argument");
+    {
+        int e = 0;
+        MV_REQUIRE(window_scale > 0.0f && frexpf(window_scale, &e) == 0.5f, "mv_fbank_create: the window scale must be a power of two");
+    }
     const int win = (int)(cfg->sample_frequency * cfg->frame_length_ms * 0.001f);
     const int shift = (int)(cfg->sample_frequency * cfg->frame_shift_ms * 0.001f);
     int rc = check_cfg(cfg, win, shift);
@@ -1145,7 +1155,7 @@ int mv_fbank_create(const MvFbankCfg* cfg, MvFbank** out) {
 
     std::vector<float> window, window_half, tw256, tw512, melb;
     std::vector<std::vector<float>> banks;
-    kaldi_window(cfg, win, &window, &window_half);
+    kaldi_window(cfg, win, window_scale, &window, &window_half);
     fft_twiddles(&tw256, &tw512);
     if (!banks_on_fft_grid(h.get(), &banks))
         return mv::fail(MV_ERR_INVALID_ARGUMENT, "mv_fbank_create: bad VTLN options (need low_freq < vtln_low < vtln_high < high_freq, and the warped cut-offs inside the band)");
@@ -1177,6 +1187,8 @@ int mv_fbank_create(const MvFbankCfg* cfg, MvFbank** out) {
     *out = h.release();
     return MV_OK;
 }
+
+extern "C" {
 
 int mv_fbank_destroy(MvFbank* h) {
     if (h == nullptr) return MV_OK;

@@ -245,6 +245,10 @@ inline bool build_mel_plan(const std::vector<std::vector<float>>& banks, int row
     return true;
 }
 
+// mv_fbank_create with every window tap times `window_scale`, a power of two: the handle featurises window_scale * waveform exactly, without a pass over
+// the waveform (w2vbert.hip: the 2^15 of the SeamlessM4T extractor).  mv_fbank_create is this with 1; the handle is an ordinary one (mv_fbank_destroy).
+int fbank_create_scaled(const MvFbankCfg* cfg, float window_scale, MvFbank** out);
+
 // a host table to a device buffer of its own, which the handle's destroy call frees
 template <typename T>
 int upload_vec(const std::vector<T>& v, T** dptr) {

@@ -60,6 +60,10 @@ class MvHfEncoderCfg(ctypes.Structure):
                 ('activation', c_i32), ('layer_norm_eps', c_f32), ('subtract_time_mean', c_i32)]
 
 
+class MvW2vBertCfg(ctypes.Structure):
+    _fields_ = [('num_mel_bins', c_i32), ('stride', c_i32), ('sampling_rate', c_i32), ('layer_norm_eps', c_f32), ('subtract_time_mean', c_i32)]
+
+
 class MvTensorRef(ctypes.Structure):
     _fields_ = [('name', ctypes.c_char_p), ('data', c_vp), ('numel', c_i64)]
 
@@ -298,6 +302,15 @@ _SIGNATURES = {
     'mv_hfenc_layer0': (c_i32, [c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_hfenc_rows': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_f32, c_i64, c_i32, c_i32, c_vp]),
     'mv_hfenc_cmn_mask': (c_i32, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32), c_i32, c_i32, c_vp]),
+    'mv_w2vbert_create': (c_i32, [ctypes.POINTER(MvW2vBertCfg), c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    'mv_w2vbert_destroy': (c_i32, [c_vp]),
+    'mv_w2vbert_num_frames': (c_i32, [c_vp, c_i64, ctypes.POINTER(c_i64)]),
+    'mv_w2vbert_workspace_bytes': (c_i32, [c_vp, c_i32, c_i64, ctypes.POINTER(c_sz)]),
+    'mv_w2vbert_forward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_w2vbert_forward_varlen': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_w2vbert_binstats_f32': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    'mv_w2vbert_rows_f32': (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_f32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp]),
+    'mv_w2vbert_cmn_mask_f32': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_i64, c_i32, c_vp]),
     'mv_fcm_conv3x3_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     'mv_fcm_block_f16': (c_i32, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
     'mv_fcm_block_c1_f16': (c_i32, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp]),
@@ -811,6 +824,109 @@ class HfEncoder(_FrontEnd):
         check(self._cdll.mv_hfenc_forward(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens_ratio), out.data_ptr(), ws.data_ptr(), need.value,
                                           current_stream(wav)), self._cdll)
         return out
+
+
+def _w2vbert_row_args(x, num_samples, L):
+    """what the kernel-level entry points of the Wav2Vec2-BERT front-end share: fp32 contiguous rows, the optional int64 lengths on their device"""
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    if num_samples is not None:
+        num_samples = torch.as_tensor(num_samples).to(device=x.device, dtype=torch.int64).contiguous()
+    return num_samples, int(L if L is not None else 0)
+
+
+def w2vbert_binstats(x, num_samples=None, L=None, cdll=None):
+    """mv_w2vbert_binstats_f32: x [B, T, 80] fp32 -> (mean, var) [B, 80]: per bin over the row's frames, unbiased variance, fp64 sums rounded once.
+    ``num_samples`` (int64 [B]) with the padded length ``L``: the row's own frame count (0 below 560 samples)."""
+    cdll = cdll or lib()
+    num_samples, L = _w2vbert_row_args(x, num_samples, L)
+    B, T, _ = x.shape
+    mean, var = torch.empty((B, 80), dtype=torch.float32, device=x.device), torch.empty((B, 80), dtype=torch.float32, device=x.device)
+    check(cdll.mv_w2vbert_binstats_f32(x.data_ptr(), B, T, _ptr(num_samples), L, mean.data_ptr(), var.data_ptr(), current_stream(x)), cdll)
+    return mean, var
+
+
+def w2vbert_rows(x, mean, var, ln_weight, ln_bias, eps, num_samples=None, L=None, out=None, cdll=None):
+    """mv_w2vbert_rows_f32: normalise x [B, T, 80] with (mean, var) [B, 80], stack pairs of frames (a frame behind the row's count is zeros),
+    LayerNorm over the 160 columns -> [B, ceil(T / 2), 160].  ``out``: a buffer to write into (tests prefill it)."""
+    cdll = cdll or lib()
+    num_samples, L = _w2vbert_row_args(x, num_samples, L)
+    B, T, _ = x.shape
+    if out is None:
+        out = torch.empty((B, (T + 1) // 2, 160), dtype=torch.float32, device=x.device)
+    check(cdll.mv_w2vbert_rows_f32(x.data_ptr(), mean.data_ptr(), var.data_ptr(), ln_weight.data_ptr(), ln_bias.data_ptr(), eps, B, T,
+                                   _ptr(num_samples), L, out.data_ptr(), current_stream(x)), cdll)
+    return out
+
+
+def w2vbert_cmn_mask(out, lens_ratio=None, num_samples=None, L=None, cmn=True, cdll=None):
+    """mv_w2vbert_cmn_mask_f32, in place on out [B, T2, 160]: minus the time mean over the row's stacked frames, zeros behind the mask length"""
+    cdll = cdll or lib()
+    num_samples, L = _w2vbert_row_args(out, num_samples, L)
+    if lens_ratio is not None:
+        lens_ratio = lens_ratio.to(device=out.device, dtype=torch.float32).contiguous()
+    B, T2, _ = out.shape
+    check(cdll.mv_w2vbert_cmn_mask_f32(out.data_ptr(), B, T2, _ptr(lens_ratio), _ptr(num_samples), L, 1 if cmn else 0, current_stream(out)), cdll)
+    return out
+
+
+class W2vBert(_FrontEnd):
+    """Handle of the HuggingFace Wav2Vec2-BERT (w2v-bert-2.0) front-end (mv_w2vbert_*): the SeamlessM4TFeatureExtractor's input_features (waveform *
+    2^15, 80-bin Kaldi log-mel, per-bin normalisation over time, pairs of frames stacked) and feature_projection.layer_norm -- `extract_features`
+    --, then AudioFeaturizer's time mean and mask.  Output [B, T2, stride * num_mel_bins].
+
+    ``cfg``: a dict with the processor's ``num_mel_bins``, ``stride``, ``sampling_rate`` and the model config's ``layer_norm_eps``;
+    ``state_dict``: holds ``feature_projection.layer_norm.weight`` / ``.bias``.  ``device``: where the handle is to run (None: the current
+    device; the emulator build ignores it).  Needs no `transformers`."""
+
+    _prefix = 'mv_w2vbert_'
+
+    def __init__(self, cfg, state_dict, device=None, subtract_time_mean=True, cdll=None):
+        self._cdll = cdll or lib()
+        c = MvW2vBertCfg()
+        c.num_mel_bins = int(cfg.get('num_mel_bins', 80))
+        c.stride = int(cfg.get('stride', 2))
+        c.sampling_rate = int(cfg.get('sampling_rate', 16000))
+        c.layer_norm_eps = float(cfg.get('layer_norm_eps', 1e-5))
+        c.subtract_time_mean = 1 if subtract_time_mean else 0
+        self.dim = c.num_mel_bins * c.stride
+        ln = []
+        for k in ('feature_projection.layer_norm.weight', 'feature_projection.layer_norm.bias'):
+            if k not in state_dict:
+                raise KeyError(f'W2vBert: the state_dict has no {k!r}')
+            t = state_dict[k].detach().to(device='cpu', dtype=torch.float32).contiguous()
+            if t.numel() != self.dim:
+                raise ValueError(f'W2vBert: {k!r} has {t.numel()} elements, expected stride * num_mel_bins = {self.dim}')
+            ln.append(t)
+        self._h = c_vp()
+        if device is not None and torch.device(device).type == 'cuda':
+            with torch.cuda.device(device):
+                check(self._cdll.mv_w2vbert_create(ctypes.byref(c), ln[0].data_ptr(), ln[1].data_ptr(), ctypes.byref(self._h)), self._cdll)
+        else:
+            check(self._cdll.mv_w2vbert_create(ctypes.byref(c), ln[0].data_ptr(), ln[1].data_ptr(), ctypes.byref(self._h)), self._cdll)
+
+    def __call__(self, wav, lens_ratio=None, num_samples=None):
+        """wav [B, L] fp32 -> [B, T2, dim] fp32 on the same device, the caller's stream, a workspace per call: one native call.  ``lens_ratio``:
+        the reference's batched semantics (every row normalised over all frames of the padded length, then the mask).  ``num_samples`` (int64
+        [B]): every row featurised on its own length, zero frames beyond it (mv_w2vbert_forward_varlen; the lengths are never read back)."""
+        wav, lens_ratio, num_samples = _forward_inputs(wav, lens_ratio, None if num_samples is None else torch.as_tensor(num_samples))
+        B, L = wav.shape
+        T2 = self.num_frames(L)
+        out = torch.empty((B, T2, self.dim), dtype=torch.float32, device=wav.device)
+        if B == 0:
+            return out
+        need = c_sz()
+        check(self._cdll.mv_w2vbert_workspace_bytes(self._h, B, L, ctypes.byref(need)), self._cdll)
+        ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=wav.device)
+        form, lens = ('forward', lens_ratio) if num_samples is None else ('forward_varlen', num_samples)
+        check(self._fn(form)(self._h, wav.data_ptr(), B, L, wav.stride(0), _ptr(lens), out.data_ptr(), ws.data_ptr(), need.value,
+                             current_stream(wav)), self._cdll)
+        return out
+
+    def binstats(self, x, num_samples=None, L=None):
+        return w2vbert_binstats(x, num_samples, L, cdll=self._cdll)
+
+    def rows(self, x, mean, var, ln_weight, ln_bias, eps, num_samples=None, L=None, out=None):
+        return w2vbert_rows(x, mean, var, ln_weight, ln_bias, eps, num_samples, L, out, cdll=self._cdll)
 
 
 class Model:

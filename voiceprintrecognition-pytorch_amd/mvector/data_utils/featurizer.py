@@ -3,6 +3,10 @@
 
 Device rule
 -----------
+* ``use_hf_model=True`` with a HuggingFace Wav2Vec2-BERT model (``facebook/w2v-bert-2.0``, the reference configs' example): ``extract_features`` is
+  ``feature_projection.layer_norm`` over the SeamlessM4TFeatureExtractor's ``input_features`` (waveform * 2^15, 80-bin Kaldi log-mel, per-bin
+  normalisation over time, pairs of frames stacked to 160 columns).  CUDA tensors run all of it in ``mv_w2vbert_forward`` / ``_forward_varlen``,
+  one native call per batch; CPU tensors run the HF processor on the numpy rows and the LayerNorm in torch, as the reference does.
 * ``use_hf_model=True`` (``feature_method`` = a local folder or cached name of a HuggingFace Wav2Vec2 / WavLM model): the reference keeps
   ``outputs.extract_features`` alone -- the processor's z-score, the convolutional feature encoder and ``feature_projection.layer_norm``.  CUDA
   tensors run them in ``mv_hfenc_forward`` (``forward_varlen``: ``mv_hfenc_forward_varlen``, one call per batch) and stay on the device (the reference calls ``.numpy()`` and cannot take them at all); CPU tensors run
@@ -32,7 +36,7 @@ class AudioFeaturizer(nn.Module):
     """音频特征器
 
     :param feature_method: 所使用的预处理方法 (``Fbank`` / ``MelSpectrogram`` / ``Spectrogram`` / ``MFCC``), or with ``use_hf_model`` the
-        local folder / cached name of a HuggingFace ``wav2vec2`` or ``wavlm`` model
+        local folder / cached name of a HuggingFace ``wav2vec2``, ``wavlm`` or ``wav2vec2-bert`` model
     :param use_hf_model: 是否使用HF上的Wav2Vec2类似模型提取音频特征
     :param method_args: 预处理方法的参数
     """
@@ -52,7 +56,7 @@ class AudioFeaturizer(nn.Module):
         _cpu_frontend.validate_args(feature_method, self._method_args)
         logger.info(f'使用【{feature_method}】提取特征')
 
-    HF_MODEL_TYPES = ('wav2vec2', 'wavlm')
+    HF_MODEL_TYPES = ('wav2vec2', 'wavlm', 'wav2vec2-bert')
 
     def _load_hf_model(self, name):
         """AutoModel / AutoFeatureExtractor as the reference loads them (featurizer.py:26-32); kept are the config, the processor's
@@ -64,20 +68,45 @@ class AudioFeaturizer(nn.Module):
         if cfg.get('model_type') not in self.HF_MODEL_TYPES:
             raise NotImplementedError(f"HuggingFace model_type {cfg.get('model_type')!r} is not implemented; the front-end is built for "
                                       f'{list(self.HF_MODEL_TYPES)}')
+        for p in model.parameters():
+            p.requires_grad_(False)
+        if cfg['model_type'] == 'wav2vec2-bert':
+            return self._keep_w2vbert(cfg, processor, model)
         if cfg.get('feat_extract_activation', 'gelu') != 'gelu':
             raise NotImplementedError(f"feat_extract_activation {cfg.get('feat_extract_activation')!r} is not implemented (only 'gelu')")
         keys = ('model_type', 'conv_dim', 'conv_kernel', 'conv_stride', 'feat_extract_norm', 'feat_extract_activation', 'conv_bias', 'layer_norm_eps')
         self._hf_cfg = {k: cfg[k] for k in keys if k in cfg}
         self._hf_cfg['do_normalize'] = bool(getattr(processor, 'do_normalize', True))
-        for p in model.parameters():
-            p.requires_grad_(False)
         # (a tuple: not registered as sub-modules -- the featurizer has no parameters of its own, and .to(device) must not move what only CPU tensors use)
         self._hf_modules = (model.feature_extractor, model.feature_projection.layer_norm)
         self._hf_sd = {k: v.detach().float().cpu() for k, v in model.state_dict().items()
                        if k.startswith('feature_extractor.') or k.startswith('feature_projection.layer_norm.')}
 
+    def _keep_w2vbert(self, cfg, processor, model):
+        """Wav2Vec2-BERT (w2v-bert-2.0): `extract_features` is feature_projection.layer_norm over the processor's input_features.  Kept are
+        feature_projection_input_dim and layer_norm_eps of the config, the processor (CPU tensors run it) with its num_mel_bins, stride,
+        sampling_rate, padding_value and padding_side, and the LayerNorm; the rest of the model is dropped.  Refused by name: what the
+        library refuses, and a processor that would not pad with zero frames on the right."""
+        keep = {'model_type': cfg['model_type'], 'feature_projection_input_dim': int(cfg['feature_projection_input_dim']),
+                'layer_norm_eps': float(cfg.get('layer_norm_eps', 1e-5))}
+        for k, want in (('num_mel_bins', 80), ('stride', 2), ('sampling_rate', 16000), ('padding_value', 0.0), ('padding_side', 'right')):
+            keep[k] = getattr(processor, k, want)
+            if keep[k] != want:
+                raise NotImplementedError(f"Wav2Vec2-BERT front-end: the processor's {k} = {keep[k]!r} is not implemented (only {want!r})")
+        if keep['feature_projection_input_dim'] != keep['num_mel_bins'] * keep['stride']:
+            raise NotImplementedError(f"Wav2Vec2-BERT front-end: feature_projection_input_dim = {keep['feature_projection_input_dim']} is not "
+                                      f"num_mel_bins * stride = {keep['num_mel_bins'] * keep['stride']}")
+        if not keep['layer_norm_eps'] > 0:
+            raise NotImplementedError(f"Wav2Vec2-BERT front-end: layer_norm_eps = {keep['layer_norm_eps']!r} is not positive")
+        self._hf_cfg = keep
+        self._hf_modules = (processor, model.feature_projection.layer_norm)
+        self._hf_sd = {k: v.detach().float().cpu() for k, v in model.state_dict().items() if k.startswith('feature_projection.layer_norm.')}
+
     def _hf_min_samples(self):
-        """the encoder's receptive field: the shortest waveform that gives a frame (400 samples on the base geometry)"""
+        """the shortest waveform the front-end featurises: the encoder's receptive field (400 samples on the base geometry); two frames, 560
+        samples, for Wav2Vec2-BERT (the per-bin variance over one frame has nothing to divide by)"""
+        if self._hf_cfg['model_type'] == 'wav2vec2-bert':
+            return 560
         n = 1
         for k, st in zip(reversed(self._hf_cfg['conv_kernel']), reversed(self._hf_cfg['conv_stride'])):
             n = (n - 1) * st + k
@@ -85,11 +114,23 @@ class AudioFeaturizer(nn.Module):
 
     def _hf_cpu(self, waveforms, input_lens_ratio):
         x = waveforms
+        if self._hf_cfg['model_type'] == 'wav2vec2-bert':   # the reference's own arithmetic: the HF processor on the numpy rows, then the LayerNorm
+            processor, ln = self._hf_modules
+            if x.shape[1] < 560:
+                raise ValueError(f'Wav2Vec2-BERT front-end: a waveform of {x.shape[1]} samples has fewer than two frames (560 samples)')
+            inputs = processor(x.numpy(), sampling_rate=16000, return_tensors='pt')
+            with torch.no_grad():
+                feature = ln(inputs['input_features'].float())
+            return self._hf_wrap(feature, input_lens_ratio)
         if self._hf_cfg['do_normalize']:   # Wav2Vec2FeatureExtractor.zero_mean_unit_var_norm over the whole (padded) row
             x = (x - x.mean(1, keepdim=True)) / torch.sqrt(x.var(1, unbiased=False, keepdim=True) + 1e-7)
         fe, ln = self._hf_modules
         with torch.no_grad():
             feature = ln(fe(x).transpose(1, 2))
+        return self._hf_wrap(feature, input_lens_ratio)
+
+    @staticmethod
+    def _hf_wrap(feature, input_lens_ratio):
         feature = feature - feature.mean(1, keepdim=True)
         if input_lens_ratio is not None:
             T = feature.shape[1]
@@ -109,7 +150,9 @@ class AudioFeaturizer(nn.Module):
         if h is None:
             from mvector import _hip
             with torch.cuda.device(key):
-                if self.use_hf_model:
+                if self.use_hf_model and self._hf_cfg['model_type'] == 'wav2vec2-bert':
+                    h = _hip.W2vBert(self._hf_cfg, self._hf_sd, device=torch.device('cuda', key))
+                elif self.use_hf_model:
                     h = _hip.HfEncoder(self._hf_cfg, self._hf_sd, device=torch.device('cuda', key))
                 elif self._feature_method == 'Fbank':
                     h = _hip.Fbank(self._method_args)
@@ -140,7 +183,7 @@ class AudioFeaturizer(nn.Module):
         own length (own frame count, own padding, own time mean, own MFCC dB floor) and rows beyond it are zero -- what the
         reference's evaluation path gets from per-utterance featurisation + ``collate_fn`` padding.  CUDA tensors: one native
         call per batch for every method and for the HuggingFace front-end (``mv_*_forward_varlen``, ``mv_hfenc_forward_varlen``), no per-row
-        loop and no host synchronisation; a row too short for the transform -- below the encoder's receptive field (400 samples) with
+        loop and no host synchronisation; a row too short for the transform -- below the encoder's receptive field (400 samples; two frames, 560 samples, for Wav2Vec2-BERT) with
         ``use_hf_model`` -- is all zero.  CPU tensors: the per-row loop, with the same all-zero rows."""
         if waveforms.dtype != torch.float32:
             waveforms = waveforms.float()
@@ -162,7 +205,10 @@ class AudioFeaturizer(nn.Module):
     @property
     def feature_dim(self):
         if self.use_hf_model:
-            return self._hf_cfg['conv_dim'][-1]   # what the reference's 1 s probe returns (featurizer.py:35-39): extract_features.shape[2]
+            # what the reference's 1 s probe returns (featurizer.py:35-39): extract_features.shape[2]
+            if self._hf_cfg['model_type'] == 'wav2vec2-bert':
+                return self._hf_cfg['feature_projection_input_dim']
+            return self._hf_cfg['conv_dim'][-1]
         if self._feature_method == 'MelSpectrogram':
             return self._method_args.get('n_mels', 128)
         elif self._feature_method == 'Spectrogram':
