@@ -1029,6 +1029,7 @@ int mv_pad_rows_f32(const float* src, int32_t F, float* dst, int64_t ldd, int64_
 #define MV_PROF_FBANK 1
 #define MV_PROF_CONV2D 2 /* work = 2*B*Ho*Wo*cin*cout*ks*ks FLOPs on the layer's own (unpadded) channel counts */
 #define MV_PROF_CONV1D_RING 3 /* since ABI 5: the launches of the dense 1x1 persistent (ring) GEMM alone -- a subset of MV_PROF_CONV1D, which keeps counting them */
+#define MV_PROF_MARGIN_SUMS 4 /* since ABI 5: the second pass of mv_margin_ce_forward over the logits (margin_seg_kernel<.., 1>); work = the logits' bytes */
 int mv_profile_enable(int32_t on);
 int mv_profile_read(int32_t kernel_class, int32_t* calls, double* total_ms, double* total_work, int32_t reset);
 
@@ -1344,6 +1345,69 @@ size_t mv_wave_gather_workspace_bytes(int32_t B, int32_t max_regions);
 int mv_wave_gather_f32(const float* wav, int64_t wav_stride, const int64_t* num_samples, const int32_t* num_regions, const int32_t* regions,
                        int32_t max_regions, int32_t B, int64_t L, float* out, int64_t out_stride, int64_t L_out, int64_t* out_samples,
                        void* workspace, size_t workspace_bytes, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Margin-softmax classification losses (added within ABI 5): CE, AM, ARM, AAM and sub-centre AAM as one fused forward and one fused backward
+ * over the logit matrix (csrc/marginloss.hip).
+ *
+ * logits [B, N * K]: row b starts at logits + b * stride elements (stride >= N * K), element type `dtype` (MV_DT_F32, MV_DT_F16, MV_DT_BF16;
+ *   16-bit elements are converted to fp32 on load, everything after that is fp32 or fp64 whatever the dtype).  labels int64 [B] on the device.
+ * Centre cosine: c_j = max_k logits[b, j * K + k], the lowest k on ties (that column receives the gradient).  K = 1 unless kind is
+ *   MV_LOSS_SUBCENTER.
+ * z_j, fp32, one correctly rounded operation at a time in this order, no contraction (y = labels[b], s = cfg.scale):
+ *     MV_LOSS_CE        z_j = c_j
+ *     MV_LOSS_AM        z_j = s * c_j (j != y),  z_y = s * (c_y - margin)
+ *     MV_LOSS_ARM       the AM values, then z_j <- (z_j - z_y < 0) ? 0 : z_j  (a zeroed column stays in the softmax with value 0)
+ *     MV_LOSS_AAM, MV_LOSS_SUBCENTER
+ *                       z_j = s * c_j (j != y);  sine = sqrt(1 - c_y * c_y), phi = c_y * cos_m - sine * sin_m,
+ *                       z_y = s * (c_y > 0 ? phi : c_y) with easy_margin, else s * (c_y > th ? phi : c_y - mmm).  No clamp: |c_y| > 1 is NaN.
+ *   cos_m, sin_m, th, mmm are the caller's (cos(margin), sin(margin), cos(pi - margin), 1 + cos(pi - margin), formed in double, passed as floats).
+ * Row loss, fp64: lse = M + log(sum_j exp(z_j - M)), M = max_j z_j;  loss_b = (1 - eps) (lse - z_y) + eps (lse - sum_j z_j / N)  (the second
+ *   term only for eps > 0);  loss = sum_b loss_b / B.  loss and loss_rows are these rounded once to fp32.
+ * Summation order (what makes a row's bits its own): the N centres are cut into segments of MV_MARGIN_SEG; inside a segment thread t of the 256
+ *   owns the chunks t, t + 256, ... of MV_MARGIN_CHUNK consecutive centres and adds exp(z_j - M) and z_j in ascending j, in fp64; the 256
+ *   partial sums are folded by a halving tree (red[t] += red[t + h], h = 128 .. 1); the segments are added in ascending order; the rows of the batch
+ *   mean in ascending b.  M is exact in any order.  None of it depends on B, on the other rows, on the dtype, on the row's alignment (16-byte
+ *   loads where the row starts on a 16-byte boundary and K <= 3, element loads otherwise -- the same values to the same threads), on what the
+ *   buffers held or on the stream.  No floating-point atomics, no workgroup waits for another: three ordinary launches (segment maxima; segment
+ *   sums; one workgroup that finishes rows and mean), nothing allocated, no synchronisation.
+ * Outputs of the forward: loss fp32 [1]; loss_rows fp32 [B]; pred int32 [B] = argmax_j c_j, the lowest j on ties, NaN cosines never chosen
+ *   (0 for a row of NaNs); saved fp64 [B, MV_MARGIN_SAVED]: {M, log(sum_j exp(z_j - M)), z_y, loss_b}.
+ * Backward: out[b, j * K + k] = (g / B) (p_j - q_j) dz_j [k = argmax], p_j = exp(z_j - lse) in fp64, q_j = (1 - eps) [j = y] + eps / N,
+ *   dz_j = s (1 for CE; 0 on ARM's zeroed columns; s (cos_m + c_y sin_m / sqrt(1 - c_y c_y)) on the phi branch of the target), rounded once to
+ *   the dtype.  g = *grad_out, an fp32 scalar on the device.  One element-wise launch; every row scalar comes from `saved`, a thread reads the
+ *   K-groups it owns before it writes them, so out == logits with out_stride == stride (in place) is allowed; any other overlap is refused.
+ * A label outside [0, N): no access outside the row; loss_rows[b], loss and every column of the row's gradient are NaN, pred[b] is valid,
+ *   other rows are as without it.  A NaN logit: the row's loss and its gradient (at the argmax columns) are NaN.
+ * workspace: device memory, 16-byte aligned, mv_margin_ce_workspace_bytes(B, N, K) bytes (0 for arguments the forward refuses); needs no
+ *   initialising.  B = 0 returns MV_OK and touches nothing.
+ * MV_ERR_INVALID_ARGUMENT with a message: a null pointer; negative B or N (N = 0 with B > 0 too); K outside 1 .. 8; K != 1 with a kind other than
+ *   MV_LOSS_SUBCENTER; stride (out_stride) below N * K; eps outside [0, 1); an unknown kind or dtype; N * K above 2^31 - 1; B * stride
+ *   beyond int64; B * segments above 2^31 - 1; out overlapping logits other than in place.  MV_ERR_WORKSPACE: a short or misaligned workspace.
+ * ------------------------------------------------------------------------------------------------ */
+#define MV_LOSS_CE 0
+#define MV_LOSS_AM 1
+#define MV_LOSS_ARM 2
+#define MV_LOSS_AAM 3
+#define MV_LOSS_SUBCENTER 4
+#define MV_DT_BF16 2
+#define MV_MARGIN_SEG 4096
+#define MV_MARGIN_CHUNK 8
+#define MV_MARGIN_SAVED 4
+typedef struct {
+    int32_t kind;        /* MV_LOSS_* */
+    int32_t K;           /* sub-centres per class */
+    int32_t easy_margin; /* AAM / sub-centre: the c_y > 0 rule */
+    float margin;        /* AM / ARM */
+    float scale;
+    float cos_m, sin_m, th, mmm; /* AAM / sub-centre */
+    float eps;           /* label smoothing */
+} MvMarginLossCfg;
+size_t mv_margin_ce_workspace_bytes(int64_t B, int64_t N, int32_t K);
+int mv_margin_ce_forward(const MvMarginLossCfg* cfg, const void* logits, int32_t dtype, const int64_t* labels, int64_t B, int64_t N, int64_t stride,
+                         float* loss, float* loss_rows, int32_t* pred, double* saved, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+int mv_margin_ce_backward(const MvMarginLossCfg* cfg, const void* logits, int32_t dtype, const int64_t* labels, int64_t B, int64_t N, int64_t stride,
+                          const double* saved, const float* grad_out, void* out, int64_t out_stride, mv_stream_t stream);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

@@ -350,6 +350,9 @@ _SIGNATURES = {
     'mv_vad_regions_i32': (c_i32, [ctypes.POINTER(MvVadSmoothCfg), c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_wave_gather_workspace_bytes': (c_sz, [c_i32, c_i32]),
     'mv_wave_gather_f32': (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, c_sz, c_vp]),
+    'mv_margin_ce_workspace_bytes': (c_sz, [c_i64, c_i64, c_i32]),
+    'mv_margin_ce_forward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_margin_ce_backward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1191,8 +1194,95 @@ def score_norm(scores, trial_stats, enroll_stats, mode='s', out=None, cdll=None)
     return out
 
 
+MV_LOSS_CE, MV_LOSS_AM, MV_LOSS_ARM, MV_LOSS_AAM, MV_LOSS_SUBCENTER = 0, 1, 2, 3, 4
+MV_DT_BF16 = 2
+MV_MARGIN_SEG, MV_MARGIN_CHUNK, MV_MARGIN_SAVED = 4096, 8, 4
+LOSS_KINDS = {'ce': MV_LOSS_CE, 'am': MV_LOSS_AM, 'arm': MV_LOSS_ARM, 'aam': MV_LOSS_AAM, 'subcenter': MV_LOSS_SUBCENTER}
+_MARGIN_DTYPES = {torch.float32: MV_DT_F32, torch.float16: MV_DT_F16, torch.bfloat16: MV_DT_BF16}
+
+
+class MvMarginLossCfg(ctypes.Structure):
+    _fields_ = [('kind', c_i32), ('K', c_i32), ('easy_margin', c_i32), ('margin', c_f32), ('scale', c_f32), ('cos_m', c_f32), ('sin_m', c_f32),
+                ('th', c_f32), ('mmm', c_f32), ('eps', c_f32)]
+
+
+def margin_cfg(kind, margin=0.2, scale=32.0, easy_margin=False, K=1, label_smoothing=0.0):
+    """MvMarginLossCfg of a loss: ``kind`` a key of LOSS_KINDS or an MV_LOSS_* code; cos_m, sin_m, th and mmm formed here in double from
+    ``margin`` as the reference's constructors form them, then passed as floats"""
+    import math
+    cfg = MvMarginLossCfg()
+    if isinstance(kind, str):
+        if kind not in LOSS_KINDS:
+            raise ValueError(f'margin loss: kind {kind!r} is not one of {sorted(LOSS_KINDS)}')
+        kind = LOSS_KINDS[kind]
+    cfg.kind, cfg.K, cfg.easy_margin = int(kind), int(K), int(bool(easy_margin))
+    cfg.margin, cfg.scale, cfg.eps = float(margin), float(scale), float(label_smoothing)
+    cfg.cos_m, cfg.sin_m = math.cos(margin), math.sin(margin)
+    cfg.th, cfg.mmm = math.cos(math.pi - margin), 1.0 + math.cos(math.pi - margin)
+    return cfg
+
+
+def _margin_geometry(logits, labels, cfg, who):
+    if logits.dim() != 2 or logits.dtype not in _MARGIN_DTYPES:
+        raise ValueError(f'{who}: logits must be a 2-D fp32, fp16 or bf16 tensor, got {tuple(logits.shape)} {logits.dtype}')
+    if logits.shape[1] > 1 and logits.stride(1) != 1:
+        raise ValueError(f'{who}: the logits need unit stride along the classes')
+    B, cols = logits.shape
+    K = max(int(cfg.K), 1)
+    if cols % K:
+        raise ValueError(f'{who}: {cols} columns are no multiple of K = {K}')
+    labels = labels.to(device=logits.device, dtype=torch.int64).contiguous()
+    if labels.shape != (B,):
+        raise ValueError(f'{who}: labels must have shape ({B},), got {tuple(labels.shape)}')
+    stride = logits.stride(0) if B > 1 else max(logits.stride(0), cols)
+    return labels, B, cols // K, stride
+
+
+def margin_ce_forward(logits, labels, kind, margin=0.2, scale=32.0, easy_margin=False, K=1, label_smoothing=0.0, cdll=None):
+    """The fused margin-softmax forward (mv_margin_ce_forward) on ``logits`` [B, N * K] (fp32 / fp16 / bf16, any row stride) and ``labels`` [B] ->
+    (loss fp32 scalar, loss_rows fp32 [B], pred int32 [B], saved fp64 [B, MV_MARGIN_SAVED] = {max z, log sum exp(z - max), z_y, row loss}), all on
+    the logits' device and stream.  ``kind``: 'ce', 'am', 'arm', 'aam' or 'subcenter'.  Nothing synchronises."""
+    cdll = cdll or lib()
+    cfg = margin_cfg(kind, margin, scale, easy_margin, K, label_smoothing)
+    labels, B, N, stride = _margin_geometry(logits, labels, cfg, 'margin_ce_forward')
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    loss_rows = torch.empty((B,), dtype=torch.float32, device=dev)
+    pred = torch.empty((B,), dtype=torch.int32, device=dev)
+    saved = torch.empty((B, MV_MARGIN_SAVED), dtype=torch.float64, device=dev)
+    nbytes = int(cdll.mv_margin_ce_workspace_bytes(B, N, int(cfg.K)))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    check(cdll.mv_margin_ce_forward(ctypes.byref(cfg), logits.data_ptr(), _MARGIN_DTYPES[logits.dtype], labels.data_ptr(), B, N, stride,
+                                    loss.data_ptr(), loss_rows.data_ptr(), pred.data_ptr(), saved.data_ptr(), ws.data_ptr(), nbytes,
+                                    current_stream(logits)), cdll)
+    if B == 0:
+        loss.fill_(float('nan'))   # the mean of no rows, as torch's
+    return loss, loss_rows, pred, saved
+
+
+def margin_ce_backward(logits, labels, saved, grad_out, kind, margin=0.2, scale=32.0, easy_margin=False, K=1, label_smoothing=0.0, out=None,
+                       cdll=None):
+    """The gradient of the loss of ``margin_ce_forward`` with respect to the logits, in the logits' dtype (mv_margin_ce_backward): ``saved`` from the
+    forward of the same arguments, ``grad_out`` the upstream scalar as an fp32 tensor on the device (read there: nothing synchronises).  ``out``:
+    where to write; ``out=logits`` runs in place, any other overlap is refused."""
+    cdll = cdll or lib()
+    cfg = margin_cfg(kind, margin, scale, easy_margin, K, label_smoothing)
+    labels, B, N, stride = _margin_geometry(logits, labels, cfg, 'margin_ce_backward')
+    grad_out = grad_out.to(device=logits.device, dtype=torch.float32).reshape(-1)
+    assert grad_out.numel() == 1, 'margin_ce_backward: grad_out is not a scalar'
+    assert saved.shape == (B, MV_MARGIN_SAVED) and saved.dtype == torch.float64 and saved.is_contiguous() and saved.device == logits.device
+    if out is None:
+        out = torch.empty((B, logits.shape[1]), dtype=logits.dtype, device=logits.device)
+    assert out.shape == logits.shape and out.dtype == logits.dtype and out.device == logits.device
+    assert out.shape[1] <= 1 or out.stride(1) == 1, 'margin_ce_backward: out needs unit stride along the classes'
+    out_stride = out.stride(0) if B > 1 else max(out.stride(0), out.shape[1])
+    check(cdll.mv_margin_ce_backward(ctypes.byref(cfg), logits.data_ptr(), _MARGIN_DTYPES[logits.dtype], labels.data_ptr(), B, N, stride,
+                                     saved.data_ptr(), grad_out.data_ptr(), out.data_ptr(), out_stride, current_stream(logits)), cdll)
+    return out
+
+
 MV_VAD_TILE_FRAMES = 256
-VAD_DEFAULTS = dict(frame_length=400, frame_shift=160, frames_context=0, energy_threshold=5.0, energy_mean_scale=0.5, proportion_threshold=0.6,
+VAD_DEFAULTS =dict(frame_length=400, frame_shift=160, frames_context=0, energy_threshold=5.0, energy_mean_scale=0.5, proportion_threshold=0.6,
                     scale=32768.0)   # compute-vad's own; scale: [-1, 1) samples in the int16 range its thresholds assume
 
 
