@@ -1409,6 +1409,128 @@ int mv_margin_ce_forward(const MvMarginLossCfg* cfg, const void* logits, int32_t
 int mv_margin_ce_backward(const MvMarginLossCfg* cfg, const void* logits, int32_t dtype, const int64_t* labels, int64_t B, int64_t N, int64_t stride,
                           const double* saved, const float* grad_out, void* out, int64_t out_stride, mv_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * SphereFace2 (added within ABI 5): a logistic loss over every column of the cosine matrix with a learnable bias, as one streaming forward and
+ * one element-wise backward (csrc/sphereface2.hip).  There are no sub-centres (no K).
+ *
+ * logits [B, N]: cosines; row b starts at logits + b * stride elements (stride >= N), element type `dtype` (MV_DT_F32, MV_DT_F16, MV_DT_BF16;
+ *   16-bit elements are converted to fp32 on load, everything after that is fp32 or fp64 whatever the dtype -- the torch expression evaluates
+ *   half logits in half, this is more exact).  labels int64 [B] on the device.  bias: a DEVICE pointer to one fp32 (the module's parameter),
+ *   read on the device; nothing synchronises.
+ * The front, fp32, one correctly rounded operation at a time in this order, no contraction, a correctly rounded sqrt (s = cfg.scale,
+ *   m = cfg.margin, b = *bias, c = logits[b, j], y = labels[b]):
+ *     g(x) = 2 * h^t - 1 with h = (x + 1) / 2 and h^t = (..(h * h) * h..), t - 1 multiplications from the left.  That is what torch.pow does
+ *       for t <= 3; for larger t torch calls powf, and THE PRODUCT IS THE DEFINITION here.  t is an integer in 1 .. MV_SF2_MAX_T.
+ *     MV_SF2_TYPE_C   zp = s * (g(c) - m) + b,  zn = s * (g(c) + m) + b
+ *     MV_SF2_TYPE_A   sine = sqrt(1 - c * c);  toward = c > th ? c * cos_m - sine * sin_m : c - mmm;  away = c * cos_m + sine * sin_m;
+ *                     zp = s * g(toward) + b,  zn = s * g(away) + b.  No clamp: |c| > 1 is NaN.
+ *   cos_m, sin_m, th, mmm are the caller's (cos(margin), sin(margin), cos(pi - margin), 1 + cos(pi - margin), formed in double, passed as floats).
+ *   Only the branch a column needs is evaluated: zp at j = y, zn elsewhere.  The torch expression evaluates both for every column and multiplies
+ *   one by zero, so a column whose UNUSED branch is NaN or infinite is NaN there and finite here.
+ * Behind the front, fp64 (lambda = (double)cfg.lanbuda):  softplus(x) = max(x, 0) + log1p(exp(-|x|)) and sigma(x) = (x >= 0 ? 1 : e) / (1 + e),
+ *   e = exp(-|x|), share the one exp.  l_j = lambda softplus(-zp) at the target, (1 - lambda) softplus(zn) elsewhere;
+ *   w_j = -lambda sigma(-zp) at the target, (1 - lambda) sigma(zn) elsewhere;  loss_b = sum_j l_j;  loss = sum_b loss_b / B.  loss and loss_rows
+ *   are these rounded once to fp32.
+ * Summation order: that of the margin-softmax losses above -- segments of MV_MARGIN_SEG columns; inside a segment thread t of the 256 owns the
+ *   chunks t, t + 256, ... of MV_MARGIN_CHUNK consecutive columns and adds l_j and w_j in ascending j; the 256 partial sums through the halving
+ *   tree; segments in ascending order; rows in ascending b.  Nothing depends on B, on the other rows, on the dtype, on the row's alignment
+ *   (16-byte loads where the row starts on a 16-byte boundary, element loads otherwise -- the same values to the same threads), on what the
+ *   buffers held or on the stream.  No floating-point atomics, no workgroup waits for another, nothing allocated, no synchronisation.  Forward:
+ *   two launches (segments; one workgroup that finishes rows and mean).  The loss needs no row maximum and no second read of the logits.
+ * Outputs of the forward: loss fp32 [1]; loss_rows fp32 [B]; pred int32 [B] = argmax_j c_j by the rules of mv_margin_ce_forward (the lowest j on
+ *   ties, NaN cosines never chosen, 0 for a row of NaNs); saved fp64 [B, MV_SF2_SAVED] = {loss_b, sum_j w_j}.
+ * Backward: out[b, j] = (g / B) w_j dz_j, rounded once to fp32 and for 16-bit logits from there to the dtype; g = *grad_out, an fp32 scalar on
+ *   the device.  dz_j = s t h^(t-1) dx_j in fp64: h the fp32 h of the front (that of the argument of g), h^(t-1) by t - 2 multiplications from
+ *   the left; dx = 1 for type C; for type A, with c taken to fp64 and sine = sqrt(1 - c c) there, dx = (c > th ? cos_m + c sin_m / sine : 1)
+ *   at the target and cos_m - c sin_m / sine elsewhere.  bias_grad fp32 [1] = (g / B) sum_b saved[b, 1], rows in ascending b.  One launch:
+ *   element-wise, a thread reads the chunk it owns before it writes it, so out == logits with out_stride == stride (in place) is allowed and
+ *   any other overlap is refused; one more workgroup of the same launch adds the bias gradient.  `saved` is needed for the bias gradient only.
+ * A label outside [0, N): no access outside the row; loss_rows[b], loss, every column of the row's gradient and bias_grad are NaN, pred[b] is
+ *   valid, the loss_rows and gradients of the other rows are as without it.  A NaN logit: its row's loss, its own gradient and bias_grad are NaN.
+ * workspace: device memory, 16-byte aligned, mv_sphereface2_workspace_bytes(B, N) bytes (0 for arguments the forward refuses); needs no
+ *   initialising.  B = 0 returns MV_OK and touches nothing.
+ * MV_ERR_INVALID_ARGUMENT with a message: a null pointer (cfg, logits, labels, bias, an output, saved, grad_out, out, bias_grad, workspace);
+ *   negative B or N (N = 0 with B > 0 too); an unknown margin_type or dtype; t outside 1 .. 8; lanbuda outside [0, 1]; stride (out_stride)
+ *   below N; N above 2^31 - 1; B above 2^31 - 1; B * stride (B * out_stride) beyond int64; B * segments above 2^31 - 1; in the backward
+ *   B * column tiles + 1 above 2^31 - 1 (a column tile is 256 chunks of MV_MARGIN_CHUNK columns; the + 1 is the bias gradient's workgroup); out
+ *   overlapping logits other than in place.  MV_ERR_WORKSPACE: a short or misaligned workspace.
+ * ------------------------------------------------------------------------------------------------ */
+#define MV_SF2_TYPE_C 0
+#define MV_SF2_TYPE_A 1
+#define MV_SF2_MAX_T 8
+#define MV_SF2_SAVED 2
+typedef struct {
+    int32_t margin_type; /* MV_SF2_TYPE_* */
+    int32_t t;           /* the exponent of g, 1 .. MV_SF2_MAX_T */
+    float scale;
+    float margin;        /* type C */
+    float lanbuda;       /* the weight of the target column; every other column weighs 1 - lanbuda */
+    float cos_m, sin_m, th, mmm; /* type A */
+} MvSphereFace2Cfg;
+size_t mv_sphereface2_workspace_bytes(int64_t B, int64_t N);
+int mv_sphereface2_forward(const MvSphereFace2Cfg* cfg, const void* logits, int32_t dtype, const int64_t* labels, const float* bias, int64_t B,
+                           int64_t N, int64_t stride, float* loss, float* loss_rows, int32_t* pred, double* saved, void* workspace,
+                           size_t workspace_bytes, mv_stream_t stream);
+int mv_sphereface2_backward(const MvSphereFace2Cfg* cfg, const void* logits, int32_t dtype, const int64_t* labels, const float* bias, int64_t B,
+                            int64_t N, int64_t stride, const double* saved, const float* grad_out, void* out, int64_t out_stride,
+                            float* bias_grad, mv_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Triplet loss on angular margin with batch-hard mining (added within ABI 5; csrc/triplet.hip).  The cross-entropy term of the reference's
+ * class is NOT part of these entry points: the caller adds mv_margin_ce_forward with MV_LOSS_CE.
+ *
+ * features [B, D]: row i starts at features + i * stride elements (stride >= D), element type `dtype` (MV_DT_F32, MV_DT_F16, MV_DT_BF16).  The
+ *   values are upcast on load and EVERYTHING AFTER THAT IS fp64.  labels int64 [B] on the device, any values, any multiset (the reference's
+ *   dist[is_pos].view(bs, -1) needs classes of equal size; this does not).  B <= MV_TRIPLET_MAX_B, 1 <= D <= MV_TRIPLET_MAX_D.
+ * Forward.  n_i = sqrt(sum_d f_id^2);  f^_i = f_i / n_i with cfg.normalize, f_i without;  sim_ij = sum_d f^_id f^_jd.
+ *   Order of the sums, a function of D alone: for n_i thread t of 256 adds f_id^2 by fma over d = t, t + 256, ... in ascending d from 0, and the
+ *   256 partial sums are folded by the halving tree (red[t] += red[t + h], h = 128 .. 1); sim_ij is acc = fma(f^_jd, f^_id, acc) over
+ *   d = 0 .. D - 1 in ascending d from 0 -- the same for every pair, and a product commutes, so sim_ij and sim_ji are the same bits.
+ *   Mining: ap_i = the smallest sim_ij over the rows j of i's label (i itself included), p_i its index; an_i = the largest over the rows of
+ *   another label, q_i its index.  THE LOWER INDEX WINS TIES.  A NaN candidate makes the value NaN (the lowest NaN's index), as torch.min /
+ *   torch.max.  A row with no other label has an = -inf and q = -1 (ranking term 0, `over` counts 1, no gradient through it).  The [B, B]
+ *   matrix is never stored.
+ *   Terms: rank_i = max(0, margin - (ap_i - an_i)) (NaN stays NaN);  short_i = ap_value - ap_i where that is > 0, else 0;
+ *   over_i = an_i - an_value where that is > 0, ELSE 1 (the reference's rule).
+ *   loss = sum_i rank_i / B + [add_absolute] absolute_loss_weight (sum_i over_i / B + sum_i short_i / B), rows added in ascending i; rounded once
+ *   to fp32.
+ *   Outputs: loss fp32 [1]; mined fp64 [B, 2] = {ap_i, an_i}; index int32 [B, 2] = {p_i, q_i}.  They are what the backward reads.
+ * Backward.  alpha_i = d loss / d ap_i = -[margin - (ap_i - an_i) >= 0] / B - [add_absolute][ap_value - ap_i > 0] weight / B;
+ *   beta_i = d loss / d an_i = [margin - (ap_i - an_i) >= 0] / B + [add_absolute][an_i - an_value > 0] weight / B  (the hinge passes its
+ *   gradient where its argument is >= 0, as torch.clamp; the two where-terms where their condition holds; 1 / B is formed first).
+ *   dF^_i = alpha_i f^_{p_i} + beta_i f^_{q_i} + sum_{b: p_b = i} alpha_b f^_b + sum_{b: q_b = i} beta_b f^_b: the two own terms first (the
+ *   second only for q_i >= 0), then b ascending, at one b the p term before the q term, each by fma.  It is a gather: workgroup i scans the
+ *   index lists; no atomics.  With normalize, df_i = (dF^_i - (dF^_i . f^_i) f^_i) / n_i, the dot product in the order of n_i's sum.
+ *   out[i, d] = g df_id, g = *grad_out (an fp32 scalar on the device), ROUNDED ONCE from fp64 to the features' dtype.
+ *   The coefficients are multiplied in even where they are 0, so a NaN row reaches every gradient row the torch expression's dense products
+ *   carry it to; a zero-norm row with normalize is such a row (0 / 0).  An index outside what the forward writes (p outside [0, B), q outside
+ *   [-1, B)) makes the row NaN and nothing is read through it.
+ * No hidden state: nothing is kept between the calls (the backward forms f^ and n again from the features, bit for bit); no atomics, no
+ *   workgroup waits for another, nothing allocated, no synchronisation.  Forward: three launches (rows; mining, MV_TRIPLET_ANCHORS anchors per
+ *   workgroup; one workgroup for the terms).  Backward: two (rows; the gather).
+ * workspace: device memory, 16-byte aligned, mv_triplet_workspace_bytes(B, D) bytes (0 for arguments the forward refuses): f^ in fp64 row-major
+ *   and transposed, and n; needs no initialising.  B = 0 returns MV_OK and touches nothing.
+ * MV_ERR_INVALID_ARGUMENT with a message: a null pointer; negative B or D; B above MV_TRIPLET_MAX_B; D outside 1 .. MV_TRIPLET_MAX_D; an unknown
+ *   dtype; stride (out_stride) below D; B * stride (B * out_stride) beyond int64; out overlapping features.  MV_ERR_WORKSPACE: a short or
+ *   misaligned workspace.
+ * ------------------------------------------------------------------------------------------------ */
+#define MV_TRIPLET_MAX_B 4096
+#define MV_TRIPLET_MAX_D 2048
+#define MV_TRIPLET_ANCHORS 4
+typedef struct {
+    double margin;
+    double absolute_loss_weight;
+    double ap_value, an_value;
+    int32_t normalize;    /* divide every row by its norm first */
+    int32_t add_absolute; /* the two absolute terms */
+} MvTripletCfg;
+size_t mv_triplet_workspace_bytes(int64_t B, int64_t D);
+int mv_triplet_forward(const MvTripletCfg* cfg, const void* features, int32_t dtype, const int64_t* labels, int64_t B, int64_t D, int64_t stride,
+                       float* loss, double* mined, int32_t* index, void* workspace, size_t workspace_bytes, mv_stream_t stream);
+int mv_triplet_backward(const MvTripletCfg* cfg, const void* features, int32_t dtype, int64_t B, int64_t D, int64_t stride, const double* mined,
+                        const int32_t* index, const float* grad_out, void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                        mv_stream_t stream);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

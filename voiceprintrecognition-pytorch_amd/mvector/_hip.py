@@ -353,6 +353,12 @@ _SIGNATURES = {
     'mv_margin_ce_workspace_bytes': (c_sz, [c_i64, c_i64, c_i32]),
     'mv_margin_ce_forward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     'mv_margin_ce_backward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'mv_sphereface2_workspace_bytes': (c_sz, [c_i64, c_i64]),
+    'mv_sphereface2_forward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_sphereface2_backward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    'mv_triplet_workspace_bytes': (c_sz, [c_i64, c_i64]),
+    'mv_triplet_forward': (c_i32, [c_vp, c_vp, c_i32, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    'mv_triplet_backward': (c_i32, [c_vp, c_vp, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_sz, c_vp]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1278,6 +1284,158 @@ def margin_ce_backward(logits, labels, saved, grad_out, kind, margin=0.2, scale=
     out_stride = out.stride(0) if B > 1 else max(out.stride(0), out.shape[1])
     check(cdll.mv_margin_ce_backward(ctypes.byref(cfg), logits.data_ptr(), _MARGIN_DTYPES[logits.dtype], labels.data_ptr(), B, N, stride,
                                      saved.data_ptr(), grad_out.data_ptr(), out.data_ptr(), out_stride, current_stream(logits)), cdll)
+    return out
+
+
+MV_SF2_TYPE_C, MV_SF2_TYPE_A, MV_SF2_MAX_T, MV_SF2_SAVED = 0, 1, 8, 2
+SF2_MARGIN_TYPES = {'C': MV_SF2_TYPE_C, 'A': MV_SF2_TYPE_A}
+MV_TRIPLET_MAX_B, MV_TRIPLET_MAX_D, MV_TRIPLET_ANCHORS = 4096, 2048, 4
+
+
+class MvSphereFace2Cfg(ctypes.Structure):
+    _fields_ = [('margin_type', c_i32), ('t', c_i32), ('scale', c_f32), ('margin', c_f32), ('lanbuda', c_f32), ('cos_m', c_f32), ('sin_m', c_f32),
+                ('th', c_f32), ('mmm', c_f32)]
+
+
+class MvTripletCfg(ctypes.Structure):
+    _fields_ = [('margin', ctypes.c_double), ('absolute_loss_weight', ctypes.c_double), ('ap_value', ctypes.c_double),
+                ('an_value', ctypes.c_double), ('normalize', c_i32), ('add_absolute', c_i32)]
+
+
+def sphereface2_cfg(margin=0.2, scale=32.0, lanbuda=0.7, t=3, margin_type='C'):
+    """MvSphereFace2Cfg: ``margin_type`` 'C', 'A' or an MV_SF2_TYPE_* code; cos_m, sin_m, th and mmm formed here in double from ``margin`` as the
+    reference's constructor forms them, then passed as floats.  ``t`` must be an integer (the library refuses one outside 1 .. 8)."""
+    import math
+    cfg = MvSphereFace2Cfg()
+    if isinstance(margin_type, str):
+        if margin_type not in SF2_MARGIN_TYPES:
+            raise ValueError(f'sphereface2: margin_type {margin_type!r} is not one of {sorted(SF2_MARGIN_TYPES)}')
+        margin_type = SF2_MARGIN_TYPES[margin_type]
+    if int(t) != t:
+        raise ValueError(f'sphereface2: t = {t!r} is not an integer')
+    cfg.margin_type, cfg.t = int(margin_type), int(t)
+    cfg.scale, cfg.margin, cfg.lanbuda = float(scale), float(margin), float(lanbuda)
+    cfg.cos_m, cfg.sin_m = math.cos(margin), math.sin(margin)
+    cfg.th, cfg.mmm = math.cos(math.pi - margin), 1.0 + math.cos(math.pi - margin)
+    return cfg
+
+
+def triplet_cfg(margin=0.5, normalize=True, add_absolute=True, absolute_loss_weight=1.0, ap_value=0.8, an_value=0.4):
+    cfg = MvTripletCfg()
+    cfg.margin, cfg.absolute_loss_weight, cfg.ap_value, cfg.an_value = float(margin), float(absolute_loss_weight), float(ap_value), float(an_value)
+    cfg.normalize, cfg.add_absolute = int(bool(normalize)), int(bool(add_absolute))
+    return cfg
+
+
+def _rows_geometry(x, labels, who, what):
+    """(labels int64 [B] on x's device, B, columns, row stride) of a 2-D fp32 / fp16 / bf16 matrix with unit stride along its columns"""
+    if x.dim() != 2 or x.dtype not in _MARGIN_DTYPES:
+        raise ValueError(f'{who}: {what} must be a 2-D fp32, fp16 or bf16 tensor, got {tuple(x.shape)} {x.dtype}')
+    if x.shape[1] > 1 and x.stride(1) != 1:
+        raise ValueError(f'{who}: the {what} need unit stride along their columns')
+    B, cols = x.shape
+    labels = labels.to(device=x.device, dtype=torch.int64).contiguous()
+    if labels.shape != (B,):
+        raise ValueError(f'{who}: labels must have shape ({B},), got {tuple(labels.shape)}')
+    return labels, B, cols, (x.stride(0) if B > 1 else max(x.stride(0), cols))
+
+
+def _sf2_bias(bias, logits, who):
+    if bias.dtype != torch.float32 or bias.numel() != 1 or bias.device != logits.device:
+        raise ValueError(f'{who}: bias must be one fp32 value on the logits\' device, got {tuple(bias.shape)} {bias.dtype} on {bias.device}')
+    return bias.detach()
+
+
+def sphereface2_forward(logits, labels, bias, margin=0.2, scale=32.0, lanbuda=0.7, t=3, margin_type='C', cdll=None):
+    """The fused SphereFace2 forward (mv_sphereface2_forward) on the cosines ``logits`` [B, N] (fp32 / fp16 / bf16, any row stride), ``labels`` [B]
+    and ``bias``, one fp32 value ON THE LOGITS' DEVICE (read there) -> (loss fp32 scalar, loss_rows fp32 [B], pred int32 [B], saved fp64
+    [B, MV_SF2_SAVED] = {row loss, the row's sum of the column weights}), all on the logits' device and stream.  Nothing synchronises."""
+    cdll = cdll or lib()
+    cfg = sphereface2_cfg(margin, scale, lanbuda, t, margin_type)
+    labels, B, N, stride = _rows_geometry(logits, labels, 'sphereface2_forward', 'logits')
+    bias = _sf2_bias(bias, logits, 'sphereface2_forward')
+    dev = logits.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    loss_rows = torch.empty((B,), dtype=torch.float32, device=dev)
+    pred = torch.empty((B,), dtype=torch.int32, device=dev)
+    saved = torch.empty((B, MV_SF2_SAVED), dtype=torch.float64, device=dev)
+    nbytes = int(cdll.mv_sphereface2_workspace_bytes(B, N))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    check(cdll.mv_sphereface2_forward(ctypes.byref(cfg), logits.data_ptr(), _MARGIN_DTYPES[logits.dtype], labels.data_ptr(), bias.data_ptr(), B, N,
+                                      stride, loss.data_ptr(), loss_rows.data_ptr(), pred.data_ptr(), saved.data_ptr(), ws.data_ptr(), nbytes,
+                                      current_stream(logits)), cdll)
+    if B == 0:
+        loss.fill_(float('nan'))   # the mean of no rows, as torch's
+    return loss, loss_rows, pred, saved
+
+
+def sphereface2_backward(logits, labels, bias, saved, grad_out, margin=0.2, scale=32.0, lanbuda=0.7, t=3, margin_type='C', out=None, cdll=None):
+    """The gradients of the loss of ``sphereface2_forward`` (mv_sphereface2_backward) -> (grad of the logits in their dtype, bias_grad fp32 [1]):
+    ``saved`` from the forward of the same arguments, ``grad_out`` the upstream scalar as an fp32 tensor on the device (read there: nothing
+    synchronises).  ``out``: where to write the logits' gradient; ``out=logits`` runs in place, any other overlap is refused."""
+    cdll = cdll or lib()
+    cfg = sphereface2_cfg(margin, scale, lanbuda, t, margin_type)
+    labels, B, N, stride = _rows_geometry(logits, labels, 'sphereface2_backward', 'logits')
+    bias = _sf2_bias(bias, logits, 'sphereface2_backward')
+    grad_out = grad_out.to(device=logits.device, dtype=torch.float32).reshape(-1)
+    assert grad_out.numel() == 1, 'sphereface2_backward: grad_out is not a scalar'
+    assert saved.shape == (B, MV_SF2_SAVED) and saved.dtype == torch.float64 and saved.is_contiguous() and saved.device == logits.device
+    if out is None:
+        out = torch.empty((B, N), dtype=logits.dtype, device=logits.device)
+    assert out.shape == logits.shape and out.dtype == logits.dtype and out.device == logits.device
+    assert out.shape[1] <= 1 or out.stride(1) == 1, 'sphereface2_backward: out needs unit stride along the classes'
+    out_stride = out.stride(0) if B > 1 else max(out.stride(0), N)
+    bias_grad = torch.zeros((1,), dtype=torch.float32, device=logits.device) if B == 0 else torch.empty((1,), dtype=torch.float32, device=logits.device)
+    check(cdll.mv_sphereface2_backward(ctypes.byref(cfg), logits.data_ptr(), _MARGIN_DTYPES[logits.dtype], labels.data_ptr(), bias.data_ptr(), B, N,
+                                       stride, saved.data_ptr(), grad_out.data_ptr(), out.data_ptr(), out_stride, bias_grad.data_ptr(),
+                                       current_stream(logits)), cdll)
+    return out, bias_grad
+
+
+def triplet_forward(features, labels, margin=0.5, normalize=True, add_absolute=True, absolute_loss_weight=1.0, ap_value=0.8, an_value=0.4,
+                    cdll=None):
+    """The batch-hard triplet term (mv_triplet_forward; WITHOUT the cross-entropy of the class) on ``features`` [B, D] (fp32 / fp16 / bf16, any
+    row stride) and ``labels`` [B] -> (loss fp32 scalar, mined fp64 [B, 2] = {hardest positive, hardest negative similarity}, index int32
+    [B, 2] = their rows, -1 for no negative), all on the features' device and stream.  Nothing synchronises."""
+    cdll = cdll or lib()
+    cfg = triplet_cfg(margin, normalize, add_absolute, absolute_loss_weight, ap_value, an_value)
+    labels, B, D, stride = _rows_geometry(features, labels, 'triplet_forward', 'features')
+    dev = features.device
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    mined = torch.empty((B, 2), dtype=torch.float64, device=dev)
+    index = torch.empty((B, 2), dtype=torch.int32, device=dev)
+    nbytes = int(cdll.mv_triplet_workspace_bytes(B, D))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    check(cdll.mv_triplet_forward(ctypes.byref(cfg), features.data_ptr(), _MARGIN_DTYPES[features.dtype], labels.data_ptr(), B, D, stride,
+                                  loss.data_ptr(), mined.data_ptr(), index.data_ptr(), ws.data_ptr(), nbytes, current_stream(features)), cdll)
+    if B == 0:
+        loss.fill_(float('nan'))
+    return loss, mined, index
+
+
+def triplet_backward(features, labels, mined, index, grad_out, margin=0.5, normalize=True, add_absolute=True, absolute_loss_weight=1.0,
+                     ap_value=0.8, an_value=0.4, out=None, cdll=None):
+    """The gradient of the loss of ``triplet_forward`` with respect to the features, in their dtype (mv_triplet_backward): ``mined`` and ``index``
+    from the forward of the same arguments (``labels`` is only checked for its shape: the mined rows carry what the gradient needs), ``grad_out``
+    the upstream scalar as an fp32 tensor on the device."""
+    cdll = cdll or lib()
+    cfg = triplet_cfg(margin, normalize, add_absolute, absolute_loss_weight, ap_value, an_value)
+    labels, B, D, stride = _rows_geometry(features, labels, 'triplet_backward', 'features')
+    dev = features.device
+    grad_out = grad_out.to(device=dev, dtype=torch.float32).reshape(-1)
+    assert grad_out.numel() == 1, 'triplet_backward: grad_out is not a scalar'
+    assert mined.shape == (B, 2) and mined.dtype == torch.float64 and mined.is_contiguous() and mined.device == dev
+    assert index.shape == (B, 2) and index.dtype == torch.int32 and index.is_contiguous() and index.device == dev
+    if out is None:
+        out = torch.empty((B, D), dtype=features.dtype, device=dev)
+    assert out.shape == features.shape and out.dtype == features.dtype and out.device == dev
+    assert out.shape[1] <= 1 or out.stride(1) == 1, 'triplet_backward: out needs unit stride along the features'
+    out_stride = out.stride(0) if B > 1 else max(out.stride(0), D)
+    nbytes = int(cdll.mv_triplet_workspace_bytes(B, D))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    check(cdll.mv_triplet_backward(ctypes.byref(cfg), features.data_ptr(), _MARGIN_DTYPES[features.dtype], B, D, stride, mined.data_ptr(),
+                                   index.data_ptr(), grad_out.data_ptr(), out.data_ptr(), out_stride, ws.data_ptr(), nbytes,
+                                   current_stream(features)), cdll)
     return out
 
 

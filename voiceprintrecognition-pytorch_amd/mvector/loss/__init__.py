@@ -3,8 +3,9 @@ AAMLoss) with ``loss_args``, the reference's contract (mvector/loss/__init__.py)
 
 ``CELoss``, ``AMLoss``, ``ARMLoss``, ``AAMLoss`` and ``SubCenterLoss`` are one softmax family (mvector/loss/softmax_family.py): on 2-D CUDA
 logits of fp32, fp16 or bf16 they run the fused native forward and backward (csrc/marginloss.hip) behind one ``torch.autograd.Function``;
-on CPU tensors and every other dtype they run the same definition as a torch expression.  ``SphereFace2`` and ``TripletAngularMarginLoss``
-run their torch expression on both devices."""
+on CPU tensors and every other dtype they run the same definition as a torch expression.  ``SphereFace2`` (csrc/sphereface2.hip) and
+``TripletAngularMarginLoss`` (csrc/triplet.hip, its cross-entropy through the family's native function) take their native paths under the
+same conditions, and run their torch expressions otherwise."""
 from mvector.utils.logger import logger
 from .softmax_family import AAMLoss, AMLoss, ARMLoss, CELoss, SubCenterLoss
 from .sphereface2 import SphereFace2
